@@ -12,15 +12,22 @@ them in flight, each on its own context and HIP stream, so that a launch's drain
 paths of its last samples, ~0.5 ms) and its gather overlap the next launch (--inflight 1: serialized).
 Inputs (the 1.4 KB scene) are resident in HBM before the timed region; nothing is skipped.
 
-With --config ff (the default) the same run also measures BASELINE.json configs[2] -- MIS +
-HG g=0.5, 1024^2 x 1024 spp, the north-star workload -- and reports it in the line's "north_star"
-object next to the reference's MIS rate on this host (--no-north-star skips it).  The CPU leg
-(cpu_baseline, rank 0 at N=1) times the reference program itself, built from its own sources by
-oracle/Makefile: with a per-thread RNG (the fair flavour) and as written; and it checks sampled
-rows of the GPU image against the reference's own functions (rmse_vs_reference_per_channel).
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step);
+--dump-outputs DIR also writes the last timed step's image to DIR/image.npy.  Everything else is
+behind --full:
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config ff|mis|dense|mis4k] [--no-cpu]
-                    [--no-north-star] [--inflight D]
+With --full the line also carries the roofline object (a counting build of the kernel, serialized
+launches for the kernel time, the build's committed PMC profile) and, at N > 1, every rank's kernel
+time and the gather's.  With --full --config ff (the default config) the same run also measures
+BASELINE.json configs[2] -- MIS + HG g=0.5, 1024^2 x 1024 spp, the north-star workload -- and
+reports it in the line's "north_star" object next to the reference's MIS rate on this host
+(--no-north-star skips it).  The CPU leg of --full (cpu_baseline, rank 0 at N=1; --no-cpu skips it)
+times the reference program itself, built from its own sources by oracle/Makefile: with a
+per-thread RNG (the fair flavour) and as written; and it checks sampled rows of the GPU image
+against the reference's own functions (rmse_vs_reference_per_channel).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config ff|mis|dense|mis4k] [--inflight D]
+                    [--dump-outputs DIR] [--full [--no-cpu] [--no-north-star]]
 """
 from __future__ import annotations
 
@@ -372,8 +379,10 @@ def pmc_fp64_flop(prof):
 def measure(c: dict, args, tracers, streams, world: int, rank: int, dev) -> dict:
     """Times args.steps images of config `c` (after args.warmup untimed ones), every rank
     rendering its row bands, strips gathered to rank 0 (N > 1); max over ranks.  Returns the
-    whole-job rate, the kernel's serialized launch time (HIP events on the launch stream) and the
-    ray-sphere tests per sample of the reference algorithm on this workload."""
+    whole-job rate and rank 0's image of the last timed step; with --full also the kernel's
+    serialized launch time (HIP events on the launch stream), the gather's (N > 1) and the
+    ray-sphere tests per sample of the reference algorithm on this workload, each from launches
+    of its own outside the timed region."""
     import torch.distributed as tdist
 
     dist = tdist if world > 1 else None
@@ -390,11 +399,13 @@ def measure(c: dict, args, tracers, streams, world: int, rank: int, dev) -> dict
     images = [torch.empty((H, W, 3), dtype=torch.float32, device=dev) if rank == 0 else None for _ in range(D)]
 
     # ray-sphere tests per sample of the reference algorithm on this workload (counting build of
-    # the same kernel, untimed; 1/16 of the spp -- the per-sample mean is what is needed)
-    cnt_cfg = vpt.RenderConfig(**{**c, "spp": max(1, SPP // 16)}, seed=0x5EED0001, band_rows=band,
-                               band_stride=world, band_offset=rank)
-    tests, iters = tracer.count_work(cnt_cfg)
-    T = tests / (rows * W * cnt_cfg.spp)
+    # the same kernel, untimed; 1/16 of the spp -- the per-sample mean is what is needed): --full only
+    T = None
+    if args.full:
+        cnt_cfg = vpt.RenderConfig(**{**c, "spp": max(1, SPP // 16)}, seed=0x5EED0001, band_rows=band,
+                                   band_stride=world, band_offset=rank)
+        tests, iters = tracer.count_work(cnt_cfg)
+        T = tests / (rows * W * cnt_cfg.spp)
 
     def step(k, ev=None):
         """step k: the whole image on slot k % D -- render the rank's bands, then (N > 1) the RCCL
@@ -423,16 +434,23 @@ def measure(c: dict, args, tracers, streams, world: int, rank: int, dev) -> dict
     if dist:
         dist.barrier()
     torch.cuda.synchronize(dev)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+           for _ in range(args.steps if args.full and D == 1 else 0)]
     t0 = time.perf_counter()
     for k in range(args.steps):
-        step(k, evs[k] if D == 1 else None)
+        step(k, evs[k] if evs else None)
     torch.cuda.synchronize(dev)
     if dist:
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
-    if D > 1:
+    img = None
+    if rank == 0:
+        if args.full:
+            for j in range(1, min(D, args.steps)):  # every slot rendered the same image
+                assert torch.equal(images[j], images[0]), "in-flight slots disagree"
+        img = images[(args.steps - 1) % D].float().cpu().numpy()  # what the last timed step computed
+    if args.full and D > 1:
         # overlapping launches make per-launch events meaningless: the kernel's duration for the
         # roofline comes from serialized launches of the same render, on one stream, right after
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -442,9 +460,9 @@ def measure(c: dict, args, tracers, streams, world: int, rank: int, dev) -> dict
             tracer.render_device(cfg, outs[0].data_ptr(), stream.cuda_stream)
             b.record(stream)
         torch.cuda.synchronize(dev)
-    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
+    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs])) if args.full else None
     gather_ms = None
-    if dist:
+    if dist and args.full:
         # the gather alone: all ranks' strips ready (barrier), rank 0's stream timed around the collective
         # and its copy into the image, serialized, a few times (outside the timed region)
         torch.cuda.synchronize(dev)
@@ -466,19 +484,14 @@ def measure(c: dict, args, tracers, streams, world: int, rank: int, dev) -> dict
     rank_elapsed, rank_kern_ms = [elapsed], [kern_ms]
     if dist:
         tdev = dev if args.dist_backend == "nccl" else torch.device("cpu")
-        t = torch.tensor([elapsed, kern_ms], dtype=torch.float64, device=tdev)
+        t = torch.tensor([elapsed, kern_ms or 0.0], dtype=torch.float64, device=tdev)
         every = [torch.empty_like(t) for _ in range(world)]
         dist.all_gather(every, t)
         rank_elapsed = [float(x[0].item()) for x in every]
-        rank_kern_ms = [float(x[1].item()) for x in every]
+        rank_kern_ms = [float(x[1].item()) for x in every] if args.full else [None] * world
         elapsed = max(rank_elapsed)  # the job's time is the slowest rank's
-    img = None
-    if rank == 0:
-        for j in range(1, min(D, args.steps)):  # every slot rendered the same image
-            assert torch.equal(images[j], images[0]), "in-flight slots disagree"
-        img = images[0].float().cpu().numpy()
     launch_samples = rows * W * SPP
-    achieved = launch_samples * FLOP_PER_TEST * T / (kern_ms * 1e-3) / 1e12
+    achieved = launch_samples * FLOP_PER_TEST * T / (kern_ms * 1e-3) / 1e12 if args.full else None
     return {"value": H * W * SPP * args.steps / elapsed / 1e6, "elapsed": elapsed, "kern_ms": kern_ms, "T": T,
             "achieved": achieved, "launch_samples": launch_samples, "image": img, "band": band, "D": D,
             "nevents": len(evs), "rank_elapsed": rank_elapsed, "rank_kern_ms": rank_kern_ms, "gather_ms": gather_ms}
@@ -564,15 +577,78 @@ def launch_ranks(n: int, cmd: list, env=None, timeout=None) -> int:
     return rc
 
 
+DUMP_LIMIT = 60_000_000  # bytes of array data --dump-outputs writes at most (64 MB with room to spare)
+
+
+def dump_outputs(directory: str, img: np.ndarray) -> None:
+    """--dump-outputs: the float32 image (file rows x width x RGB) that rank 0 holds after the last timed
+    step -- what a caller of the timed path receives -- as <directory>/image.npy.  The inputs are fixed
+    (scene, camera, medium, seed 0x5EED0001), so two builds run with the same arguments write comparable
+    files.  An image above DUMP_LIMIT is written as a sample of whole rows: the sorted choice of a
+    generator seeded with a constant, the same rows in every run."""
+    os.makedirs(directory, exist_ok=True)
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    keep = DUMP_LIMIT // max(1, img[0].nbytes)
+    if keep < img.shape[0]:
+        img = img[np.sort(np.random.default_rng(0x5EED0001).choice(img.shape[0], size=keep, replace=False))]
+    np.save(os.path.join(directory, "image.npy"), img)
+
+
+def roofline(m: dict, c: dict, prof, D: int) -> dict:
+    """The line's `roofline` object (--full): the reference-equivalent intersection flops over the kernel's
+    serialized launch time, and what the build's PMC profile adds (pmc_fields, pmc_fp64_flop)"""
+    kern_ms, T = m["kern_ms"], m["T"]
+    full = pmc_fp64_flop(prof)
+    return {
+        "bound": "fp64_valu",
+        "achieved": round(m["achieved"], 4),
+        "peak": FP64_PEAK_TFLOPS,
+        "unit": "TFLOP/s",
+        "frac": round(m["achieved"] / FP64_PEAK_TFLOPS, 5),
+        "peak_no_fma": FP64_PEAK_TFLOPS / 2,
+        "frac_of_no_fma_peak": round(m["achieved"] / (FP64_PEAK_TFLOPS / 2), 5),
+        "traffic": pmc_traffic(prof),
+        **pmc_fields(prof, kern_ms, fb_bytes(c), partial_bytes(c)),
+        "kernel": (f"pool_kernel<{c['estimator']}> + reduce_kernel (one launch pair)"
+                   if c["estimator"] not in ("ray_marching",) else "render_kernel_simple (one lane per pixel)"),
+        "kernel_ms": round(kern_ms, 3),
+        "kernel_ms_from": "HIP events around each launch of the timed steps on their stream" if D == 1 else
+                          f"HIP events around {m['nevents']} serialized launches of the same render on one stream, "
+                          f"right after the timed region (its {D} in-flight steps overlap)",
+        "work_basis": "reference-equivalent: the ray-sphere tests the REFERENCE algorithm performs on this "
+                      "workload (counting build), including the tests of rays the kernel's exact shortcuts "
+                      "never cast (pLight toward a sphere light, MISv2's BSDF ray, the H5 point-light cone); "
+                      "achieved/frac are therefore not executed FP64 work -- all_fp64_* is",
+        "algorithmic": f"{FLOP_PER_TEST} FP64 flop x {T:.2f} ray-sphere tests per sample (SURVEY 8d) x "
+                       f"{m['launch_samples']} samples per launch",
+        "all_fp64_tflops": round(full / (kern_ms * 1e-3) / 1e12, 3) if full else None,
+        "all_fp64_frac": round(full / (kern_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS, 4) if full else None,
+        "note": "FP64 VALU bound (no dense contraction exists, no MFMA): peak 78.6 TFLOP/s counts an FMA as "
+                "2 flop; the path runs with contraction off (the reference's rounding), so 39.3 TFLOP/s "
+                "(peak_no_fma) is the ceiling for its separately rounded mul/add. achieved/frac count "
+                "intersection flops only (SURVEY 8d); all_fp64_*, traffic, hbm_gbs, valu_busy and lane_util "
+                "come from the committed PMC profile of this command collected on this build "
+                "(pmc_profile, pmc_build_id == build_id; null when none exists); traffic_over_* divide "
+                "the HBM bytes by the float32 framebuffer and by the chunk partials the design writes",
+    }
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="ff", choices=list(CONFIGS))
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the roofline (counting build, serialized kernel launches, "
+                         "the build's PMC profile), the per-rank kernel and gather times (N > 1), the north-star "
+                         "workload (--config ff) and the CPU baseline (N = 1); a plain run does none of these")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-north-star", action="store_true",
-                    help="skip the second measurement of BASELINE.json configs[2] (the north-star workload)")
+                    help="with --full: skip the second measurement of BASELINE.json configs[2] (the north-star workload)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed to DIR/image.npy (float32 H x W x 3; "
+                         "above 64 MB a fixed, seeded sample of its rows)")
     ap.add_argument("--chunk", type=int, default=0, help="samples per work unit (0 = auto: 32, more above 4096 spp, tapered; vpt_chunks.h)")
     ap.add_argument("--inflight", type=int, default=3,
                     help="steps in flight: each on its own context + HIP stream, so one launch's drain (its "
@@ -650,14 +726,13 @@ def main() -> None:
     streams = [torch.cuda.current_stream(dev)] if D == 1 else [torch.cuda.Stream(dev) for _ in range(D)]
     m = measure(c, args, tracers, streams, world, rank, dev)
     ns = None
-    if args.config == "ff" and not args.no_north_star:
+    if args.full and args.config == "ff" and not args.no_north_star:
         ns = measure(CONFIGS[NORTH_STAR], args, tracers, streams, world, rank, dev)
     build = vpt.build_id()
-    prof = None if args.size else pmc_profile(args.config, world, build)
-    full = pmc_fp64_flop(prof)
-    kern_ms, T = m["kern_ms"], m["T"]
     if rank == 0 and args.save_image:
         np.save(args.save_image, m["image"])
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, m["image"])
     if rank == 0:
         img = m["image"]
         H, W, SPP = c["height"], c["width"], c["spp"]
@@ -668,6 +743,7 @@ def main() -> None:
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(m["elapsed"] / args.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": "strong",
@@ -687,47 +763,18 @@ def main() -> None:
                                   # each rank's serialized launch time of its shard (HIP events on its launch
                                   # stream) and rank 0's gather of one image's strips, timed serialized after
                                   # a barrier: imbalance and an exposed gather show here, not in `value`
-                                  "rank_kernel_ms": [round(x, 4) for x in m["rank_kern_ms"]],
+                                  # (--full; null in a plain run)
+                                  "rank_kernel_ms": [round(x, 4) for x in m["rank_kern_ms"]] if args.full else None,
                                   "gather_ms": None if m["gather_ms"] is None else round(m["gather_ms"], 4),
                                   "shared_device": bool(args.shared_device)},
-            },
-            "roofline": {
-                "bound": "fp64_valu",
-                "achieved": round(m["achieved"], 4),
-                "peak": FP64_PEAK_TFLOPS,
-                "unit": "TFLOP/s",
-                "frac": round(m["achieved"] / FP64_PEAK_TFLOPS, 5),
-                "peak_no_fma": FP64_PEAK_TFLOPS / 2,
-                "frac_of_no_fma_peak": round(m["achieved"] / (FP64_PEAK_TFLOPS / 2), 5),
-                "traffic": pmc_traffic(prof),
-                **pmc_fields(prof, kern_ms, fb_bytes(c), partial_bytes(c)),
-                "kernel": (f"pool_kernel<{c['estimator']}> + reduce_kernel (one launch pair)"
-                           if c["estimator"] not in ("ray_marching",) else "render_kernel_simple (one lane per pixel)"),
-                "kernel_ms": round(kern_ms, 3),
-                "kernel_ms_from": "HIP events around each launch of the timed steps on their stream" if D == 1 else
-                                  f"HIP events around {m['nevents']} serialized launches of the same render on one stream, "
-                                  f"right after the timed region (its {D} in-flight steps overlap)",
-                "work_basis": "reference-equivalent: the ray-sphere tests the REFERENCE algorithm performs on this "
-                              "workload (counting build), including the tests of rays the kernel's exact shortcuts "
-                              "never cast (pLight toward a sphere light, MISv2's BSDF ray, the H5 point-light cone); "
-                              "achieved/frac are therefore not executed FP64 work -- all_fp64_* is",
-                "algorithmic": f"{FLOP_PER_TEST} FP64 flop x {T:.2f} ray-sphere tests per sample (SURVEY 8d) x "
-                               f"{m['launch_samples']} samples per launch",
-                "all_fp64_tflops": round(full / (kern_ms * 1e-3) / 1e12, 3) if full else None,
-                "all_fp64_frac": round(full / (kern_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS, 4) if full else None,
-                "note": "FP64 VALU bound (no dense contraction exists, no MFMA): peak 78.6 TFLOP/s counts an FMA as "
-                        "2 flop; the path runs with contraction off (the reference's rounding), so 39.3 TFLOP/s "
-                        "(peak_no_fma) is the ceiling for its separately rounded mul/add. achieved/frac count "
-                        "intersection flops only (SURVEY 8d); all_fp64_*, traffic, hbm_gbs, valu_busy and lane_util "
-                        "come from the committed PMC profile of this command collected on this build "
-                        "(pmc_profile, pmc_build_id == build_id; null when none exists); traffic_over_* divide "
-                        "the HBM bytes by the float32 framebuffer and by the chunk partials the design writes",
             },
             "image_mean": [round(float(x), 6) for x in img.reshape(-1, 3).mean(0)],
             "build_id": build,
         }
+        if args.full:
+            res["roofline"] = roofline(m, c, None if args.size else pmc_profile(args.config, world, build), D)
         threads = int(os.environ.get("OMP_NUM_THREADS", "0")) or min(16, os.cpu_count() or 1)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             res["cpu_baseline"] = cpu_baseline(img, c, threads)
             res["cpu_baseline"]["port_per_sample_rng"] = cpu_port_check(img, c, threads, bands=4,
                                                                          ref_rate=res["cpu_baseline"]["value"])

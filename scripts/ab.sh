@@ -28,7 +28,7 @@ fi
 for rep in $(seq 1 "${REPS:-2}"); do
     for v in "$@"; do
         for c in ${CFGS:-ff}; do
-            VPT_LIB=$(lib "$v") timeout -k 10 300 python bench.py --config "$c" --steps 3 --warmup 1 --no-cpu --inflight 1 \
+            VPT_LIB=$(lib "$v") timeout -k 10 300 python bench.py --config "$c" --steps 3 --warmup 1 --full --no-cpu --inflight 1 \
                 ${BENCH_ARGS:-} > "$OUT/b_${v}_$c.log" 2>&1
             rc=$?; [ $rc -eq 0 ] || { tail -5 "$OUT/b_${v}_$c.log"; echo "STOP bench rc=$rc"; exit $rc; }
             python - "$OUT/b_${v}_$c.log" "$v" "$c" <<'PY'

@@ -18,7 +18,7 @@ for v in "$@"; do
     lib=minimal_volumetric_path_tracer_amd/libvpt.so
     case $v in base*) ;; *) lib=build_variants/libvpt_$v.so ;; esac
     VPT_LIB=$lib timeout -k 10 300 rocprofv3 --pmc $CTRS --kernel-trace -d "$OUT/$v" -o run --output-format csv -- \
-        python3 bench.py --config ff --steps 1 --warmup 0 --no-cpu --inflight 1 > "$OUT/$v.log" 2>&1
+        python3 bench.py --config ff --steps 1 --warmup 0 --full --no-cpu --inflight 1 > "$OUT/$v.log" 2>&1
     rc=$?
     echo "$v rc=$rc"
     case $rc in 0) ;; *) tail -5 "$OUT/$v.log"; echo "STOP"; exit $rc ;; esac

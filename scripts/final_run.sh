@@ -13,7 +13,7 @@ python3 scripts/pmc_summary.py "$OUT/pmc_$TAG" 'pool_kernel<0, false>' > "$OUT/p
 python3 scripts/pmc_summary.py "$OUT/pmc_$TAG" 'pool_kernel<1, false>' > "$OUT/pmc_pool_kernel_mis_$TAG.json" || exit 1
 cp "$OUT/pmc_pool_kernel_$TAG.json" "profiles/$RD/pmc_pool_kernel.json"
 cp "$OUT/pmc_pool_kernel_mis_$TAG.json" "profiles/$RD/pmc_pool_kernel_mis.json"
-timeout -k 10 500 python bench.py --steps 3 --warmup 1 > "$OUT/bench_$TAG.log" 2>&1 || { echo "STOP bench2"; exit 1; }
+timeout -k 10 500 python bench.py --steps 3 --warmup 1 --full > "$OUT/bench_$TAG.log" 2>&1 || { echo "STOP bench2"; exit 1; }
 grep '^{' "$OUT/bench_$TAG.log" | tail -1
 bash scripts/gpu_pipe.sh "$TAG" || exit $?
 echo "== final done"

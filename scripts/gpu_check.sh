@@ -31,13 +31,13 @@ for s in $STEPS; do
     case $s in
         tests) run pytest_gpu 900 python -u -m pytest tests -m gpu -x -v -p no:cacheprovider --timeout 300 --timeout-method thread ;;
         smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-        bench) run bench 600 python bench.py --steps 3 --warmup 1 ;;
+        bench) run bench 600 python bench.py --steps 3 --warmup 1 --full ;;
         prof)  run prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$TAG" -o run --output-format csv -- \
-                   python3 bench.py --steps 3 --warmup 1 --no-cpu --inflight 1 ;;
+                   python3 bench.py --steps 3 --warmup 1 --full --no-cpu --inflight 1 ;;
         pmc)   run pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch_$TAG" -o run --output-format csv -- \
-                   python3 bench.py --steps 1 --warmup 0 --no-cpu --inflight 1 &&
+                   python3 bench.py --steps 1 --warmup 0 --full --no-cpu --inflight 1 &&
                run pmc_write 600 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write_$TAG" -o run --output-format csv -- \
-                   python3 bench.py --steps 1 --warmup 0 --no-cpu --inflight 1 ;;
+                   python3 bench.py --steps 1 --warmup 0 --full --no-cpu --inflight 1 ;;
         *) echo "unknown step $s" ;;
     esac
 done

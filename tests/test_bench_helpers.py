@@ -54,6 +54,23 @@ def test_cpu_port_check_rmse():
     assert bench.cpu_port_check(img, c, threads=2, bands=2, band=16, cal_spp=1)["rmse_vs_gpu_per_channel"][1] > 0
 
 
+def test_dump_outputs_writes_float32_within_its_limit(tmp_path, monkeypatch):
+    """--dump-outputs: the whole image when it fits; above the limit the same seeded sample of whole rows
+    in every run, in row order"""
+    assert bench.fb_bytes(bench.CONFIGS["ff"]) < bench.DUMP_LIMIT < 64e6  # the default image is written whole
+    img = np.arange(40 * 8 * 3, dtype=np.float64).reshape(40, 8, 3)
+    bench.dump_outputs(str(tmp_path / "a"), img)
+    a = np.load(tmp_path / "a" / "image.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, img.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 10 * 8 * 3 * 4 + 50)  # room for 10 of the 40 rows
+    bench.dump_outputs(str(tmp_path / "b"), img)
+    bench.dump_outputs(str(tmp_path / "c"), img + 0.0)
+    b, c = np.load(tmp_path / "b" / "image.npy"), np.load(tmp_path / "c" / "image.npy")
+    assert b.dtype == np.float32 and b.shape == (10, 8, 3) and b.nbytes <= bench.DUMP_LIMIT and np.array_equal(b, c)
+    rows = (b[:, 0, 0] / 24).astype(int)
+    assert (np.diff(rows) > 0).all() and np.array_equal(b, img[rows].astype(np.float32))
+
+
 def test_bench_configs_match_baseline():
     assert bench.CONFIGS["ff"] == dict(width=1024, height=1024, spp=256, estimator="ff", sigma_a=0.001, sigma_s=0.009)
     assert bench.CONFIGS["mis4k"]["spp"] == 8192 and bench.CONFIGS["mis4k"]["width"] == 4096

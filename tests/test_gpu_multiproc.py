@@ -49,7 +49,7 @@ def test_bench_multi_rank_branch(gpu_tracer, tmp_path, world):
     W, H, SPP = 64, 96, 8
     out = tmp_path / "bench.npy"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--dist-backend", "gloo",
-                        "--shared-device", "--size", f"{W}x{H}x{SPP}", "--no-cpu", "--no-north-star", "--inflight", "2",
+                        "--shared-device", "--size", f"{W}x{H}x{SPP}", "--full", "--no-cpu", "--no-north-star", "--inflight", "2",
                         "--steps", "3", "--warmup", "1", "--save-image", str(out)],
                        capture_output=True, text=True, timeout=170, env=_clean_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -68,6 +68,32 @@ def test_bench_multi_rank_branch(gpu_tracer, tmp_path, world):
     gpu_tracer.set_scene(vpt.default_scene())
     ref = gpu_tracer.render(vpt.RenderConfig(width=W, height=H, spp=SPP, estimator="ff", seed=0x5EED0001))
     assert bitwise_equal(np.load(out), ref).all()
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_image(gpu_tracer, tmp_path):
+    """a plain bench.py --gpus 1 run: the result line with the headline fields and none of --full's legs
+    (roofline, north star, CPU baseline), and --dump-outputs writes the last timed step's image, float32,
+    bit-identical to a direct render of the same configuration"""
+    W, H, SPP = 64, 48, 8
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                        "--size", f"{W}x{H}x{SPP}", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=170, env=_clean_env(), cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["unit"] == "Msamples/s" and res["higher_is_better"] is True and res["dtype"] == "f64"
+    assert res["steps"] == 4 and res["full"] is False and res["value"] > 0 and res["ms_per_step"] > 0
+    # value and ms_per_step are the same measurement: samples of one image / the time of one step
+    # (both rounded to 3 decimals in the line)
+    assert res["ms_per_step"] == pytest.approx(W * H * SPP / res["value"] / 1e3, rel=1e-3, abs=1e-3)
+    assert not {"roofline", "north_star", "cpu_baseline"} & set(res)
+    assert os.listdir(tmp_path / "out") == ["image.npy"]
+    img = np.load(tmp_path / "out" / "image.npy")
+    gpu_tracer.set_scene(vpt.default_scene())
+    ref = gpu_tracer.render(vpt.RenderConfig(width=W, height=H, spp=SPP, estimator="ff", seed=0x5EED0001))
+    assert img.dtype == np.float32 and img.shape == ref.shape == (H, W, 3)
+    assert bitwise_equal(img, ref).all()
 
 
 def test_bench_refuses_more_gpus_than_the_box_has():
