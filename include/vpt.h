@@ -31,7 +31,7 @@ typedef enum {
     VPT_E_INVALID = -1,        /* bad argument (null pointer, size, NaN parameter ...) */
     VPT_E_TOO_MANY = -2,       /* more spheres than VPT_MAX_SPHERES */
     VPT_E_NO_EMITTER = -3,     /* reserved */
-    VPT_E_UNSUPPORTED = -4,    /* material id outside {0,1,2,3} */
+    VPT_E_UNSUPPORTED = -4,    /* material id outside {0,1,2,3}; an estimator the accumulator cannot serve */
     VPT_E_HIP = -5,            /* HIP runtime error (message in vpt_last_error) */
     VPT_E_IO = -6,             /* file could not be written */
     VPT_E_INTERNAL = -7        /* an internal invariant failed (message in vpt_last_error) */
@@ -173,6 +173,71 @@ int vpt_multi_render(vpt_multi* m, const vpt_params* p, void* h_out);
 void vpt_multi_destroy(vpt_multi* m);
 /* one-shot: create, set the scene, render, destroy */
 int vpt_render_multi(const vpt_sphere* spheres, int n, const vpt_params* p, int n_gpus, void* h_out);
+
+/* ---- progressive accumulator: a render that can be continued, with a per-tile error ----
+ * An accumulator holds, per pixel of p's shard, the sum of the samples received so far and a running
+ * noise statistic (csrc/vpt_accum.h), and per 8x8 tile (row-major over the shard, tiles_x per row) a level
+ * count and an error.  Samples arrive in chunk levels of C samples: level k of a pixel is its samples
+ * [kC, kC + C), so a pixel that holds m levels -- through any sequence of vpt_accum_add / vpt_accum_refine
+ * calls -- resolves to the bits of vpt_render(spp = mC, chunk_spp = C) for that pixel.
+ * p->spp is the cap (most samples a pixel may receive), a multiple of C; C = p->chunk_spp, or min(32, spp)
+ * when that is 0; estimators 0-5 (6-9 have no chunks: VPT_E_UNSUPPORTED); band_* are honoured, so a shard
+ * can be accumulated.  The partial-sum buffer holds only the levels of one pass.
+ * All calls are synchronous except vpt_accum_resolve_device.  The context must outlive the accumulator, and
+ * its scene must not change (vpt_set_scene) while an accumulator holds samples: that is the caller's error
+ * and is not detected.  One accumulator is used by one thread at a time. */
+typedef struct vpt_accum vpt_accum;
+
+int vpt_accum_create(vpt_context* ctx, const vpt_params* p, vpt_accum** out);
+void vpt_accum_destroy(vpt_accum* a);
+/* the tile grid, the chunk size C and the cap in levels (any pointer may be NULL) */
+int vpt_accum_tiles(const vpt_accum* a, int* tiles_x, int* tiles_y, int* chunk, int* max_levels);
+
+/* `levels` more chunk levels for the n_tiles listed tiles (tiles NULL = all): indices in [0, tiles_x *
+ * tiles_y), no duplicates, any order.  A tile that would pass max_levels, a duplicate or an index out of
+ * range -> VPT_E_INVALID, and nothing is rendered.  A list that is not the whole tile set needs estimator 0 or 1
+ * (the tile-list variant of the pool kernel exists for these two): VPT_E_UNSUPPORTED otherwise, also from
+ * vpt_accum_refine once its active set is a subset (the passes made until then stay). */
+int vpt_accum_add(vpt_accum* a, int levels, const int32_t* tiles, int n_tiles);
+
+/* Adaptive refinement.  A tile is active iff levels < max_levels && (levels < min_levels || err > target);
+ * a NaN error therefore retires a tile once it has min_levels.  lum_floor: the mean luminance below which
+ * the error is taken relative to lum_floor instead (0.01 by default; it also becomes the floor of later
+ * vpt_accum_add calls).  min_levels >= 2 (one level has no variance). */
+typedef struct vpt_refine {
+    double target, lum_floor;
+    int32_t min_levels, levels_per_pass;
+} vpt_refine;
+typedef struct vpt_refine_report {
+    int32_t passes;            /* passes this call made */
+    int32_t tiles_converged;   /* tiles whose error is not above target */
+    int32_t tiles_capped;      /* tiles stopped by max_levels with an error above target */
+    uint64_t samples;          /* camera samples this call rendered (valid pixels x levels x C) */
+    double max_err;            /* largest tile error at the end (NaN if any tile's is NaN) */
+} vpt_refine_report;
+/* repeats vpt_accum_add (levels_per_pass levels, fewer where the cap is nearer) on the active tiles until
+ * none is active; report may be NULL */
+int vpt_accum_refine(vpt_accum* a, const vpt_refine* r, vpt_refine_report* report);
+
+/* The image so far: per pixel sum * (1 / (double)(levels * C)) with its tile's level count, 0 for a tile
+ * without samples; vpt_shard_rows * width * 3 elements of fb_format, file order. */
+int vpt_accum_resolve(vpt_accum* a, int fb_format, void* h_out);
+/* enqueues the resolve on `stream` (NULL = default stream) and returns; the caller synchronises that
+ * stream before reading d_out */
+int vpt_accum_resolve_device(vpt_accum* a, int fb_format, void* d_out, void* stream);
+
+/* state download, any pointer may be NULL: sum[rows*w*3], s12[rows*w*2] (s1, s2 per pixel),
+ * tile_levels[tiles], tile_err[tiles] (+inf below two levels) */
+int vpt_accum_read(vpt_accum* a, double* sum, double* s12, int32_t* tile_levels, double* tile_err);
+
+/* csrc/vpt_accum.h on host arrays (no GPU needed): the chunk sums csum[m][npix][3] of m levels -> per pixel
+ * sum[3], s12[2] and err (any output may be NULL); chunk = C */
+int vpt_accum_stat_host(const double* csum, int m, int64_t npix, int chunk, double lum_floor, double* sum, double* s12,
+                        double* err);
+/* the refine policy on host arrays (no GPU needed): returns the number of active tiles and writes their
+ * ascending indices to active (n_tiles entries), or a negative vpt_status */
+int vpt_accum_select_host(const int32_t* tile_levels, const double* tile_err, int n_tiles, const vpt_refine* r,
+                          int max_levels, int32_t* active);
 
 /* The per-sample call itself, batched: rays[i] with erand48 start state states[i] (low 48
  * bits) through the estimator of `m`; out_rgb[3i..3i+2] = the Color the reference returns,

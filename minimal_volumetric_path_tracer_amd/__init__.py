@@ -5,6 +5,7 @@ from ._lib import (EXPLICIT_EQUIANGULAR, EXPLICIT_FREE, FB_F32, FB_F64, FREE_FLI
                    RAY_DTYPE, RAY_MARCHING, RAY_MARCHING_EXPLICIT, RAY_MARCHING_GLOBAL, RAY_MARCHING_SA, SPHERE_DTYPE,
                    SURFACE_PT, VPTError, build_id, lib)
 from .tracer import (
+    Accumulator,
     MultiTracer,
     Ray,
     RenderConfig,
@@ -21,5 +22,5 @@ from .tracer import (
 __all__ = [
     "FB_F32", "FB_F64", "FREE_FLIGHT", "MIS_EQUIANGULAR", "EXPLICIT_FREE", "IMPLICIT_FREE", "EXPLICIT_EQUIANGULAR", "SURFACE_PT", "RAY_MARCHING",
     "RAY_MARCHING_SA", "RAY_MARCHING_GLOBAL", "RAY_MARCHING_EXPLICIT", "RAY_DTYPE", "SPHERE_DTYPE", "VPTError", "build_id", "lib",
-    "MultiTracer", "render_multi", "Ray", "RenderConfig", "Sphere", "Tracer", "default_scene", "encode_ppm", "scene", "stream_state", "write_ppm",
+    "Accumulator", "MultiTracer", "render_multi", "Ray", "RenderConfig", "Sphere", "Tracer", "default_scene", "encode_ppm", "scene", "stream_state", "write_ppm",
 ]

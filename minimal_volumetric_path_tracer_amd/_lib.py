@@ -71,6 +71,15 @@ class vpt_params(ctypes.Structure):
     ]
 
 
+class vpt_refine(ctypes.Structure):
+    _fields_ = [("target", c_double), ("lum_floor", c_double), ("min_levels", c_int32), ("levels_per_pass", c_int32)]
+
+
+class vpt_refine_report(ctypes.Structure):
+    _fields_ = [("passes", c_int32), ("tiles_converged", c_int32), ("tiles_capped", c_int32), ("samples", c_uint64),
+                ("max_err", c_double)]
+
+
 class VPTError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"libvpt error {code}: {msg}")
@@ -94,6 +103,16 @@ PROTOTYPES = [
     ("vpt_multi_render", c_int, [c_void_p, POINTER(vpt_params), c_void_p]),
     ("vpt_multi_destroy", None, [c_void_p]),
     ("vpt_render_multi", c_int, [c_void_p, c_int, POINTER(vpt_params), c_int, c_void_p]),
+    ("vpt_accum_create", c_int, [c_void_p, POINTER(vpt_params), POINTER(c_void_p)]),
+    ("vpt_accum_destroy", None, [c_void_p]),
+    ("vpt_accum_tiles", c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    ("vpt_accum_add", c_int, [c_void_p, c_int, c_void_p, c_int]),
+    ("vpt_accum_refine", c_int, [c_void_p, POINTER(vpt_refine), POINTER(vpt_refine_report)]),
+    ("vpt_accum_resolve", c_int, [c_void_p, c_int, c_void_p]),
+    ("vpt_accum_resolve_device", c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    ("vpt_accum_read", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vpt_accum_stat_host", c_int, [c_void_p, c_int, c_int64, c_int, c_double, c_void_p, c_void_p, c_void_p]),
+    ("vpt_accum_select_host", c_int, [c_void_p, c_void_p, c_int, POINTER(vpt_refine), c_int, c_void_p]),
     ("vpt_trace_batch", c_int, [c_void_p, POINTER(vpt_medium), c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     ("vpt_punctual_volumetric", c_int, [c_void_p, c_int, c_void_p, c_int, c_double, c_double, c_double, c_void_p]),
     ("vpt_ray_marching_batch", c_int, [c_void_p, c_double, c_double, c_double, c_void_p, c_void_p, c_int, c_void_p,

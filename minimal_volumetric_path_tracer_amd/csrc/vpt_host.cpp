@@ -19,6 +19,7 @@
 
 #include <thread>
 
+#include "vpt_accum.h"
 #include "vpt_internal.h"
 #include "vpt_rng.h"
 
@@ -124,6 +125,48 @@ int vpt_shard_rows(const vpt_params* p)
         rows += r1 - r0;
     }
     return rows;
+}
+
+/* ---- the accumulator's statistic and policy on host arrays (csrc/vpt_accum.h) ---- */
+int vpt_accum_stat_host(const double* csum, int m, int64_t npix, int chunk, double lum_floor, double* sum, double* s12,
+                        double* err)
+{
+    vpt_clear_error();
+    if (!csum || m < 0 || npix < 0 || chunk <= 0) return vpt_fail(VPT_E_INVALID, "vpt_accum_stat_host: bad arguments");
+    if (!(lum_floor >= 0 && lum_floor - lum_floor == 0.0))
+        return vpt_fail(VPT_E_INVALID, "vpt_accum_stat_host: lum_floor must be finite and >= 0");
+    const double cfloor = (double)chunk * lum_floor;
+    for (int64_t p = 0; p < npix; ++p) {
+        vpt_accum_px a = {{0.0, 0.0, 0.0}, 0.0, 0.0};
+        for (int k = 0; k < m; ++k) {
+            const double* c = csum + ((int64_t)k * npix + p) * 3;
+            vpt_accum_level(&a, c[0], c[1], c[2]);
+        }
+        if (sum) memcpy(sum + 3 * p, a.sum, sizeof a.sum);
+        if (s12) {
+            s12[2 * p] = a.s1;
+            s12[2 * p + 1] = a.s2;
+        }
+        if (err) err[p] = vpt_accum_err(a.s1, a.s2, m, cfloor);
+    }
+    return VPT_OK;
+}
+
+int vpt_accum_select_host(const int32_t* tile_levels, const double* tile_err, int n_tiles, const vpt_refine* r,
+                          int max_levels, int32_t* active)
+{
+    vpt_clear_error();
+    if (!tile_levels || !tile_err || !r || !active || n_tiles < 0 || max_levels < 0)
+        return vpt_fail(VPT_E_INVALID, "vpt_accum_select_host: bad arguments");
+    switch (vpt_accum_refine_bad(r->target, r->lum_floor, r->min_levels, r->levels_per_pass)) {
+    case 1: return vpt_fail(VPT_E_INVALID, "vpt_accum_select_host: target and lum_floor must be finite and >= 0");
+    case 2: return vpt_fail(VPT_E_INVALID, "vpt_accum_select_host: min_levels must be >= 2");
+    case 3: return vpt_fail(VPT_E_INVALID, "vpt_accum_select_host: levels_per_pass must be > 0");
+    }
+    int k = 0;
+    for (int t = 0; t < n_tiles; ++t)
+        if (vpt_accum_active(tile_levels[t], tile_err[t], r->min_levels, max_levels, r->target)) active[k++] = t;
+    return k;
 }
 
 /* ---- PPM ---- */

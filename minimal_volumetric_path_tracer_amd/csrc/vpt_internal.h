@@ -8,4 +8,12 @@
 int vpt_fail(int code, const char* fmt, ...);
 void vpt_clear_error(void);
 
+/* what the progressive accumulator (vpt_accum.hip) needs of a context (vpt_kernels.hip) */
+int vpt_int_device(const vpt_context* ctx);
+const unsigned* vpt_int_guard_flag(const vpt_context* ctx);   /* device address of PoolParams::guard's flag */
+int vpt_int_check_guard(vpt_context* ctx, const char* who);   /* after a synchronisation */
+int vpt_int_check_params(const vpt_context* ctx, const vpt_params* p);  /* build_kparams' validation */
+int vpt_int_pool_pass(vpt_context* ctx, const vpt_params* p, int C, int k0, int k1, const unsigned* d_tiles,
+                      unsigned n_tiles, double* d_partials, unsigned* d_queue);
+
 #endif

@@ -30,6 +30,8 @@
 namespace vpt {
 extern template __global__ void pool_kernel<1, false>(PoolParams P0, Medium m0, const DevScene* __restrict__ S,
                                                       unsigned long long* counters, unsigned long long* stats);
+extern template __global__ void pool_kernel<1, false, true>(PoolParams P0, Medium m0, const DevScene* __restrict__ S,
+                                                            unsigned long long* counters, unsigned long long* stats);
 }  // namespace vpt
 #if VPT_SECTIONS
 extern "C" int vpt_mis_sections_add(unsigned long long* out);
@@ -674,80 +676,128 @@ static int launch_one(vpt_context* ctx, KParams K, hipStream_t stream)
     return VPT_OK;
 }
 
-template <int EST, int FB>
-static int launch_pool(vpt_context* ctx, KParams K, hipStream_t stream)
+/* One pass of the pool kernel: the chunks [c0, c1) of layout `lay` for a set of 8x8 tiles -- every tile of
+ * the shard in order (tile_map NULL, n_tiles = tiles_x * tiles_y) or the n_tiles tiles a device list names.
+ * pool_plan fills Q and checks the bounds (no GPU call); pool_enqueue sets the buffers and launches.
+ * The units of a pass are chunk-major like a whole render's, level_units = 64 n_tiles per chunk, and the
+ * pass is the unit range [c0 level_units, c1 level_units) of the layout.  A tile list needs pool_kernel<EST, false, true>
+ * (estimators 0 and 1; VPT_E_UNSUPPORTED otherwise). */
+static int pool_plan(const KParams& K, vpt_chunk_layout lay, int c0, int c1, const unsigned* tile_map, unsigned n_tiles,
+                     PoolParams& Q, uint64_t* first, uint64_t* count)
+{
+    if (K.w > 65535 || K.h > 65535) return vpt_fail(VPT_E_INVALID, "width and height must be < 65536");
+    Q.w = K.w;
+    Q.h = K.h;
+    Q.spp = K.spp;
+    Q.rows = K.shard_rows;
+    Q.band_rows = K.band_rows;
+    Q.band_stride = K.band_stride;
+    Q.band_offset = K.band_offset;
+    Q.tiles_x = K.tiles_x;
+    Q.lay = lay;
+    Q.nch = Q.lay.n;
+    Q.level_units = n_tiles * 64u;
+    Q.sh_lu = log2_exact((int64_t)Q.level_units);
+    Q.sh_tx = log2_exact(K.tiles_x);
+    Q.sh_br = log2_exact(K.band_rows);
+    Q.sh_bs = log2_exact(K.band_stride);
+    Q.sh_c = log2_exact(Q.lay.C);
+    Q.rw = log2_exact(K.w) >= 0 ? 1.0 / K.w : 0.0;
+    Q.rh = log2_exact(K.h) >= 0 ? 1.0 / K.h : 0.0;
+    Q.tile_map = tile_map;
+    /* the kernel adds unit0 to a unit's index in u32: the pass's last unit must fit */
+    const uint64_t end = (uint64_t)n_tiles * 64u * (uint64_t)c1;
+    if (end >= 0xFFFFFFFFull) return vpt_fail(VPT_E_INVALID, "too many work units (%llu)", (unsigned long long)end);
+    *first = (uint64_t)n_tiles * 64u * (uint64_t)c0;
+    *count = end - *first;
+    Q.seed = K.seed;
+    for (int i = 0; i < 3; ++i) {
+        Q.o[i] = K.o[i];
+        Q.d[i] = K.d[i];
+        Q.cx[i] = K.cx[i];
+        Q.cy[i] = K.cy[i];
+    }
+    return VPT_OK;
+}
+
+/* partials: where chunk 0's plane would start (a pass that holds only the chunks from c0 on passes its buffer
+ * minus c0 planes; the address is only formed, never dereferenced below the buffer) */
+template <int EST>
+static int pool_enqueue(vpt_context* ctx, const KParams& K, PoolParams& Q, uint64_t first, uint64_t units, double* partials,
+                        unsigned* queue, hipStream_t stream)
 {
     const DevScene* S = ctx->d_scene;
     constexpr bool COUNT = false;
     int blocks = 0;
+    Q.partials = partials;
+    Q.queue = queue;
+    Q.guard = ctx->d_guard;
+    Q.guard_bias = ctx->guard_bias;
+    const Medium m{K.sigma_a, K.sigma_s, K.g, K.max_depth, K.march_step, K.march_light};
+    /* a pass over a tile list runs pool_kernel<EST, false, true>, which exists for the estimators 0 and 1 */
+    constexpr bool HAS_TILES = EST <= 1;
+    const bool tiles = Q.tile_map != nullptr;
+    if (tiles && !HAS_TILES)
+        return vpt_fail(VPT_E_UNSUPPORTED, "estimator %d renders whole tile sets only (tile subsets: estimators 0 and 1)", EST);
+    int rc;
+    if constexpr (HAS_TILES) {
+        rc = tiles ? persistent_grid(ctx, pool_kernel<EST, COUNT, true>, &blocks, VPT_POOL_THREADS)
+                   : persistent_grid(ctx, pool_kernel<EST, COUNT>, &blocks, VPT_POOL_THREADS);
+    } else {
+        rc = persistent_grid(ctx, pool_kernel<EST, COUNT>, &blocks, VPT_POOL_THREADS);
+    }
+    if (rc) return rc;
+    const uint64_t need = (units + POOL - 1) / POOL;
+    if ((uint64_t)blocks > need) blocks = (int)need;
+    /* every workgroup adds UREFILL to the u32 queue once more after it runs dry */
+    if (first + units + (uint64_t)blocks * (UREFILL + 1) >= 0xFFFFFFFFull)
+        return vpt_fail(VPT_E_INVALID, "too many work units (%llu) for the u32 work queue", (unsigned long long)(first + units));
+    /* launches of at most 2^launch_log2 samples per workgroup (launch_max_units); samples per
+     * unit: at most the layout's head chunk C, and a unit above 2^LAUNCH_LOG2_MAX is refused */
+    if (Q.lay.C > (1 << LAUNCH_LOG2_MAX))
+        return vpt_fail(VPT_E_INVALID, "chunk of %d samples > 2^26 (the per-workgroup launch bound)", Q.lay.C);
+    const uint64_t max_units = launch_max_units(blocks, Q.lay.C, ctx->launch_log2);
+    unsigned long long* stats = nullptr;
+    if (env_int("VPT_POOL_STATS", 0)) {  /* debug: scheduler statistics, vpt_debug_pool_stats */
+        if (!g_pool_stats) HIP_OK(hipMalloc((void**)&g_pool_stats, (TL0 + 3 * TL_MAXWG) * sizeof(unsigned long long)));
+        HIP_OK(hipMemsetAsync(g_pool_stats, 0, TL0 * sizeof(unsigned long long), stream));
+        HIP_OK(hipMemsetAsync(g_pool_stats + TL0, 0xFF, 3 * TL_MAXWG * sizeof(unsigned long long), stream));
+        stats = g_pool_stats;
+    }
+    for (uint64_t u0 = 0; u0 < units; u0 += max_units) {
+        Q.unit0 = (unsigned)(first + u0);
+        Q.nunits = (unsigned)(units - u0 < max_units ? units - u0 : max_units);
+        HIP_OK(hipMemsetAsync(Q.queue, 0, sizeof(unsigned), stream));
+        if constexpr (HAS_TILES) {
+            if (tiles) pool_kernel<EST, COUNT, true><<<dim3((unsigned)blocks), dim3(VPT_POOL_THREADS), 0, stream>>>(Q, m, S, K.counters, stats);
+            else pool_kernel<EST, COUNT><<<dim3((unsigned)blocks), dim3(VPT_POOL_THREADS), 0, stream>>>(Q, m, S, K.counters, stats);
+        } else {
+            pool_kernel<EST, COUNT><<<dim3((unsigned)blocks), dim3(VPT_POOL_THREADS), 0, stream>>>(Q, m, S, K.counters, stats);
+        }
+        HIP_OK(hipGetLastError());
+    }
+    return VPT_OK;
+}
+
+template <int EST, int FB>
+static int launch_pool(vpt_context* ctx, KParams K, hipStream_t stream)
+{
+    [[maybe_unused]] constexpr bool COUNT = false;  /* the debug arm below */
     int rc;
     const bool wave = EST <= 1 && env_int("VPT_WAVE_KERNEL", 0);  /* A/B: the previous design, FF/MIS */
     if (!wave) {  /* default: workgroup task pool (vpt_pool.h) */
-        if (K.w > 65535 || K.h > 65535) return vpt_fail(VPT_E_INVALID, "width and height must be < 65536");
         PoolParams Q;
-        Q.w = K.w;
-        Q.h = K.h;
-        Q.spp = K.spp;
-        Q.rows = K.shard_rows;
-        Q.band_rows = K.band_rows;
-        Q.band_stride = K.band_stride;
-        Q.band_offset = K.band_offset;
-        Q.tiles_x = K.tiles_x;
-        Q.lay = vpt_chunks(K.spp, K.chunk, K.taper);
-        Q.nch = Q.lay.n;
-        Q.level_units = (unsigned)K.tiles_x * (unsigned)K.tiles_y * 64u;
-        Q.sh_lu = log2_exact((int64_t)Q.level_units);
-        Q.sh_tx = log2_exact(K.tiles_x);
-        Q.sh_br = log2_exact(K.band_rows);
-        Q.sh_bs = log2_exact(K.band_stride);
-        Q.sh_c = log2_exact(Q.lay.C);
-        Q.rw = log2_exact(K.w) >= 0 ? 1.0 / K.w : 0.0;
-        Q.rh = log2_exact(K.h) >= 0 ? 1.0 / K.h : 0.0;
-        const uint64_t units = (uint64_t)K.tiles_x * (uint64_t)K.tiles_y * 64u * (uint64_t)Q.nch;
-        if (units >= 0xFFFFFFFFull) return vpt_fail(VPT_E_INVALID, "too many work units (%llu)", (unsigned long long)units);
-        Q.seed = K.seed;
-        for (int i = 0; i < 3; ++i) {
-            Q.o[i] = K.o[i];
-            Q.d[i] = K.d[i];
-            Q.cx[i] = K.cx[i];
-            Q.cy[i] = K.cy[i];
-        }
+        uint64_t first = 0, units = 0;
+        const vpt_chunk_layout lay = vpt_chunks(K.spp, K.chunk, K.taper);
+        rc = pool_plan(K, lay, 0, lay.n, nullptr, (unsigned)K.tiles_x * (unsigned)K.tiles_y, Q, &first, &units);
+        if (rc) return rc;
         const size_t pbytes = (size_t)K.shard_rows * (size_t)K.w * (size_t)Q.nch * 3 * sizeof(double);
         std::lock_guard<std::mutex> lock(ctx->mu);  /* until the launches on the slot are enqueued */
         StreamSlot* sl = nullptr;
         rc = stream_slot(ctx, stream, pbytes, &sl);
         if (rc) return rc;
-        Q.partials = sl->d_partials;
-        Q.queue = sl->d_queue;
-        Q.guard = ctx->d_guard;
-        Q.guard_bias = ctx->guard_bias;
-        const Medium m{K.sigma_a, K.sigma_s, K.g, K.max_depth, K.march_step, K.march_light};
-        rc = persistent_grid(ctx, pool_kernel<EST, COUNT>, &blocks, VPT_POOL_THREADS);
+        rc = pool_enqueue<EST>(ctx, K, Q, first, units, sl->d_partials, sl->d_queue, stream);
         if (rc) return rc;
-        const uint64_t need = (units + POOL - 1) / POOL;
-        if ((uint64_t)blocks > need) blocks = (int)need;
-        /* every workgroup adds UREFILL to the u32 queue once more after it runs dry */
-        if (units + (uint64_t)blocks * (UREFILL + 1) >= 0xFFFFFFFFull)
-            return vpt_fail(VPT_E_INVALID, "too many work units (%llu) for the u32 work queue", (unsigned long long)units);
-        /* launches of at most 2^launch_log2 samples per workgroup (launch_max_units); samples per
-         * unit: at most the layout's head chunk C, and a unit above 2^LAUNCH_LOG2_MAX is refused */
-        if (Q.lay.C > (1 << LAUNCH_LOG2_MAX))
-            return vpt_fail(VPT_E_INVALID, "chunk of %d samples > 2^26 (the per-workgroup launch bound)", Q.lay.C);
-        const uint64_t max_units = launch_max_units(blocks, Q.lay.C, ctx->launch_log2);
-        unsigned long long* stats = nullptr;
-        if (env_int("VPT_POOL_STATS", 0)) {  /* debug: scheduler statistics, vpt_debug_pool_stats */
-            if (!g_pool_stats) HIP_OK(hipMalloc((void**)&g_pool_stats, (TL0 + 3 * TL_MAXWG) * sizeof(unsigned long long)));
-            HIP_OK(hipMemsetAsync(g_pool_stats, 0, TL0 * sizeof(unsigned long long), stream));
-            HIP_OK(hipMemsetAsync(g_pool_stats + TL0, 0xFF, 3 * TL_MAXWG * sizeof(unsigned long long), stream));
-            stats = g_pool_stats;
-        }
-        for (uint64_t u0 = 0; u0 < units; u0 += max_units) {
-            Q.unit0 = (unsigned)u0;
-            Q.nunits = (unsigned)(units - u0 < max_units ? units - u0 : max_units);
-            HIP_OK(hipMemsetAsync(Q.queue, 0, sizeof(unsigned), stream));
-            pool_kernel<EST, COUNT><<<dim3((unsigned)blocks), dim3(VPT_POOL_THREADS), 0, stream>>>(Q, m, S, K.counters, stats);
-            HIP_OK(hipGetLastError());
-        }
         const size_t npix = (size_t)K.shard_rows * (size_t)K.w;
         reduce_kernel<FB><<<dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream>>>(Q, K.out);
         HIP_OK(hipGetLastError());
@@ -808,6 +858,50 @@ static int launch_render(vpt_context* ctx, KParams K, hipStream_t stream)
     }
 #undef VPT_LAUNCH_EST
     return vpt_fail(VPT_E_INVALID, "unknown estimator %d", K.est);
+}
+
+/* ---- for the progressive accumulator (vpt_accum.hip; declared in vpt_internal.h) ---- */
+int vpt_int_device(const vpt_context* ctx) { return ctx->device; }
+const unsigned* vpt_int_guard_flag(const vpt_context* ctx) { return ctx->d_guard; }
+int vpt_int_check_guard(vpt_context* ctx, const char* who) { return check_guard(ctx, who); }
+
+int vpt_int_check_params(const vpt_context* ctx, const vpt_params* p)
+{
+    KParams K;
+    return build_kparams(ctx, p, (void*)1, K);
+}
+
+/* chunk levels [k0, k1) of the uniform layout with chunk C, for the n_tiles tiles d_tiles lists (NULL: all
+ * tiles_x * tiles_y tiles of p's shard), into d_partials, which holds the planes of those levels only (level k0
+ * first).  Enqueued on the default stream; the caller owns the buffers and synchronises. */
+int vpt_int_pool_pass(vpt_context* ctx, const vpt_params* p, int C, int k0, int k1, const unsigned* d_tiles,
+                      unsigned n_tiles, double* d_partials, unsigned* d_queue)
+{
+    KParams K;
+    int rc = build_kparams(ctx, p, (void*)1, K);
+    if (rc) return rc;
+    if (K.est > 5) return vpt_fail(VPT_E_UNSUPPORTED, "estimator %d does not run on the pool kernel", K.est);
+    if (C <= 0 || k0 < 0 || k1 <= k0 || (int64_t)k1 * C > 0x7FFFFFFF || n_tiles == 0 || K.shard_rows == 0)
+        return vpt_fail(VPT_E_INVALID, "bad pass (levels [%d, %d) of %d samples, %u tiles)", k0, k1, C, n_tiles);
+    K.tiles_x = (K.w + 7) / 8;
+    K.tiles_y = (K.shard_rows + 7) / 8;
+    K.spp = k1 * C;
+    K.chunk = C;
+    K.taper = 0;
+    PoolParams Q;
+    uint64_t first = 0, units = 0;
+    rc = pool_plan(K, vpt_chunks(K.spp, C, 0), k0, k1, d_tiles, n_tiles, Q, &first, &units);
+    if (rc) return rc;
+    const size_t plane = (size_t)K.shard_rows * (size_t)K.w * 3;
+    double* base = (double*)((uintptr_t)d_partials - (uintptr_t)k0 * plane * sizeof(double));
+    switch (K.est) {
+    case 0: return pool_enqueue<0>(ctx, K, Q, first, units, base, d_queue, nullptr);
+    case 1: return pool_enqueue<1>(ctx, K, Q, first, units, base, d_queue, nullptr);
+    case 2: return pool_enqueue<2>(ctx, K, Q, first, units, base, d_queue, nullptr);
+    case 3: return pool_enqueue<3>(ctx, K, Q, first, units, base, d_queue, nullptr);
+    case 4: return pool_enqueue<4>(ctx, K, Q, first, units, base, d_queue, nullptr);
+    default: return pool_enqueue<5>(ctx, K, Q, first, units, base, d_queue, nullptr);
+    }
 }
 
 extern "C" {

@@ -172,6 +172,9 @@ struct PoolParams {
     unsigned* queue;
     unsigned* guard;        /* the argument-layout guard's flag (VPT_P_KARG): set when the check fails */
     unsigned guard_bias;    /* 0; vpt_debug_karg_guard sets it to make the check fail (its test) */
+    const unsigned* tile_map; /* read by pool_kernel<EST, false, true> only: the level's j-th group of 64 units is tile
+                               * tile_map[j] (a pass over a tile subset, vpt_accum.hip; level_units = 64 x the
+                               * number of listed tiles); pool_kernel's units cover every tile in order */
 };
 
 /* VPT_P_KARG: the launch parameters read where they are used, by scalar loads from the kernel-argument
@@ -220,6 +223,7 @@ struct Unit {
     bool valid;
 };
 
+template <bool TMAP>
 __device__ __forceinline__ Unit decode_unit(const PoolParams& P0, unsigned u)
 {
     VPT_PARAMS(P0);
@@ -227,7 +231,7 @@ __device__ __forceinline__ Unit decode_unit(const PoolParams& P0, unsigned u)
     Unit r;
     const unsigned c = udiv_p(u, P.level_units, P.sh_lu), rem = u - c * P.level_units;
     r.c = (int)c;
-    const unsigned tile = rem >> 6, p = rem & 63u;
+    const unsigned tile = TMAP ? P.tile_map[rem >> 6] : rem >> 6, p = rem & 63u;
     const unsigned ty = udiv_p(tile, (unsigned)P.tiles_x, P.sh_tx);
     r.x = (int)(tile - ty * (unsigned)P.tiles_x) * 8 + (int)(p & 7u);
     const int lr = (int)ty * 8 + (int)(p >> 3);  /* row within the shard */
@@ -406,7 +410,7 @@ __device__ __forceinline__ bool path_ends_after_event(uint64_t X, int depth, con
  * are taken and its camera ray is never built.  Then every ready lane runs decide() once; a path
  * that ends there goes back to ring A.  Returns the ring of the task's next stage (R_DONE:
  * retired). */
-template <int EST, bool COUNT>
+template <int EST, bool TMAP, bool COUNT>
 __device__ __forceinline__ int stage_a(TaskPool& sh, const PoolParams& P0, const DevScene* __restrict__ S,
                                        const Medium& m, Sampler<COUNT>& smp, Task& t, bool active, int lane,
                                        uint64_t below, bool dbg, ADbg& D)
@@ -474,7 +478,7 @@ __device__ __forceinline__ int stage_a(TaskPool& sh, const PoolParams& P0, const
                     if (ex) done = true;
                     else parked = true;
                 } else {
-                    const Unit uu = decode_unit(P0, ent);
+                    const Unit uu = decode_unit<TMAP>(P0, ent);
                     if (uu.valid) {  /* (an invalid unit -- a tile's padding -- is dropped) */
                         t.pix = (unsigned)uu.x | ((unsigned)uu.y << 16);
                         t.key = vpt_stream_key(P.seed, (uint64_t)(P.h - 1 - uu.y) * (uint64_t)P.w + (uint64_t)uu.x);
@@ -621,7 +625,12 @@ __device__ __forceinline__ int stage_a(TaskPool& sh, const PoolParams& P0, const
     return result;
 }
 
-template <int EST, bool COUNT>
+/* TMAP: the units' tiles come from PoolParams::tile_map, for the accumulator's passes over a tile subset.  A
+ * template parameter, instantiated for EST 0 and 1 only: read in the one kernel, behind a test for NULL, the
+ * indirection cost the free-flight render 0.7 % (a serial scalar load and a wait for every outstanding vector
+ * access at each unit hand-out; DESIGN, the accumulator's section).  With TMAP = false the code is the same
+ * as without the parameter. */
+template <int EST, bool COUNT, bool TMAP = false>
 __global__ __launch_bounds__(VPT_POOL_THREADS, VPT_POOL_WGS) void pool_kernel(PoolParams P0, Medium m0, const DevScene* __restrict__ S,
                                                    unsigned long long* counters, unsigned long long* stats)
 {
@@ -831,7 +840,7 @@ __global__ __launch_bounds__(VPT_POOL_THREADS, VPT_POOL_WGS) void pool_kernel(Po
             run_event<EST, COUNT>(S, smp, t, m, st);
             t.X = smp.X;
         }
-        next = stage_a<EST>(sh, P0, S, m, smp, t, active, lane, below, dbga, D);
+        next = stage_a<EST, TMAP>(sh, P0, S, m, smp, t, active, lane, below, dbga, D);
         SECT_BEGIN(stt);
         if (active) store_task(sh, slot, t, true);
 #if VPT_DUP == DUP_LDST

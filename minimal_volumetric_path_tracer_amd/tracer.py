@@ -149,6 +149,12 @@ class Tracer:
         p = cfg.params()
         check(lib().vpt_render_device(self._ctx, byref(p), c_void_p(out_ptr), c_void_p(stream)))
 
+    def accumulator(self, cfg: RenderConfig, chunk: Optional[int] = None) -> "Accumulator":
+        """A progressive accumulator for cfg's image or shard (vpt_accum_*): cfg.spp is the cap, a multiple of
+        the chunk (`chunk`, else cfg.chunk_spp, else min(32, spp)).  The scene must stay as it is while the
+        accumulator holds samples."""
+        return Accumulator(self, cfg, chunk)
+
     def count_work(self, cfg: RenderConfig) -> tuple[int, int]:
         """(ray-sphere tests, estimator iterations) of the reference algorithm for this render."""
         t, i = c_uint64(), c_uint64()
@@ -255,6 +261,90 @@ class Tracer:
         check(lib().vpt_phase_probe(self._ctx, float(g), d.ctypes.data, s.ctypes.data, len(s), dirs.ctypes.data,
                                     so.ctypes.data, w.ctypes.data, len(w), vals.ctypes.data))
         return dirs, so, vals
+
+
+class Accumulator:
+    """A render that can be continued (vpt_accum_*, include/vpt.h).  Samples arrive in chunk levels of
+    `chunk` samples, for all 8x8 tiles or for chosen ones; a pixel that holds m levels equals, bit for bit,
+    the pixel of ``Tracer.render(spp=m * chunk, chunk_spp=chunk)``.  Tiles are numbered row-major over the
+    shard, ``tiles_x`` per row."""
+
+    def __init__(self, tracer: Tracer, cfg: RenderConfig, chunk: Optional[int] = None):
+        p = cfg.params()
+        if chunk is not None:
+            p.chunk_spp = int(chunk)
+        h = c_void_p()
+        check(lib().vpt_accum_create(tracer._ctx, byref(p), byref(h)))
+        self._a = h
+        self._tracer = tracer  # the context must outlive the accumulator
+        tx, ty, c, ml = c_int(), c_int(), c_int(), c_int()
+        check(lib().vpt_accum_tiles(self._a, byref(tx), byref(ty), byref(c), byref(ml)))
+        self.tiles_x, self.tiles_y, self.chunk, self.max_levels = tx.value, ty.value, c.value, ml.value
+        self.width = cfg.width
+        self.rows = int(lib().vpt_shard_rows(byref(p)))
+
+    @property
+    def tiles(self) -> int:
+        return self.tiles_x * self.tiles_y
+
+    def close(self) -> None:
+        if getattr(self, "_a", None):
+            lib().vpt_accum_destroy(self._a)
+            self._a = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, levels: int = 1, tiles: Optional[Sequence[int]] = None) -> None:
+        """`levels` more chunk levels for all tiles or the listed ones (any order, no duplicates)."""
+        if tiles is None:
+            check(lib().vpt_accum_add(self._a, int(levels), None, 0))
+        else:
+            t = np.ascontiguousarray(tiles, dtype=np.int32)
+            check(lib().vpt_accum_add(self._a, int(levels), t.ctypes.data, len(t)))
+
+    def refine(self, target: float, lum_floor: float = 0.01, min_levels: int = 4, levels_per_pass: int = 1) -> dict:
+        """Adds levels to the tiles whose error is above `target` until none is left or capped."""
+        r = _lib.vpt_refine(float(target), float(lum_floor), int(min_levels), int(levels_per_pass))
+        rep = _lib.vpt_refine_report()
+        check(lib().vpt_accum_refine(self._a, byref(r), byref(rep)))
+        return {"passes": rep.passes, "tiles_converged": rep.tiles_converged, "tiles_capped": rep.tiles_capped,
+                "samples": int(rep.samples), "max_err": rep.max_err}
+
+    def image(self, fp64: bool = False) -> np.ndarray:
+        """(rows, width, 3) in file order: the average of the samples each pixel holds (0 where none)."""
+        out = np.zeros((self.rows, self.width, 3), dtype=np.float64 if fp64 else np.float32)
+        check(lib().vpt_accum_resolve(self._a, FB_F64 if fp64 else FB_F32, out.ctypes.data))
+        return out
+
+    def resolve_device(self, ptr: int, stream: int = 0, fp64: bool = False) -> None:
+        """Enqueues the resolve into a device buffer on `stream`; synchronise it before reading."""
+        check(lib().vpt_accum_resolve_device(self._a, FB_F64 if fp64 else FB_F32, c_void_p(ptr), c_void_p(stream)))
+
+    def state(self) -> dict:
+        """The arrays of vpt_accum_read: sum (rows, w, 3), s1 and s2 (rows, w), tile_levels, tile_err (tiles)."""
+        s = np.zeros((self.rows, self.width, 3))
+        s12 = np.zeros((self.rows, self.width, 2))
+        lv = np.zeros(self.tiles, dtype=np.int32)
+        er = np.zeros(self.tiles)
+        check(lib().vpt_accum_read(self._a, s.ctypes.data, s12.ctypes.data, lv.ctypes.data, er.ctypes.data))
+        return {"sum": s, "s1": np.ascontiguousarray(s12[..., 0]), "s2": np.ascontiguousarray(s12[..., 1]),
+                "tile_levels": lv, "tile_err": er}
+
+    def _to_pixels(self, per_tile: np.ndarray) -> np.ndarray:
+        g = per_tile.reshape(self.tiles_y, self.tiles_x)
+        return np.repeat(np.repeat(g, 8, axis=0), 8, axis=1)[:self.rows, :self.width]
+
+    def spp_map(self) -> np.ndarray:
+        """(rows, width) samples each pixel holds."""
+        return self._to_pixels(self.state()["tile_levels"].astype(np.int64) * self.chunk)
+
+    def error_map(self) -> np.ndarray:
+        """(rows, width) the tiles' errors, broadcast to their pixels."""
+        return self._to_pixels(self.state()["tile_err"])
 
 
 class MultiTracer:

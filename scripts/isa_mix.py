@@ -109,7 +109,7 @@ def main():
             if m:
                 sect_entries[m.group(1).strip()] = int(m.group(2))
     dis = subprocess.run([LLVM + "llvm-objdump", "-d", "--no-show-raw-insn", co], capture_output=True, text=True).stdout
-    kern = f"_ZN3vpt11pool_kernelILi{est}ELb0EE"
+    kern = f"_ZN3vpt11pool_kernelILi{est}ELb0ELb0EE"
     funcs, cur = {}, None
     for line in dis.splitlines():
         m = re.match(r"^([0-9a-f]+) <(.+)>:$", line)

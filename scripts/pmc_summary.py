@@ -17,9 +17,16 @@ import os
 import sys
 
 
+def name_matches(pattern, name):
+    """the name contains the pattern; a pattern that closes a template argument list, as in
+    'pool_kernel<0, false>', also stands for the default of a later parameter (the pool kernel's TMAP,
+    csrc/vpt_pool.h): 'pool_kernel<0, false, false>'"""
+    return pattern in name or (pattern.endswith(">") and pattern[:-1] + ", false>" in name)
+
+
 def last_dispatch(path, pattern):
     rows = list(csv.DictReader(open(path)))
-    ids = [r["Dispatch_Id"] for r in rows if pattern in r["Kernel_Name"]]
+    ids = [r["Dispatch_Id"] for r in rows if name_matches(pattern, r["Kernel_Name"])]
     if not ids:
         return None, {}
     did = ids[-1]

@@ -1,14 +1,14 @@
 #!/usr/bin/env bash
 # PMC of the pool kernel for libvpt.so variants (build_variants/libvpt_<name>.so; "base" = in-tree):
 # two short passes each (one FF bench step; PMCV_ARGS=--full also runs the north-star MIS + HG step, for
-# PMC_KERNEL="pool_kernel<1, false>"), summarised per variant.  usage: bash scripts/pmc_var.sh name...
+# PMC_KERNEL="pool_kernel<1, false, false>"), summarised per variant.  usage: bash scripts/pmc_var.sh name...
 set -u
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 P1=${P1:-"SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_ANY SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_BUSY_CYCLES SQ_INSTS_SALU SQ_INSTS_LDS"}
 P2=${P2:-"TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum TCC_EA0_WRREQ_sum"}
-# the timed dispatch only (with --full, bench.py runs the counting build, pool_kernel<EST, true>, first)
-export PMC_KERNEL=${PMC_KERNEL:-"pool_kernel<0, false>"}
+# the timed dispatch only (with --full, bench.py runs the counting build, pool_kernel<EST, true, false>, first)
+export PMC_KERNEL=${PMC_KERNEL:-"pool_kernel<0, false, false>"}
 for v in "$@"; do
     lib=build_variants/libvpt_$v.so
     [ "$v" = base ] && lib=minimal_volumetric_path_tracer_amd/libvpt.so
