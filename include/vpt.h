@@ -81,11 +81,17 @@ typedef enum {
     VPT_RAY_MARCHING_GLOBAL = 8,   /* rayMarchingGlobal, rayMarchingMethods.h:106: 10 diffuse bounces, each
                                     * marched by rayMarching in march_step segments (a count), toward the
                                     * hard-coded sphere 5 (scenes need >= 6 spheres) */
-    VPT_RAY_MARCHING_EXPLICIT = 9  /* rayMarching, rayMarchingMethods.h:34: the Color it returns for the camera
+    VPT_RAY_MARCHING_EXPLICIT = 9, /* rayMarching, rayMarchingMethods.h:34: the Color it returns for the camera
                                     * ray with sigma_t = sigma_a + sigma_s, steps = march_step (a count),
                                     * light = sphere 5; its out-parameters: vpt_ray_marching_batch */
+    VPT_HETERO_FREE = 10           /* extension: iterativeVPTracerFree's control flow in a heterogeneous medium, the
+                                    * density grid of vpt_set_density_grid (VPT_E_INVALID without one): delta
+                                    * tracking for freeFlightSample, the grid's transmittance for every
+                                    * transmittance factor; sigma_a, sigma_s are per unit density; a ray that
+                                    * leaves the grid without a hit ends its path; rendered by a kernel of its own
+                                    * (chunk_spp is ignored, as for 6-9); csrc/vpt_grid.h, csrc/vpt_hetero.h */
 } vpt_estimator;
-#define VPT_NUM_ESTIMATORS 10
+#define VPT_NUM_ESTIMATORS 11
 
 typedef enum {
     VPT_FB_F32 = 0,            /* framebuffer: 3 x float per pixel */
@@ -147,6 +153,18 @@ void vpt_context_destroy(vpt_context* ctx);
 /* Copies the scene to the device (replaces the reference's global `spheres`). */
 int vpt_set_scene(vpt_context* ctx, const vpt_sphere* spheres, int n);
 
+/* ---- heterogeneous medium (estimator VPT_HETERO_FREE) ----
+ * nx x ny x nz float32 voxels of density rho >= 0 (finite), x fastest, piecewise constant inside the world box
+ * [lo, hi]; rho = 0 outside.  The medium's coefficients are rho(x) sigma_a and rho(x) sigma_s. */
+typedef struct vpt_grid_desc {
+    int32_t nx, ny, nz, reserved_;
+    double lo[3], hi[3];
+} vpt_grid_desc;
+/* Copies the grid to the device (synchronous); desc NULL clears it.  The grid persists across vpt_set_scene and
+ * must not change while a render is in flight.  A dimension < 1, hi <= lo, a NaN, negative or infinite density
+ * or more than 2^27 voxels -> VPT_E_INVALID (the previous grid stays). */
+int vpt_set_density_grid(vpt_context* ctx, const vpt_grid_desc* desc, const float* density);
+
 /* Renders into a DEVICE buffer on `stream` (a hipStream_t, NULL = default stream); returns
  * after enqueueing.  d_out: vpt_shard_rows(p) * width * 3 elements of fb_format, the
  * per-pixel average BEFORE the clamp of src/rt.cpp:803.  Renders on different streams of one
@@ -169,6 +187,8 @@ int vpt_render(vpt_context* ctx, const vpt_params* p, void* h_out);
 typedef struct vpt_multi vpt_multi;
 int vpt_multi_create(int n_gpus, vpt_multi** out);
 int vpt_multi_set_scene(vpt_multi* m, const vpt_sphere* spheres, int n);
+/* vpt_set_density_grid on every context of the handle */
+int vpt_multi_set_density_grid(vpt_multi* m, const vpt_grid_desc* desc, const float* density);
 int vpt_multi_render(vpt_multi* m, const vpt_params* p, void* h_out);
 void vpt_multi_destroy(vpt_multi* m);
 /* one-shot: create, set the scene, render, destroy */
@@ -280,6 +300,17 @@ int vpt_math_probe(vpt_context* ctx, int fn, const double* x, const double* y, d
  * synchronous (property tests). */
 int vpt_phase_probe(vpt_context* ctx, double g, const double din[3], const uint64_t* states, int n, double* dirs,
                     uint64_t* states_out, const double* wl, int nw, double* values);
+
+/* Density-grid probe (csrc/vpt_grid.h) on the GPU, in the style of vpt_phase_probe: for each of the n rays
+ * (unit directions) with surface distance tmax[i] and erand48 state states[i]: tau[i] = the optical depth of
+ * the context's grid over t in [0, tmax[i]] (no draw), t_coll[i] = the delta-tracking result for sigma_t (-1:
+ * none, NaN: the 2^22-step cap), states_out[i] = the state after the track.  Host arrays, synchronous. */
+int vpt_grid_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
+                   int n, double* tau, double* t_coll, uint64_t* states_out);
+/* the same code compiled for the host, on a grid given directly (no GPU needed) */
+int vpt_grid_probe_host(const vpt_grid_desc* desc, const float* density, double sigma_t, const vpt_ray* rays,
+                        const double* tmax, const uint64_t* states, int n, double* tau, double* t_coll,
+                        uint64_t* states_out);
 
 /* PPM writer of main() (src/rt.cpp:812-820): clamp to [0,1] (src/rt.cpp:803), gamma 1/2.2,
  * int(v*255 + .5) (include/mathUtilities.h:43-45), "P3\n%d %d\n255\n" then "%d %d %d " per

@@ -23,6 +23,7 @@ VPT_E_INVALID, VPT_E_TOO_MANY, VPT_E_NO_EMITTER, VPT_E_UNSUPPORTED, VPT_E_HIP, V
 VPT_MAX_SPHERES = 64
 FREE_FLIGHT, MIS_EQUIANGULAR, EXPLICIT_FREE, IMPLICIT_FREE, EXPLICIT_EQUIANGULAR, SURFACE_PT, RAY_MARCHING = 0, 1, 2, 3, 4, 5, 6  # vpt_estimator
 RAY_MARCHING_SA, RAY_MARCHING_GLOBAL, RAY_MARCHING_EXPLICIT = 7, 8, 9
+HETERO_FREE = 10
 FB_F32, FB_F64 = 0, 1
 
 # numpy view of vpt_sphere == reference Sphere (include/Sphere.h:12-21), 144 bytes
@@ -71,6 +72,11 @@ class vpt_params(ctypes.Structure):
     ]
 
 
+class vpt_grid_desc(ctypes.Structure):
+    _fields_ = [("nx", c_int32), ("ny", c_int32), ("nz", c_int32), ("reserved_", c_int32), ("lo", c_double * 3),
+                ("hi", c_double * 3)]
+
+
 class vpt_refine(ctypes.Structure):
     _fields_ = [("target", c_double), ("lum_floor", c_double), ("min_levels", c_int32), ("levels_per_pass", c_int32)]
 
@@ -96,10 +102,12 @@ PROTOTYPES = [
     ("vpt_context_create", c_int, [c_int, POINTER(c_void_p)]),
     ("vpt_context_destroy", None, [c_void_p]),
     ("vpt_set_scene", c_int, [c_void_p, c_void_p, c_int]),
+    ("vpt_set_density_grid", c_int, [c_void_p, POINTER(vpt_grid_desc), c_void_p]),
     ("vpt_render_device", c_int, [c_void_p, POINTER(vpt_params), c_void_p, c_void_p]),
     ("vpt_render", c_int, [c_void_p, POINTER(vpt_params), c_void_p]),
     ("vpt_multi_create", c_int, [c_int, POINTER(c_void_p)]),
     ("vpt_multi_set_scene", c_int, [c_void_p, c_void_p, c_int]),
+    ("vpt_multi_set_density_grid", c_int, [c_void_p, POINTER(vpt_grid_desc), c_void_p]),
     ("vpt_multi_render", c_int, [c_void_p, POINTER(vpt_params), c_void_p]),
     ("vpt_multi_destroy", None, [c_void_p]),
     ("vpt_render_multi", c_int, [c_void_p, c_int, POINTER(vpt_params), c_int, c_void_p]),
@@ -122,6 +130,9 @@ PROTOTYPES = [
     ("vpt_math_probe", c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int]),
     ("vpt_phase_probe", c_int, [c_void_p, c_double, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                 c_void_p]),
+    ("vpt_grid_probe", c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    ("vpt_grid_probe_host", c_int, [POINTER(vpt_grid_desc), c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int,
+                                    c_void_p, c_void_p, c_void_p]),
     ("vpt_write_ppm", c_int, [c_char_p, c_void_p, c_int, c_int, c_int]),
     ("vpt_encode_ppm", c_int64, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64]),
     ("vpt_last_error", c_char_p, []),

@@ -534,6 +534,13 @@ VPT_DEV double transmitance(dv3 a, dv3 b, double sigma_t)
     return lm_exp(sigma_t * d * -1.0);
 }
 
+/* Transmittance policy of the helpers estimator 10 (vpt_hetero.h) shares with the homogeneous estimators:
+ * TrHom (the default) selects the code above, unchanged; a policy with hom == false supplies
+ * between(a, b, sigma_t) and along(o, unit d, dist, sigma_t) -- the density grid's transmittance. */
+struct TrHom {
+    static constexpr bool hom = true;
+};
+
 /* multipleT, include/volumetricBasicFunctions.h:26-57 (material-3 spheres only) */
 template <bool COUNT>
 VPT_DEV double multiple_t(const DevScene* __restrict__ S, Sampler<COUNT>& smp, dv3 x1, dv3 x2, double sigma_t)
@@ -910,9 +917,9 @@ VPT_DEV double power_heuristic(double f, double g)
 
 /* MISv2, include/misSamplingFunctions.h:96-170 (TR = true), and MIS, :19-91 (TR = false): the same
  * function without the transmitance factor on the light samples (:29 vs :106) */
-template <bool COUNT, int MK = -1, bool TR = true>
+template <bool COUNT, int MK = -1, bool TR = true, class TP = TrHom>
 VPT_DEV dv3 mis_v2(const DevScene* __restrict__ S, Sampler<COUNT>& smp, int obj, dv3 x, dv3 n, dv3 wray, double alpha,
-                   double sigma_t)
+                   double sigma_t, const TP& tp = TP())
 {
     const int omat = mat_of<MK>(S, obj);
     dv3 mc = mk(0, 0, 0), g;
@@ -923,7 +930,11 @@ VPT_DEV dv3 mis_v2(const DevScene* __restrict__ S, Sampler<COUNT>& smp, int obj,
     for (int k = 0; k < S->n_mis; ++k) {  /* spheres with r > 0 && radiance.x > 0, in index order */
         const int light = S->mis_light[k];
         dv3 f = light_sample_sa(S, smp, light, x, obj, omat, n, wray, wiLight, cmax, alpha);
-        if (TR) f = scl(f, transmitance(x, sph_p(S, light), sigma_t));
+        if constexpr (TP::hom) {
+            if (TR) f = scl(f, transmitance(x, sph_p(S, light), sigma_t));
+        } else {
+            if (TR) f = scl(f, tp.between(x, sph_p(S, light), sigma_t));
+        }
         fpdf = solid_angle_prob(cmax);
         if (omat == 0) {
             gpdf = hemi_cosine_prob(dot(n, wiLight));
@@ -1396,30 +1407,33 @@ VPT_DEV dv3 p_light_nee(const DevScene* __restrict__ S, Sampler<COUNT>& smp, int
 /* mag: |lp - xt|, formed by the caller (VPT_PL_REUSE: visibility's distance and the transmittance's are
  * the same root of the same dot product) */
 /* the radiance of a visible point light (wl = nrm(lp - xt) under VPT_PL_REUSE) */
-template <bool COUNT>
+template <bool COUNT, class TP = TrHom>
 VPT_DEV dv3 point_shadow_value(const DevScene* __restrict__ S, Sampler<COUNT>& smp, dv3 xt, dv3 din, int src,
                                double sigma_t, bool with_sigma, double sigma_s, double trxt, double probSource,
-                               double mag, dv3 wl)
+                               double mag, dv3 wl, const TP& tp = TP())
 {
     const dv3 lp = sph_p(S, src);
     const dv3 rad = sph_rad(S, src);
     double distanceLight = dot(sub(lp, xt), sub(lp, xt));
     dv3 Le = scl(rad, (1 / distanceLight));
     double ph = smp.g == 0.0 ? 1 / (4 * VPT_PI) : phase_value(smp.g, din, VPT_PL_REUSE ? wl : nrm(sub(lp, xt)));
-    dv3 Ls = scl(scl(Le, VPT_PL_REUSE ? lm_exp(sigma_t * mag * -1.0) : transmitance(xt, lp, sigma_t)), ph);
+    dv3 Ls;
+    if constexpr (TP::hom) Ls = scl(scl(Le, VPT_PL_REUSE ? lm_exp(sigma_t * mag * -1.0) : transmitance(xt, lp, sigma_t)), ph);
+    else Ls = scl(scl(Le, tp.between(xt, lp, sigma_t)), ph);
     if (with_sigma) return scl(scl(scl(Ls, trxt), sigma_s), (1 / probSource));
     return scl(Ls, (1 / probSource));
 }
-template <bool COUNT>
+template <bool COUNT, class TP = TrHom>
 VPT_DEV dv3 point_shadow_ld(const DevScene* __restrict__ S, Sampler<COUNT>& smp, dv3 xt, dv3 din, int src,
-                            double sigma_t, bool with_sigma, double sigma_s, double trxt, double probSource, double mag)
+                            double sigma_t, bool with_sigma, double sigma_s, double trxt, double probSource, double mag,
+                            const TP& tp = TP())
 {
     const dv3 lp = sph_p(S, src);
     dv3 Ld = mk(0, 0, 0);
     const dv3 wl = VPT_PL_REUSE ? nrm(sub(lp, xt)) : mk(0, 0, 0);
     if (VPT_PL_REUSE ? visibility_pre(S, smp, lp, mag, wl, false, -1.0, false)
                      : visibility(S, smp, lp, xt, false, -1.0, false))
-        Ld = point_shadow_value(S, smp, xt, din, src, sigma_t, with_sigma, sigma_s, trxt, probSource, mag, wl);
+        Ld = point_shadow_value(S, smp, xt, din, src, sigma_t, with_sigma, sigma_s, trxt, probSource, mag, wl, tp);
     return Ld;
 }
 
@@ -1435,10 +1449,10 @@ VPT_DEV dv3 point_shadow_ld(const DevScene* __restrict__ S, Sampler<COUNT>& smp,
 #define VPT_SS_FUSE 1
 #endif
 
-template <bool COUNT, int LT = -1>  /* LT: 1 point light, 0 not, -1 unknown (read r) */
+template <bool COUNT, int LT = -1, class TP = TrHom>  /* LT: 1 point light, 0 not, -1 unknown (read r) */
 VPT_DEV dv3 single_scattering(const DevScene* __restrict__ S, Sampler<COUNT>& smp, dv3 xt, dv3 din, int src,
                               double sigma_t, bool with_sigma, double sigma_s, double trxt, double probSource,
-                              bool zero_ok = false)
+                              bool zero_ok = false, const TP& tp = TP())
 {
     const double lr = LT == 1 ? 0.0 : S->sph[src].r;
     const dv3 lp = sph_p(S, src);
@@ -1508,14 +1522,16 @@ VPT_DEV dv3 single_scattering(const DevScene* __restrict__ S, Sampler<COUNT>& sm
     if (shl) {
         smp.tests(S->n);  /* the shadow ray (cast in the pass above) or the cone ray: each is counted */
         if (tdist > mag || tdist == 0)  /* visibility_pre */
-            Ld = point_shadow_value(S, smp, xt, din, src, sigma_t, with_sigma, sigma_s, trxt, probSource, mag, wls);
+            Ld = point_shadow_value(S, smp, xt, din, src, sigma_t, with_sigma, sigma_s, trxt, probSource, mag, wls, tp);
     } else if (src == idHit) {
         if (point) smp.tests(S->n);  /* the shadow ray the reference casts first (result overwritten) */
         /* a point light's cone (cmax == 1: prob_wl = +inf) scores Ls * (1 / inf) = +-0 with Ls finite
          * (SURVEY H5); zero_ok: the caller's update absorbs a signed zero (finite throughput and
          * pdf), so +0 is the same result without the exponential and the phase value */
         if (!(point && zero_ok && cmax == 1.0)) {
-            double it = lm_exp(sigma_t * tdist * -1.0);
+            double it;
+            if constexpr (TP::hom) it = lm_exp(sigma_t * tdist * -1.0);
+            else it = tp.along(xt, wl, tdist, sigma_t);
             double ph = smp.g == 0.0 ? 1 / (4 * VPT_PI) : phase_value(smp.g, din, wl);
             dv3 Ls = scl(scl(rad, it), ph);
             if (with_sigma) Ld = scl(scl(scl(scl(Ls, trxt), sigma_s), (1 / prob_wl)), (1 / probSource));
@@ -1523,7 +1539,7 @@ VPT_DEV dv3 single_scattering(const DevScene* __restrict__ S, Sampler<COUNT>& sm
         }
     } else if (point) {
         SECT_BEGIN(swi);
-        Ld = point_shadow_ld(S, smp, xt, din, src, sigma_t, with_sigma, sigma_s, trxt, probSource, mag);
+        Ld = point_shadow_ld(S, smp, xt, din, src, sigma_t, with_sigma, sigma_s, trxt, probSource, mag, tp);
         SECT_END(swi, SECT_M_SHADOW_IN);
     }
     SECT_END(sw, SECT_M_SS_SHADOW);

@@ -1,0 +1,180 @@
+/*
+ * vpt_hetero.h -- estimator 10 (VPT_HETERO_FREE): the control flow of iterativeVPTracerFree (estimator 0,
+ * include/vptShadeMethods.h:1263-1340) in a heterogeneous medium, the density grid of vpt_grid.h.  An
+ * extension: the reference has no counterpart.  Draw for draw estimator 0, with two substitutions:
+ *   - freeFlightSample becomes delta tracking: a collision is a medium event at t; "none" with a hit is a
+ *     surface event; "none" without a hit ends the path with no contribution (the ray left into vacuum);
+ *   - every transmittance factor estimator 0 reaches becomes the grid's over the same segment: Trs to the
+ *     picked light's centre, MISv2's per-light factor, the point-light factor of freeSingleScattering and the
+ *     factor over tdist along the sampled cone direction (the TP policy of vpt_device.h's helpers).
+ * Material-3 spheres keep their multipleT treatment; hg_g and max_depth act as in estimator 0.
+ * No branch of estimator 0 depends on a transmittance value, so on a uniform rho == 1 grid that contains
+ * every path this estimator walks estimator 0's paths with the same draws and differs only in the rounding
+ * of tau (tests/test_gpu_hetero.py).  The steps are the generic (MK = -1, LT = -1) statements of
+ * decide / surface_event / medium_event<0>: the tuned instantiations of the pool kernel are not touched.
+ */
+#ifndef VPT_HETERO_H
+#define VPT_HETERO_H
+
+#include "vpt_device.h"
+
+#define VPT_GRID_EXP lm_exp
+#define VPT_GRID_LOG lm_log
+#include "vpt_grid.h"
+
+namespace vpt {
+
+/* the grid's transmittance as the TP policy of mis_v2 / single_scattering (vpt_device.h TrHom) */
+struct GridTr {
+    static constexpr bool hom = false;
+    vpt_grid_view G;
+    __device__ __forceinline__ double along(dv3 o, dv3 d, double dist, double sigma_t) const
+    {
+        const double oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
+        return vpt_grid_transmittance(&G, oo, dd, dist, sigma_t);
+    }
+    /* a to b: the distance and the unit direction formed as transmitance() and nrm() form them */
+    __device__ __forceinline__ double between(dv3 a, dv3 b, double sigma_t) const
+    {
+        const dv3 aux = sub(b, a);
+        const double dist = vm_sqrt(dot(aux, aux));
+        if (!(dist > 0)) return lm_exp(sigma_t * 0.0 * -1.0);
+        return along(a, nrm(aux), dist, sigma_t);
+    }
+};
+
+/* measurement only (vpt_debug_hetero_steps): delta-tracking calls and their tentative steps */
+struct HeteroStats {
+    unsigned long long tracks, steps;
+};
+
+/* decide<0> with delta tracking in freeFlightSample's place */
+template <bool COUNT>
+VPT_DEV int hetero_decide(const DevScene* __restrict__ S, const GridTr& tp, Sampler<COUNT>& smp, Path& p, Event& e,
+                          const Medium& m, HeteroStats* hs = nullptr)
+{
+    const double sigma_t = m.sigma_a + m.sigma_s;
+    int id = 0;
+    double t = 0.0;
+    const bool hit = scene_intersect_grouped<VPT_DECIDE_GROUP>(S, smp, p.o, p.d, t, id);
+    if (!hit) t = VPT_MAXFLOAT;
+    e.t = t;
+    e.id = id;
+    const int count = S->n_emit;
+    if (VPT_UNLIKELY(count == 0)) return EV_END;
+    e.src = emit_pick(S, (int)(smp.next() * count), count);
+    const double oo[3] = {p.o.x, p.o.y, p.o.z}, dd[3] = {p.d.x, p.d.y, p.d.z};
+    uint32_t nsteps = 0;
+    const double tc = vpt_grid_track(&tp.G, oo, dd, t, sigma_t, &smp.X, hs ? &nsteps : (uint32_t*)nullptr);
+    if (hs) {
+        hs->tracks += 1;
+        hs->steps += nsteps;
+    }
+    if (VPT_UNLIKELY(tc != tc)) {  /* the step cap: NaN, like trace_ray_marching's */
+        p.L = mk(tc, tc, tc);
+        return EV_END;
+    }
+    if (tc >= 0) {
+        e.dist = tc;
+        return EV_MED;
+    }
+    if (!hit) return EV_END;  /* left the medium into vacuum */
+    if (sph_flag(S->m_emitter, id)) {  /* the path ends on a light; only a camera ray sees it */
+        if (p.depth == 0) p.L = mul(sph_rad(S, id), p.beta);
+        return EV_END;
+    }
+    return EV_SURF;
+}
+
+/* surface_event<0> (MK = -1, PT = -1) */
+template <bool COUNT>
+VPT_DEV void hetero_surface(const DevScene* __restrict__ S, const GridTr& tp, Sampler<COUNT>& smp, Path& p,
+                            const Event& e, const Medium& m)
+{
+    const double sigma_t = m.sigma_a + m.sigma_s;
+    const double continueprob = 0.6;
+    const int id = e.id, src = e.src;
+    const dv3 xs = add(p.o, scl(p.d, e.t));
+    const dv3 nx = nrm(sub(xs, sph_p(S, id)));
+    const double probSource = 1.0 / S->n_emit;
+    const double alpha = S->sph[id].alpha;
+    const double Trs = tp.between(xs, sph_p(S, src), sigma_t);
+    const dv3 Ldp = scl(scl(p_light<COUNT>(S, smp, id, xs, nx, p.d, src, alpha), Trs), (1 / probSource));
+    const dv3 Ld = mis_v2<COUNT, -1, true, GridTr>(S, smp, id, xs, nx, p.d, alpha, sigma_t, tp);
+    p.L = add(p.L, scl(mul(add(Ldp, Ld), p.beta), (1 / continueprob)));
+    dv3 wi = mk(0, 0, 0);
+    double pdf = 0;
+    const dv3 fs = bdsf<COUNT>(S, smp, wi, p.d, nx, pdf, id);
+    wi = nrm(wi);
+    const double cosine = dot(nx, wi);
+    p.beta = scl(scl(scl(mul(p.beta, fs), (1 / continueprob)), cosine), (1 / pdf));
+    p.o = xs;
+    p.d = wi;
+    p.depth++;
+}
+
+/* medium_event<0> (LT = -1): freeSingleScattering toward the picked light, the phase continuation; the
+ * local albedo rho sigma_s / (rho sigma_t) is medium_tail's sigma_s / sigma_t */
+template <bool COUNT>
+VPT_DEV void hetero_medium(const DevScene* __restrict__ S, const GridTr& tp, Sampler<COUNT>& smp, Path& p,
+                           const Event& e, const Medium& m)
+{
+    const double sigma_t = m.sigma_a + m.sigma_s;
+    const dv3 xt = add(p.o, scl(p.d, e.dist));
+    const double probSource = 1.0 / S->n_emit;
+    const bool zero_ok = p.beta.x - p.beta.x == 0 && p.beta.y - p.beta.y == 0 && p.beta.z - p.beta.z == 0;
+    const dv3 Ld = single_scattering<COUNT, -1, GridTr>(S, smp, xt, p.d, e.src, sigma_t, false, m.sigma_s, 1.0, probSource,
+                                                        zero_ok, tp);
+    medium_tail<0, COUNT>(smp, p, Ld, 1.0, e.pdf, xt, m, true);
+}
+
+/* one camera sample, sequentially (vpt_trace_batch, render_kernel_simple<10>) */
+template <bool COUNT>
+__device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridTr& tp, Sampler<COUNT>& smp, dv3 o, dv3 d,
+                                   const Medium& m, HeteroStats* hs = nullptr)
+{
+    Path p;
+    p.o = o;
+    p.d = d;
+    p.beta = mk(1, 1, 1);
+    p.L = mk(0, 0, 0);
+    p.depth = 0;
+    Event e;
+    e.pdf = 0;
+    while (continue_path(smp, p, m)) {
+        const int ev = hetero_decide(S, tp, smp, p, e, m, hs);
+        if (ev == EV_END) break;
+        if (ev == EV_SURF) hetero_surface(S, tp, smp, p, e, m);
+        else hetero_medium(S, tp, smp, p, e, m);
+    }
+    return p.L;
+}
+
+/* what hetero_kernel (vpt_hetero.hip) needs of a render: vpt_kernels.hip fills it from its own parameters */
+struct HeteroParams {
+    int32_t w, h, spp, fb;
+    int32_t band_rows, band_stride, band_offset, shard_rows;
+    int32_t tiles_x, tiles_y;
+    uint64_t seed;
+    double o[3], d[3], cx[3], cy[3];
+    void* out;
+    unsigned* queue;               /* pixel work queue head (zeroed before the launch) */
+    const vpt_grid_view* grid;     /* device */
+};
+
+}  // namespace vpt
+
+/* vpt_hetero.hip: the persistent-wave render kernel of estimator 10, enqueued on `stream` (the caller owns
+ * the queue word and has zeroed it in stream order) */
+int vpt_int_hetero_launch(int device, const vpt::HeteroParams& H, const vpt::Medium& m, const DevScene* S, void* stream);
+/* render_kernel_simple<10> for the same render (counters: vpt_count_work's device counters, else NULL) */
+int vpt_int_hetero_simple_launch(const vpt::HeteroParams& H, const vpt::Medium& m, const DevScene* S,
+                                 unsigned long long* counters, void* stream);
+/* the per-sample call and the grid probe on device arrays, default stream (the caller reads hipGetLastError);
+ * stats: vpt_debug_hetero_steps' two counters, else NULL */
+void vpt_int_hetero_trace_launch(const vpt_ray* rays, const uint64_t* states, int n, const vpt::Medium& m, const DevScene* S,
+                                 const vpt_grid_view* grid, double* out, uint64_t* out_states, unsigned long long* stats);
+void vpt_int_grid_probe_launch(const vpt_grid_view* grid, double sigma_t, const vpt_ray* rays, const double* tmax,
+                               const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out);
+
+#endif

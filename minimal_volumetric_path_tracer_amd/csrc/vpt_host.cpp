@@ -20,6 +20,7 @@
 #include <thread>
 
 #include "vpt_accum.h"
+#include "vpt_grid.h"
 #include "vpt_internal.h"
 #include "vpt_rng.h"
 
@@ -37,6 +38,20 @@ int vpt_fail(int code, const char* fmt, ...)
 }
 
 void vpt_clear_error(void) { g_err.clear(); }
+
+/* vpt_grid_bad (csrc/vpt_grid.h) as a status with its message */
+int vpt_int_grid_check(const vpt_grid_desc* desc, const float* density, const char* who)
+{
+    if (!desc || !density) return vpt_fail(VPT_E_INVALID, "%s: NULL grid", who);
+    const int32_t n[3] = {desc->nx, desc->ny, desc->nz};
+    switch (vpt_grid_bad(n, desc->lo, desc->hi, density)) {
+    case 1: return vpt_fail(VPT_E_INVALID, "%s: grid %d x %d x %d (each dimension >= 1, at most 2^27 voxels)", who,
+                            desc->nx, desc->ny, desc->nz);
+    case 2: return vpt_fail(VPT_E_INVALID, "%s: the box must be finite with hi > lo", who);
+    case 3: return vpt_fail(VPT_E_INVALID, "%s: densities must be finite and >= 0", who);
+    }
+    return VPT_OK;
+}
 
 extern "C" {
 
@@ -167,6 +182,28 @@ int vpt_accum_select_host(const int32_t* tile_levels, const double* tile_err, in
     for (int t = 0; t < n_tiles; ++t)
         if (vpt_accum_active(tile_levels[t], tile_err[t], r->min_levels, max_levels, r->target)) active[k++] = t;
     return k;
+}
+
+/* ---- the density grid's walkers on host arrays (csrc/vpt_grid.h) ---- */
+int vpt_grid_probe_host(const vpt_grid_desc* desc, const float* density, double sigma_t, const vpt_ray* rays,
+                        const double* tmax, const uint64_t* states, int n, double* tau, double* t_coll,
+                        uint64_t* states_out)
+{
+    vpt_clear_error();
+    if (!rays || !tmax || !states || n < 0) return vpt_fail(VPT_E_INVALID, "vpt_grid_probe_host: bad arguments");
+    int rc = vpt_int_grid_check(desc, density, "vpt_grid_probe_host");
+    if (rc) return rc;
+    const int32_t dims[3] = {desc->nx, desc->ny, desc->nz};
+    vpt_grid_view G;
+    vpt_grid_view_init(&G, dims, desc->lo, desc->hi, density, density);
+    for (int i = 0; i < n; ++i) {
+        uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
+        if (tau) tau[i] = vpt_grid_tau(&G, rays[i].o, rays[i].d, tmax[i]);
+        const double tc = vpt_grid_track(&G, rays[i].o, rays[i].d, tmax[i], sigma_t, &X, nullptr);
+        if (t_coll) t_coll[i] = tc;
+        if (states_out) states_out[i] = X;
+    }
+    return VPT_OK;
 }
 
 /* ---- PPM ---- */

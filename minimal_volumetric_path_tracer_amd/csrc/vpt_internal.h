@@ -16,4 +16,7 @@ int vpt_int_check_params(const vpt_context* ctx, const vpt_params* p);  /* build
 int vpt_int_pool_pass(vpt_context* ctx, const vpt_params* p, int C, int k0, int k1, const unsigned* d_tiles,
                       unsigned n_tiles, double* d_partials, unsigned* d_queue);
 
+/* vpt_grid_bad's verdict on a grid as a vpt_status with its message (vpt_host.cpp) */
+int vpt_int_grid_check(const vpt_grid_desc* desc, const float* density, const char* who);
+
 #endif

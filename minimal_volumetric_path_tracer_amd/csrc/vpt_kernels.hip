@@ -19,6 +19,7 @@
 
 #include "vpt_device.h"
 #include "vpt_pool.h"
+#include "vpt_render_simple.h"
 #include "vpt_internal.h"
 
 /* the EST = 1 pool kernel comes from vpt_pool_mis.hip, compiled with flags of its own (VPT_MIS_TU;
@@ -42,93 +43,12 @@ using namespace vpt;
 
 namespace {
 
-struct KParams {
-    int32_t w, h, spp, fb;
-    int32_t band_rows, band_stride, band_offset, shard_rows;
-    double sigma_a, sigma_s, g;
-    int32_t max_depth, est;
-    double march_step;             /* rayMarching3 (estimator 6) */
-    int32_t march_light;
-    uint64_t seed;
-    double o[3], d[3], cx[3], cy[3];
-    void* out;
-    unsigned long long* counters;  /* counting mode: [tests, iterations] */
-    unsigned* queue;               /* pixel work queue head (zeroed before each launch) */
-    int32_t tiles_x, tiles_y;      /* 8x8 pixel tiles covering the shard */
-    int32_t cost_surf, cost_med;   /* event scheduler weights */
-    int32_t chunk;                 /* samples per partial sum (pool kernel) */
-    int32_t taper;                 /* tapered chunk layout (auto mode, vpt_chunks.h) */
-};
-
 #define HIP_OK(expr)                                                                         \
     do {                                                                                     \
         hipError_t e_ = (expr);                                                              \
         if (e_ != hipSuccess)                                                                \
             return vpt_fail(VPT_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));       \
     } while (0)
-
-template <int EST, bool COUNT, int FB>
-__global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const DevScene* __restrict__ S)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
-    const int lr = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
-    /* rayMarching3: every shadow ray leaves the light's centre, so oc and |oc|^2 of each sphere are
-     * formed once per workgroup (round 3: 26.7 -> 32.4 Msamples/s) */
-    __shared__ double march_oc[EST == 6 ? VPT_MAX_SPHERES : 1][4];
-    if (EST == 6) {
-        march_origin_init(S, sph_p(S, P.march_light), march_oc);
-        __syncthreads();
-    }
-    if (x >= P.w || lr >= P.shard_rows) return;
-    const int k = lr / P.band_rows, r = lr - k * P.band_rows;
-    const int fr = (P.band_offset + k * P.band_stride) * P.band_rows + r;  /* file row */
-    const int y = P.h - 1 - fr;                                              /* camera row */
-    const uint64_t idx = (uint64_t)fr * (uint64_t)P.w + (uint64_t)x;          /* src/rt.cpp:773 */
-    const Medium m{P.sigma_a, P.sigma_s, P.g, P.max_depth, P.march_step, P.march_light};
-    const dv3 o = mk(P.o[0], P.o[1], P.o[2]), cd = mk(P.d[0], P.d[1], P.d[2]);
-    const dv3 cx = mk(P.cx[0], P.cx[1], P.cx[2]), cy = mk(P.cy[0], P.cy[1], P.cy[2]);
-    dv3 acc = mk(0, 0, 0);
-    uint64_t tests = 0, iters = 0, mism = 0;
-    for (int i = 0; i < P.spp; ++i) {
-        Sampler<COUNT> smp;
-        smp.X = vpt_stream_start(P.seed, idx, (uint64_t)i);
-        smp.g = P.g;
-        smp.cnt.tests = 0;
-        smp.cnt.iterations = 0;
-        smp.cnt.draw_mismatch = 0;
-        /* jittered camera ray, src/rt.cpp:787, x draw first */
-        double jx = smp.next();
-        double jy = smp.next();
-        dv3 dir = add(add(scl(cx, (((double)x + jx - 0.5) / P.w - .5)), scl(cy, (((double)y + jy - 0.5) / P.h - .5))), cd);
-        dir = nrm(dir);
-        dv3 L = trace_sample<EST, COUNT>(S, smp, o, dir, m, EST == 6 ? march_oc : nullptr);
-        acc = add(L, acc);
-        if (COUNT) {
-            tests += smp.cnt.tests;
-            iters += smp.cnt.iterations;
-            mism += smp.cnt.draw_mismatch;
-        }
-    }
-    acc = scl(acc, (1 / (double)P.spp));
-    const size_t oi = ((size_t)lr * (size_t)P.w + (size_t)x) * 3;
-    if (FB == VPT_FB_F32) {
-        float* out = (float*)P.out;
-        out[oi] = (float)acc.x;
-        out[oi + 1] = (float)acc.y;
-        out[oi + 2] = (float)acc.z;
-    } else {
-        double* out = (double*)P.out;
-        out[oi] = acc.x;
-        out[oi + 1] = acc.y;
-        out[oi + 2] = acc.z;
-    }
-    if (COUNT) {
-        atomicAdd(&P.counters[0], (unsigned long long)tests);
-        atomicAdd(&P.counters[1], (unsigned long long)iters);
-        if (mism) atomicAdd(&P.counters[2], (unsigned long long)mism);
-    }
-}
 
 /* camera ray of one sample, src/rt.cpp:787 (x draw first) */
 template <bool COUNT>
@@ -452,6 +372,10 @@ struct vpt_context {
     std::vector<std::unique_ptr<StreamSlot>> slots;  /* stable addresses */
     unsigned long long tick = 0;
     int launch_log2 = LAUNCH_LOG2_MAX;  /* samples per workgroup per launch <= 2^launch_log2 (vpt_debug_set_launch_bound) */
+    /* the density grid of estimator 10 (vpt_set_density_grid): its view and its voxels on the device */
+    vpt_grid_view* d_grid = nullptr;
+    float* d_rho = nullptr;
+    int has_grid = 0;
 };
 
 /* The stream's slot, created on first use (or taken over from an idle stream once MAX_STREAM_SLOTS
@@ -523,6 +447,10 @@ static int check_medium(const vpt_medium* m)
  * (include/rayMarchingMethods.h:64,153), so the scene needs at least 6 spheres */
 static int check_march(const vpt_context* ctx, const vpt_medium* m)
 {
+    if (m->estimator == VPT_HETERO_FREE) {
+        if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "estimator %d needs a density grid (vpt_set_density_grid)", m->estimator);
+        return VPT_OK;
+    }
     if (m->estimator < VPT_RAY_MARCHING) return VPT_OK;
     if (!is_finite(m->march_step) || !(m->march_step > 0))
         return vpt_fail(VPT_E_INVALID, "march_step must be finite and > 0");
@@ -585,6 +513,7 @@ static int build_kparams(const vpt_context* ctx, const vpt_params* p, void* d_ou
     K.cy[1] = cry * inv * p->fov_scale;
     K.cy[2] = crz * inv * p->fov_scale;
     K.out = d_out;
+    K.grid = ctx->has_grid ? ctx->d_grid : nullptr;
     if (p->chunk_spp < 0) return vpt_fail(VPT_E_INVALID, "chunk_spp must be >= 0");
     /* auto: 32 samples per work unit (A/B at 1024^2 x 256: chunk 4 / 8 / 16 / 32 / 64 -> 3816 / 3969 /
      * 4085 / 4153 / 4129 Ms/s), the last 32 of a pixel tapered (vpt_chunks.h); spp <= 32 is then one
@@ -655,25 +584,76 @@ static int log2_exact(int64_t v)
     return k;
 }
 
+/* VPT_SIMPLE_KERNEL=1 selects render_kernel_simple<10> for estimator 10 in every build (the production
+ * library ignores the variable for estimators 0-9, env_int): the one-lane-per-pixel kernel is the new
+ * kernel's reference in tests/test_gpu_hetero.py, which must be able to run it on the library as shipped */
+static bool hetero_simple_kernel()
+{
+    const char* v = getenv("VPT_SIMPLE_KERNEL");
+    return v && *v && atoi(v) != 0;
+}
+
+/* estimator 10 (vpt_hetero.hip): hetero_kernel on the stream's queue word; counting mode and
+ * VPT_SIMPLE_KERNEL=1: render_kernel_simple<10> */
+static int launch_hetero(vpt_context* ctx, const KParams& K, bool count, hipStream_t stream)
+{
+    HeteroParams H;
+    memset(&H, 0, sizeof H);
+    H.w = K.w;
+    H.h = K.h;
+    H.spp = K.spp;
+    H.fb = K.fb;
+    H.band_rows = K.band_rows;
+    H.band_stride = K.band_stride;
+    H.band_offset = K.band_offset;
+    H.shard_rows = K.shard_rows;
+    H.tiles_x = K.tiles_x;
+    H.tiles_y = K.tiles_y;
+    H.seed = K.seed;
+    for (int i = 0; i < 3; ++i) {
+        H.o[i] = K.o[i];
+        H.d[i] = K.d[i];
+        H.cx[i] = K.cx[i];
+        H.cy[i] = K.cy[i];
+    }
+    H.out = K.out;
+    H.grid = K.grid;
+    const Medium m{K.sigma_a, K.sigma_s, K.g, K.max_depth, K.march_step, K.march_light};
+    if (count || hetero_simple_kernel()) return vpt_int_hetero_simple_launch(H, m, ctx->d_scene, count ? K.counters : nullptr, stream);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    StreamSlot* sl = nullptr;
+    int rc = stream_slot(ctx, stream, 0, &sl);
+    if (rc) return rc;
+    H.queue = sl->d_queue;
+    HIP_OK(hipMemsetAsync(H.queue, 0, sizeof(unsigned), stream));
+    rc = vpt_int_hetero_launch(ctx->device, H, m, ctx->d_scene, stream);
+    if (rc) return rc;
+    return slot_done(sl, stream);
+}
+
 template <int EST, bool COUNT, int FB>
 static int launch_one(vpt_context* ctx, KParams K, hipStream_t stream)
 {
-    const DevScene* S = ctx->d_scene;
-    /* counting (vpt_count_work) needs only the totals: the one-lane-per-pixel kernel, which is
-     * also the A/B baseline (VPT_SIMPLE_KERNEL=1: samples in sequence per lane) */
-    if (COUNT || env_int("VPT_SIMPLE_KERNEL", 0)) {
-        dim3 grid((unsigned)((K.w + 15) / 16), (unsigned)((K.shard_rows + 15) / 16));
-        render_kernel_simple<EST, COUNT, FB><<<grid, dim3(256), 0, stream>>>(K, S);
-        HIP_OK(hipGetLastError());
+    if constexpr (EST == VPT_HETERO_FREE) {  /* its kernels live in vpt_hetero.hip */
+        return launch_hetero(ctx, K, COUNT, stream);
+    } else {
+        const DevScene* S = ctx->d_scene;
+        /* counting (vpt_count_work) needs only the totals: the one-lane-per-pixel kernel, which is
+         * also the A/B baseline (VPT_SIMPLE_KERNEL=1: samples in sequence per lane) */
+        if (COUNT || env_int("VPT_SIMPLE_KERNEL", 0)) {
+            dim3 grid((unsigned)((K.w + 15) / 16), (unsigned)((K.shard_rows + 15) / 16));
+            render_kernel_simple<EST, COUNT, FB><<<grid, dim3(256), 0, stream>>>(K, S);
+            HIP_OK(hipGetLastError());
+            return VPT_OK;
+        }
+        if constexpr (!COUNT && EST <= 5) return launch_pool<EST, FB>(ctx, K, stream);
+        if constexpr (EST >= 6) {  /* ray marching: one lane per pixel, samples summed in order */
+            dim3 grid((unsigned)((K.w + 15) / 16), (unsigned)((K.shard_rows + 15) / 16));
+            render_kernel_simple<EST, COUNT, FB><<<grid, dim3(256), 0, stream>>>(K, S);
+            HIP_OK(hipGetLastError());
+        }
         return VPT_OK;
     }
-    if constexpr (!COUNT && EST <= 5) return launch_pool<EST, FB>(ctx, K, stream);
-    if constexpr (EST >= 6) {  /* ray marching: one lane per pixel, samples summed in order */
-        dim3 grid((unsigned)((K.w + 15) / 16), (unsigned)((K.shard_rows + 15) / 16));
-        render_kernel_simple<EST, COUNT, FB><<<grid, dim3(256), 0, stream>>>(K, S);
-        HIP_OK(hipGetLastError());
-    }
-    return VPT_OK;
 }
 
 /* One pass of the pool kernel: the chunks [c0, c1) of layout `lay` for a set of 8x8 tiles -- every tile of
@@ -855,6 +835,7 @@ static int launch_render(vpt_context* ctx, KParams K, hipStream_t stream)
         VPT_LAUNCH_EST(7)
         VPT_LAUNCH_EST(8)
         VPT_LAUNCH_EST(9)
+        VPT_LAUNCH_EST(10)
     }
 #undef VPT_LAUNCH_EST
     return vpt_fail(VPT_E_INVALID, "unknown estimator %d", K.est);
@@ -943,6 +924,8 @@ void vpt_context_destroy(vpt_context* ctx)
     if (ctx->d_scene) (void)hipFree(ctx->d_scene);
     if (ctx->d_counters) (void)hipFree(ctx->d_counters);
     if (ctx->d_guard) (void)hipFree(ctx->d_guard);
+    if (ctx->d_grid) (void)hipFree(ctx->d_grid);
+    if (ctx->d_rho) (void)hipFree(ctx->d_rho);
     for (auto& sl : ctx->slots) {
         if (sl->done) (void)hipEventSynchronize(sl->done);
         if (sl->d_partials) (void)hipFree(sl->d_partials);
@@ -1000,6 +983,79 @@ int vpt_set_scene(vpt_context* ctx, const vpt_sphere* s, int n)
     HIP_OK(hipMemcpy(ctx->d_scene, &h, sizeof h, hipMemcpyHostToDevice));
     ctx->h_scene = h;
     ctx->has_scene = 1;
+    return VPT_OK;
+}
+
+int vpt_set_density_grid(vpt_context* ctx, const vpt_grid_desc* desc, const float* density)
+{
+    vpt_clear_error();
+    if (!ctx) return vpt_fail(VPT_E_INVALID, "vpt_set_density_grid: NULL context");
+    HIP_OK(hipSetDevice(ctx->device));
+    if (!desc) {  /* clear */
+        HIP_OK(hipDeviceSynchronize());
+        if (ctx->d_rho) (void)hipFree(ctx->d_rho);
+        ctx->d_rho = nullptr;
+        ctx->has_grid = 0;
+        return VPT_OK;
+    }
+    int rc = vpt_int_grid_check(desc, density, "vpt_set_density_grid");
+    if (rc) return rc;
+    const int32_t dims[3] = {desc->nx, desc->ny, desc->nz};
+    const size_t bytes = (size_t)desc->nx * (size_t)desc->ny * (size_t)desc->nz * sizeof(float);
+    float* d_rho = nullptr;
+    HIP_OK(hipMalloc((void**)&d_rho, bytes));
+    vpt_grid_view G;
+    vpt_grid_view_init(&G, dims, desc->lo, desc->hi, density, d_rho);  /* the majorant: scanned on the host */
+    hipError_t e = hipMemcpy(d_rho, density, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !ctx->d_grid) e = hipMalloc((void**)&ctx->d_grid, sizeof(vpt_grid_view));
+    if (e == hipSuccess) e = hipDeviceSynchronize();  /* nothing in flight reads the previous grid */
+    if (e == hipSuccess) e = hipMemcpy(ctx->d_grid, &G, sizeof G, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d_rho);
+        return vpt_fail(VPT_E_HIP, "vpt_set_density_grid: %s", hipGetErrorString(e));
+    }
+    if (ctx->d_rho) (void)hipFree(ctx->d_rho);
+    ctx->d_rho = d_rho;
+    ctx->has_grid = 1;
+    return VPT_OK;
+}
+
+int vpt_grid_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
+                   int n, double* tau, double* t_coll, uint64_t* states_out)
+{
+    vpt_clear_error();
+    if (!ctx || !rays || !tmax || !states || !tau || !t_coll || !states_out || n < 0)
+        return vpt_fail(VPT_E_INVALID, "vpt_grid_probe: bad arguments");
+    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "vpt_grid_probe: no density grid set (vpt_set_density_grid)");
+    if (n == 0) return VPT_OK;
+    HIP_OK(hipSetDevice(ctx->device));
+    vpt_ray* dr = nullptr;
+    uint64_t *ds = nullptr, *dso = nullptr;
+    double *dtm = nullptr, *dtau = nullptr, *dtc = nullptr;
+    const size_t nn = (size_t)n;
+    hipError_t e = hipMalloc((void**)&dr, sizeof(vpt_ray) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&ds, sizeof(uint64_t) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&dso, sizeof(uint64_t) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&dtm, sizeof(double) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&dtau, sizeof(double) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&dtc, sizeof(double) * nn);
+    if (e == hipSuccess) e = hipMemcpy(dr, rays, sizeof(vpt_ray) * nn, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ds, states, sizeof(uint64_t) * nn, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dtm, tmax, sizeof(double) * nn, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        vpt_int_grid_probe_launch(ctx->d_grid, sigma_t, dr, dtm, ds, n, dtau, dtc, dso);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(tau, dtau, sizeof(double) * nn, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(t_coll, dtc, sizeof(double) * nn, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(states_out, dso, sizeof(uint64_t) * nn, hipMemcpyDeviceToHost);
+    (void)hipFree(dr);
+    (void)hipFree(ds);
+    (void)hipFree(dso);
+    (void)hipFree(dtm);
+    (void)hipFree(dtau);
+    (void)hipFree(dtc);
+    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "vpt_grid_probe: %s", hipGetErrorString(e));
     return VPT_OK;
 }
 
@@ -1069,8 +1125,20 @@ int vpt_count_work(vpt_context* ctx, const vpt_params* p, uint64_t* tests, uint6
     return VPT_OK;
 }
 
+/* stats: vpt_debug_hetero_steps' two device counters (estimator 10), else NULL */
+static int trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* rays, const uint64_t* states, int n,
+                       double* out_rgb, uint64_t* out_states, unsigned long long* stats);
+
 int vpt_trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* rays, const uint64_t* states, int n,
                     double* out_rgb, uint64_t* out_states)
+{
+    return trace_batch(ctx, m, rays, states, n, out_rgb, out_states, nullptr);
+}
+
+}  // extern "C"
+
+static int trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* rays, const uint64_t* states, int n,
+                       double* out_rgb, uint64_t* out_states, unsigned long long* stats)
 {
     vpt_clear_error();
     if (!ctx || !rays || !states || !out_rgb || n < 0) return vpt_fail(VPT_E_INVALID, "vpt_trace_batch: bad arguments");
@@ -1102,6 +1170,7 @@ int vpt_trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* rays, 
         case 6: trace_batch_kernel<6><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         case 7: trace_batch_kernel<7><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         case 8: trace_batch_kernel<8><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
+        case VPT_HETERO_FREE: vpt_int_hetero_trace_launch(dr, ds, n, mm, ctx->d_scene, ctx->d_grid, dout, dso, stats); break;
         default: trace_batch_kernel<9><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         }
         e = hipGetLastError();
@@ -1115,6 +1184,8 @@ int vpt_trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* rays, 
     if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "vpt_trace_batch: %s", hipGetErrorString(e));
     return VPT_OK;
 }
+
+extern "C" {
 
 int vpt_punctual_volumetric(vpt_context* ctx, int idsource, const double* x, int n, double phase, double sigma_t,
                             double sigma_s, double* out_rgb)
@@ -1259,6 +1330,24 @@ extern "C" int vpt_debug_pool_stats(unsigned long long* out)
     if (!g_pool_stats || !out) return VPT_E_INVALID;
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemcpy(out, g_pool_stats, NSTATS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return VPT_OK;
+}
+
+/* measurement (not part of include/vpt.h; scripts/hetero_time.py): vpt_trace_batch for estimator 10 that also
+ * counts the delta-tracking calls of the batch and their tentative steps */
+extern "C" int vpt_debug_hetero_steps(vpt_context* ctx, const vpt_medium* m, const vpt_ray* rays, const uint64_t* states,
+                                      int n, double* out_rgb, uint64_t* tracks, uint64_t* steps)
+{
+    if (!ctx || !m || m->estimator != VPT_HETERO_FREE || !tracks || !steps)
+        return vpt_fail(VPT_E_INVALID, "vpt_debug_hetero_steps: bad arguments");
+    HIP_OK(hipSetDevice(ctx->device));
+    unsigned long long hc[2] = {0, 0};
+    HIP_OK(hipMemset(ctx->d_counters, 0, sizeof hc));
+    const int rc = trace_batch(ctx, m, rays, states, n, out_rgb, nullptr, ctx->d_counters);
+    if (rc) return rc;
+    HIP_OK(hipMemcpy(hc, ctx->d_counters, sizeof hc, hipMemcpyDeviceToHost));
+    *tracks = hc[0];
+    *steps = hc[1];
     return VPT_OK;
 }
 

@@ -219,6 +219,17 @@ int vpt_multi_set_scene(vpt_multi* m, const vpt_sphere* spheres, int n)
     return VPT_OK;
 }
 
+int vpt_multi_set_density_grid(vpt_multi* m, const vpt_grid_desc* desc, const float* density)
+{
+    vpt_clear_error();
+    if (!m) return vpt_fail(VPT_E_INVALID, "vpt_multi_set_density_grid: NULL handle");
+    for (int g = 0; g < m->n; ++g) {
+        int rc = vpt_set_density_grid(m->ctx[g], desc, density);
+        if (rc) return rc;
+    }
+    return VPT_OK;
+}
+
 int vpt_multi_render(vpt_multi* m, const vpt_params* p, void* h_out)
 {
     vpt_clear_error();

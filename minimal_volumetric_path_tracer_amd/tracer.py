@@ -23,7 +23,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (EXPLICIT_EQUIANGULAR, EXPLICIT_FREE, FB_F32, FB_F64, FREE_FLIGHT, IMPLICIT_FREE, MIS_EQUIANGULAR,
+from ._lib import (EXPLICIT_EQUIANGULAR, EXPLICIT_FREE, FB_F32, FB_F64, FREE_FLIGHT, HETERO_FREE, IMPLICIT_FREE, MIS_EQUIANGULAR,
                    RAY_DTYPE, RAY_MARCHING, RAY_MARCHING_EXPLICIT, RAY_MARCHING_GLOBAL, RAY_MARCHING_SA, SPHERE_DTYPE,
                    SURFACE_PT, check, lib)
 
@@ -31,7 +31,7 @@ ESTIMATORS = {"ff": FREE_FLIGHT, "free_flight": FREE_FLIGHT, "mis": MIS_EQUIANGU
               "explicit_free": EXPLICIT_FREE, "implicit_free": IMPLICIT_FREE, "explicit": EXPLICIT_EQUIANGULAR,
               "explicit_equiangular": EXPLICIT_EQUIANGULAR, "surface_pt": SURFACE_PT, "path_tracer": SURFACE_PT,
               "ray_marching": RAY_MARCHING, "ray_marching_sa": RAY_MARCHING_SA, "ray_marching_global": RAY_MARCHING_GLOBAL,
-              "ray_marching_explicit": RAY_MARCHING_EXPLICIT}
+              "ray_marching_explicit": RAY_MARCHING_EXPLICIT, "hetero": HETERO_FREE, "hetero_free": HETERO_FREE}
 
 
 def Sphere(r, p, c=(0, 0, 0), radiance=(0, 0, 0), material=0, eta=(0, 0, 0), kappa=(0, 0, 0), alpha=0.0) -> np.ndarray:
@@ -63,6 +63,38 @@ def Ray(o: Sequence[float], d: Sequence[float]) -> np.ndarray:
 def stream_state(seed: int, pixel_idx: int, sample: int) -> int:
     """erand48 start state of one camera sample (csrc/vpt_rng.h)."""
     return int(lib().vpt_stream_state(seed, pixel_idx, sample))
+
+
+def _grid_args(rho, lo, hi) -> tuple[_lib.vpt_grid_desc, np.ndarray]:
+    """(vpt_grid_desc, float32 voxels) of a density array of shape [nz, ny, nx] (x fastest) in the box [lo, hi]."""
+    r = np.ascontiguousarray(rho, dtype=np.float32)
+    if r.ndim != 3:
+        raise ValueError("rho must have shape [nz, ny, nx]")
+    d = _lib.vpt_grid_desc()
+    d.nz, d.ny, d.nx = r.shape
+    d.lo[:] = [float(v) for v in lo]
+    d.hi[:] = [float(v) for v in hi]
+    return d, r
+
+
+def _probe_args(rays, tmax, states):
+    r = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+    t = np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, dtype=np.float64), (len(r),)))
+    s = np.ascontiguousarray(states, dtype=np.uint64)
+    if len(r) != len(s):
+        raise ValueError("rays and states must have the same length")
+    return r, t, s, np.zeros(len(r)), np.zeros(len(r)), np.zeros(len(r), dtype=np.uint64)
+
+
+def grid_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, states):
+    """csrc/vpt_grid.h on the host (vpt_grid_probe_host, no GPU): per ray (unit direction) the optical depth of
+    the grid over t in [0, tmax], the delta-tracking result from `states` (-1: none, NaN: step cap) and the
+    erand48 states after the track."""
+    d, r = _grid_args(rho, lo, hi)
+    ry, t, s, tau, tc, so = _probe_args(rays, tmax, states)
+    check(lib().vpt_grid_probe_host(byref(d), r.ctypes.data, float(sigma_t), ry.ctypes.data, t.ctypes.data, s.ctypes.data,
+                                    len(ry), tau.ctypes.data, tc.ctypes.data, so.ctypes.data))
+    return tau, tc, so
 
 
 @dataclass
@@ -132,6 +164,23 @@ class Tracer:
         s = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE)
         check(lib().vpt_set_scene(self._ctx, s.ctypes.data, len(s)))
         self.spheres = s
+
+    # ---- heterogeneous medium (estimator "hetero") ----
+    def set_density_grid(self, rho, lo, hi) -> None:
+        """The density grid of estimator "hetero": rho of shape [nz, ny, nx] (float32, finite, >= 0) in the world
+        box [lo, hi], zero outside; sigma_a / sigma_s are then per unit density.  Kept across set_scene."""
+        d, r = _grid_args(rho, lo, hi)
+        check(lib().vpt_set_density_grid(self._ctx, byref(d), r.ctypes.data))
+
+    def clear_density_grid(self) -> None:
+        check(lib().vpt_set_density_grid(self._ctx, None, None))
+
+    def grid_probe(self, sigma_t: float, rays, tmax, states):
+        """grid_probe_host's quantities for the tracer's grid, computed on the GPU (vpt_grid_probe)."""
+        ry, t, s, tau, tc, so = _probe_args(rays, tmax, states)
+        check(lib().vpt_grid_probe(self._ctx, float(sigma_t), ry.ctypes.data, t.ctypes.data, s.ctypes.data, len(ry),
+                                   tau.ctypes.data, tc.ctypes.data, so.ctypes.data))
+        return tau, tc, so
 
     # ---- main()'s pixel loop (src/rt.cpp:767-805) ----
     def render(self, cfg: Optional[RenderConfig] = None, **kw) -> np.ndarray:
@@ -367,6 +416,14 @@ class MultiTracer:
         s = np.ascontiguousarray(default_scene() if spheres is None else spheres, dtype=SPHERE_DTYPE)
         check(lib().vpt_multi_set_scene(self._m, s.ctypes.data, len(s)))
         self.spheres = s
+
+    def set_density_grid(self, rho, lo, hi) -> None:
+        """Tracer.set_density_grid on every rank's context."""
+        d, r = _grid_args(rho, lo, hi)
+        check(lib().vpt_multi_set_density_grid(self._m, byref(d), r.ctypes.data))
+
+    def clear_density_grid(self) -> None:
+        check(lib().vpt_multi_set_density_grid(self._m, None, None))
 
     def render(self, cfg: Optional[RenderConfig] = None, **kw) -> np.ndarray:
         """(height, width, 3), file order; cfg.band_rows (when it cuts the image) is the band size."""
