@@ -164,6 +164,14 @@ typedef struct vpt_grid_desc {
  * must not change while a render is in flight.  A dimension < 1, hi <= lo, a NaN, negative or infinite density
  * or more than 2^27 voxels -> VPT_E_INVALID (the previous grid stays). */
 int vpt_set_density_grid(vpt_context* ctx, const vpt_grid_desc* desc, const float* density);
+/* Local majorants for the delta tracking of estimator VPT_HETERO_FREE (csrc/vpt_grid.h): the voxels are grouped
+ * into cubic super-voxels of `block` voxels per axis, each with the maximum density of its voxels, and a track
+ * steps with the majorant of the super-voxel it is in (empty ones are skipped).  Fewer null collisions on sparse
+ * fields; the same estimator in distribution, other draws.  block 0 (the default) turns it off: the single
+ * global majorant, every value as before.  block >= max(nx, ny, nz) is one super-voxel and reproduces block 0
+ * bit for bit; block < 0 -> VPT_E_INVALID.  The setting belongs to the context: it is applied to the current
+ * grid at once (synchronous), to every later vpt_set_density_grid, and survives a clear. */
+int vpt_set_grid_majorant_block(vpt_context* ctx, int block);
 
 /* Renders into a DEVICE buffer on `stream` (a hipStream_t, NULL = default stream); returns
  * after enqueueing.  d_out: vpt_shard_rows(p) * width * 3 elements of fb_format, the
@@ -189,6 +197,8 @@ int vpt_multi_create(int n_gpus, vpt_multi** out);
 int vpt_multi_set_scene(vpt_multi* m, const vpt_sphere* spheres, int n);
 /* vpt_set_density_grid on every context of the handle */
 int vpt_multi_set_density_grid(vpt_multi* m, const vpt_grid_desc* desc, const float* density);
+/* vpt_set_grid_majorant_block on every context of the handle */
+int vpt_multi_set_grid_majorant_block(vpt_multi* m, int block);
 int vpt_multi_render(vpt_multi* m, const vpt_params* p, void* h_out);
 void vpt_multi_destroy(vpt_multi* m);
 /* one-shot: create, set the scene, render, destroy */
@@ -311,6 +321,15 @@ int vpt_grid_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const 
 int vpt_grid_probe_host(const vpt_grid_desc* desc, const float* density, double sigma_t, const vpt_ray* rays,
                         const double* tmax, const uint64_t* states, int n, double* tau, double* t_coll,
                         uint64_t* states_out);
+/* The two probes above always track with the global majorant.  vpt_grid_probe_lm honours the context's
+ * vpt_set_grid_majorant_block setting and vpt_grid_probe_host_lm takes the block size (0: the global majorant,
+ * < 0 -> VPT_E_INVALID); steps (may be NULL): per ray the tentative steps of the track, one per draw of a free
+ * path (csrc/vpt_grid.h). */
+int vpt_grid_probe_lm(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
+                      int n, double* tau, double* t_coll, uint64_t* states_out, uint32_t* steps);
+int vpt_grid_probe_host_lm(const vpt_grid_desc* desc, const float* density, int block, double sigma_t, const vpt_ray* rays,
+                           const double* tmax, const uint64_t* states, int n, double* tau, double* t_coll,
+                           uint64_t* states_out, uint32_t* steps);
 
 /* PPM writer of main() (src/rt.cpp:812-820): clamp to [0,1] (src/rt.cpp:803), gamma 1/2.2,
  * int(v*255 + .5) (include/mathUtilities.h:43-45), "P3\n%d %d\n255\n" then "%d %d %d " per

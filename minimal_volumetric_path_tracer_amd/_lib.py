@@ -103,11 +103,13 @@ PROTOTYPES = [
     ("vpt_context_destroy", None, [c_void_p]),
     ("vpt_set_scene", c_int, [c_void_p, c_void_p, c_int]),
     ("vpt_set_density_grid", c_int, [c_void_p, POINTER(vpt_grid_desc), c_void_p]),
+    ("vpt_set_grid_majorant_block", c_int, [c_void_p, c_int]),
     ("vpt_render_device", c_int, [c_void_p, POINTER(vpt_params), c_void_p, c_void_p]),
     ("vpt_render", c_int, [c_void_p, POINTER(vpt_params), c_void_p]),
     ("vpt_multi_create", c_int, [c_int, POINTER(c_void_p)]),
     ("vpt_multi_set_scene", c_int, [c_void_p, c_void_p, c_int]),
     ("vpt_multi_set_density_grid", c_int, [c_void_p, POINTER(vpt_grid_desc), c_void_p]),
+    ("vpt_multi_set_grid_majorant_block", c_int, [c_void_p, c_int]),
     ("vpt_multi_render", c_int, [c_void_p, POINTER(vpt_params), c_void_p]),
     ("vpt_multi_destroy", None, [c_void_p]),
     ("vpt_render_multi", c_int, [c_void_p, c_int, POINTER(vpt_params), c_int, c_void_p]),
@@ -133,6 +135,10 @@ PROTOTYPES = [
     ("vpt_grid_probe", c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     ("vpt_grid_probe_host", c_int, [POINTER(vpt_grid_desc), c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int,
                                     c_void_p, c_void_p, c_void_p]),
+    ("vpt_grid_probe_lm", c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
+    ("vpt_grid_probe_host_lm", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p,
+                                       c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vpt_write_ppm", c_int, [c_char_p, c_void_p, c_int, c_int, c_int]),
     ("vpt_encode_ppm", c_int64, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64]),
     ("vpt_last_error", c_char_p, []),

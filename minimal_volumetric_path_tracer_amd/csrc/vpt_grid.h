@@ -27,6 +27,31 @@
  * no-draw rule at the majorant is deliberate: with rho == 1 everywhere and the origin inside the box the
  * first step is 0 + (-log(1 - xi) / (1 sigma_t)), the reference's freeFlightSample bit for bit from the same
  * single draw, so estimator 10 on a uniform grid walks estimator 0's paths draw for draw.
+ *
+ * Local majorants (opt-in: vpt_grid_view.block = B >= 1, 0 = none; vpt_grid_track_lm).  The voxels are grouped
+ * into cubic super-voxels of B voxels per axis, nb[a] = ceil(n[a] / B) of them (the last of an axis may be
+ * partial); maj[bz][by][bx] is the float32 maximum of rho over the block, built on the host next to the
+ * rho_max scan and widened to double on load.  Super-voxel planes are voxel planes, formed with vpt_grid_tau's
+ * expression lo + (double)k * cell, k = ib * B, so the two walkers never disagree on a plane; the two
+ * outermost planes of an axis are lo and hi themselves, so that the exit distance of a single super-voxel is
+ * the slab test's t1 bit for bit.  The track: "none" with no draw when rho_max == 0 or the slab test leaves no
+ * interval; else from t = t0, in the super-voxel of the entry point, each tentative step:
+ *   1. draw xi; rem = -log(1 - xi), the optical depth still to cover             one draw, one step counted
+ *   2. walk the super-voxels by DDA; in one with majorant mu and exit plane at te (only where te > t):
+ *        mu == 0: skipped -- no draw, no density fetch, rem untouched
+ *        else s = mu * sigma_t, tc = t + (rem / s); tc < te: a tentative collision at tc (3.)
+ *        else rem = rem - s * (te - t)
+ *      then t = te; none if te >= t1 or te > tmax, or when the walk leaves the grid; crossing takes no draw
+ *   3. none if tc > tmax or tc >= t1; rho = density(o + d tc); rho >= mu: a real collision, NO draw; else draw
+ *      xi'; xi' * mu < rho: a real collision; else t = tc and the next tentative step (1.) goes on in the same
+ *      super-voxel
+ * capped at 2^22 tentative steps (NaN) and at nb[0] + nb[1] + nb[2] + 4 crossings per tentative step (none).
+ * Choices the description above leaves open, made so that one super-voxel (B >= max(n)) is the global track
+ * bit for bit -- results, step counts, end states: a step is counted where xi is drawn (the global track
+ * counts the step that ends in "none" too), so `steps` is the number of xi draws; s is formed as mu * sigma_t
+ * and the candidate as t + (rem / s), the global track's t + (-log(1 - xi) / (rho_max * sigma_t)); a NaN
+ * candidate fails tc < te and ends at the boundary test as "none".  With B = 1 the majorant is the voxel's own
+ * density, no collision is null, and a track takes exactly one draw: analytic inversion of the optical depth.
  */
 #ifndef VPT_GRID_H
 #define VPT_GRID_H
@@ -62,6 +87,10 @@ typedef struct vpt_grid_view {
     double cell[3];        /* (hi - lo) / n */
     double rho_max;
     const float* rho;
+    /* local majorants (header comment); block == 0: none, maj is not read */
+    const float* maj;      /* nb[2] x nb[1] x nb[0] block maxima, x fastest */
+    int32_t nb[3];
+    int32_t block;
 } vpt_grid_view;
 
 /* 0 when valid, else 1 dimension < 1 or too many voxels, 2 box not finite or hi <= lo, 3 a density that is
@@ -99,6 +128,41 @@ static inline void vpt_grid_view_init(vpt_grid_view* G, const int32_t n[3], cons
     G->pad_ = 0;
     G->rho_max = (double)mx;
     G->rho = rho;
+    G->maj = 0;
+    G->nb[0] = G->nb[1] = G->nb[2] = 0;
+    G->block = 0;
+}
+
+/* host: the super-voxel counts of block size B >= 1 and the block maxima of `density` into out (nb[2] x nb[1] x
+ * nb[0] floats, x fastest) */
+static inline void vpt_grid_majorant_counts(const int32_t n[3], int32_t B, int32_t nb[3])
+{
+    for (int a = 0; a < 3; ++a) nb[a] = (n[a] - 1) / B + 1;
+}
+
+static inline void vpt_grid_majorant_build(const int32_t n[3], int32_t B, const float* density, float* out)
+{
+    int32_t nb[3];
+    vpt_grid_majorant_counts(n, B, nb);
+    const int64_t nbv = (int64_t)nb[0] * nb[1] * nb[2];
+    for (int64_t i = 0; i < nbv; ++i) out[i] = 0.0f;
+    for (int32_t z = 0; z < n[2]; ++z)
+        for (int32_t y = 0; y < n[1]; ++y) {
+            const float* row = density + ((int64_t)z * n[1] + y) * n[0];
+            float* orow = out + ((int64_t)(z / B) * nb[1] + y / B) * nb[0];
+            for (int32_t x = 0; x < n[0]; ++x)
+                if (row[x] > orow[x / B]) orow[x / B] = row[x];
+        }
+}
+
+/* host: turns the majorant grid of an initialised view on (B >= 1, `maj` the pointer the walkers will read) or
+ * off (B == 0) */
+static inline void vpt_grid_view_set_majorant(vpt_grid_view* G, int32_t B, const float* maj)
+{
+    G->block = B;
+    G->maj = B ? maj : 0;
+    if (B) vpt_grid_majorant_counts(G->n, B, G->nb);
+    else G->nb[0] = G->nb[1] = G->nb[2] = 0;
 }
 
 VPT_GR int vpt_grid_axis_index(const vpt_grid_view* G, int a, double p)
@@ -199,6 +263,71 @@ VPT_GR double vpt_grid_track(const vpt_grid_view* G, const double o[3], const do
         const double rho = vpt_grid_density(G, o[0] + d[0] * t, o[1] + d[1] * t, o[2] + d[2] * t);
         if (rho >= G->rho_max) return t;
         if (vpt_erand48(X) * G->rho_max < rho) return t;
+    }
+    return (double)NAN;
+}
+
+/* the plane below super-voxel kb of axis a (kb == nb[a]: the plane above the last one); header comment */
+VPT_GR double vpt_grid_block_plane(const vpt_grid_view* G, int a, int kb)
+{
+    if (kb <= 0) return G->lo[a];
+    if (kb >= G->nb[a]) return G->hi[a];
+    return G->lo[a] + (double)(kb * G->block) * G->cell[a];
+}
+
+/* delta tracking with local majorants (header comment; G->block >= 1): vpt_grid_track's arguments and
+ * results */
+VPT_GR double vpt_grid_track_lm(const vpt_grid_view* G, const double o[3], const double d[3], double tmax,
+                                double sigma_t, uint64_t* X, uint32_t* steps)
+{
+    double t0, t1;
+    if (steps) *steps = 0;
+    if (!(G->rho_max > 0.0)) return -1.0;
+    if (!vpt_grid_slab(G, o, d, &t0, &t1)) return -1.0;
+    int i[3], step[3];
+    double tn[3], inv[3];
+    for (int a = 0; a < 3; ++a) {
+        i[a] = vpt_grid_axis_index(G, a, o[a] + d[a] * t0) / G->block;
+        step[a] = d[a] > 0.0 ? 1 : (d[a] < 0.0 ? -1 : 0);
+        inv[a] = step[a] ? 1.0 / d[a] : 0.0;
+        tn[a] = step[a] ? (vpt_grid_block_plane(G, a, i[a] + (step[a] > 0)) - o[a]) * inv[a] : VPT_GRID_BIG;
+    }
+    const int max_cross = G->nb[0] + G->nb[1] + G->nb[2] + 4;
+    double t = t0;
+    /* the current super-voxel: its exit axis and plane and its majorant, kept across null collisions (one
+     * majorant fetch per super-voxel entered, none per tentative step) */
+    int a = tn[0] <= tn[1] ? (tn[0] <= tn[2] ? 0 : 2) : (tn[1] <= tn[2] ? 1 : 2);
+    double te = tn[a];
+    double mu = te > t ? (double)G->maj[((int64_t)i[2] * G->nb[1] + i[1]) * G->nb[0] + i[0]] : 0.0;
+    for (int k = 0; k < VPT_GRID_MAX_TRACK_STEPS; ++k) {
+        double rem = -VPT_GRID_LOG(1 - vpt_erand48(X));
+        if (steps) *steps = (uint32_t)(k + 1);
+        double tc = 0.0;
+        int c = 0;
+        for (; c < max_cross; ++c) {
+            if (te > t) {  /* (a super-voxel the rounding left without length is passed over) */
+                if (mu > 0.0) {
+                    const double s = mu * sigma_t;
+                    tc = t + (rem / s);
+                    if (tc < te) break;  /* a tentative collision */
+                    rem = rem - s * (te - t);
+                }
+                t = te;
+            }
+            if (!(te < t1) || te > tmax) return -1.0;
+            i[a] += step[a];
+            if (i[a] < 0 || i[a] >= G->nb[a]) return -1.0;
+            tn[a] = (vpt_grid_block_plane(G, a, i[a] + (step[a] > 0)) - o[a]) * inv[a];
+            a = tn[0] <= tn[1] ? (tn[0] <= tn[2] ? 0 : 2) : (tn[1] <= tn[2] ? 1 : 2);
+            te = tn[a];
+            mu = te > t ? (double)G->maj[((int64_t)i[2] * G->nb[1] + i[1]) * G->nb[0] + i[0]] : 0.0;
+        }
+        if (c == max_cross) return -1.0;
+        if (tc > tmax || tc >= t1) return -1.0;
+        const double rho = vpt_grid_density(G, o[0] + d[0] * tc, o[1] + d[1] * tc, o[2] + d[2] * tc);
+        if (rho >= mu) return tc;
+        if (vpt_erand48(X) * mu < rho) return tc;
+        t = tc;
     }
     return (double)NAN;
 }

@@ -12,9 +12,15 @@
  * every path this estimator walks estimator 0's paths with the same draws and differs only in the rounding
  * of tau (tests/test_gpu_hetero.py).  The steps are the generic (MK = -1, LT = -1) statements of
  * decide / surface_event / medium_event<0>: the tuned instantiations of the pool kernel are not touched.
+ * Local majorants (vpt_grid.h, vpt_set_grid_majorant_block): where the grid has a majorant grid the track is
+ * vpt_grid_track_lm, else vpt_grid_track.  The choice is the template parameter LM of hetero_decide,
+ * trace_hetero and every kernel of estimator 10, made on the host at launch from the context's view, so the
+ * LM = false instantiations are the kernels as they were before local majorants existed.
  */
 #ifndef VPT_HETERO_H
 #define VPT_HETERO_H
+
+#include <stddef.h>
 
 #include "vpt_device.h"
 
@@ -28,6 +34,17 @@ namespace vpt {
 struct GridTr {
     static constexpr bool hom = false;
     vpt_grid_view G;
+    /* the context's view from device memory.  Without local majorants only the fields the global-majorant
+     * walkers read are copied (everything before `maj`): block, nb and maj stay unset and nothing reads them, so
+     * the LM = false kernels load what they loaded before local majorants existed */
+    template <bool LM>
+    __device__ __forceinline__ static GridTr load(const vpt_grid_view* __restrict__ g)
+    {
+        GridTr tp;
+        if (LM) tp.G = *g;
+        else __builtin_memcpy(&tp.G, g, offsetof(vpt_grid_view, maj));
+        return tp;
+    }
     __device__ __forceinline__ double along(dv3 o, dv3 d, double dist, double sigma_t) const
     {
         const double oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
@@ -49,7 +66,7 @@ struct HeteroStats {
 };
 
 /* decide<0> with delta tracking in freeFlightSample's place */
-template <bool COUNT>
+template <bool COUNT, bool LM = false>
 VPT_DEV int hetero_decide(const DevScene* __restrict__ S, const GridTr& tp, Sampler<COUNT>& smp, Path& p, Event& e,
                           const Medium& m, HeteroStats* hs = nullptr)
 {
@@ -65,7 +82,8 @@ VPT_DEV int hetero_decide(const DevScene* __restrict__ S, const GridTr& tp, Samp
     e.src = emit_pick(S, (int)(smp.next() * count), count);
     const double oo[3] = {p.o.x, p.o.y, p.o.z}, dd[3] = {p.d.x, p.d.y, p.d.z};
     uint32_t nsteps = 0;
-    const double tc = vpt_grid_track(&tp.G, oo, dd, t, sigma_t, &smp.X, hs ? &nsteps : (uint32_t*)nullptr);
+    const double tc = LM ? vpt_grid_track_lm(&tp.G, oo, dd, t, sigma_t, &smp.X, hs ? &nsteps : (uint32_t*)nullptr)
+                        : vpt_grid_track(&tp.G, oo, dd, t, sigma_t, &smp.X, hs ? &nsteps : (uint32_t*)nullptr);
     if (hs) {
         hs->tracks += 1;
         hs->steps += nsteps;
@@ -129,7 +147,7 @@ VPT_DEV void hetero_medium(const DevScene* __restrict__ S, const GridTr& tp, Sam
 }
 
 /* one camera sample, sequentially (vpt_trace_batch, render_kernel_simple<10>) */
-template <bool COUNT>
+template <bool COUNT, bool LM = false>
 __device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridTr& tp, Sampler<COUNT>& smp, dv3 o, dv3 d,
                                    const Medium& m, HeteroStats* hs = nullptr)
 {
@@ -142,7 +160,7 @@ __device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridTr&
     Event e;
     e.pdf = 0;
     while (continue_path(smp, p, m)) {
-        const int ev = hetero_decide(S, tp, smp, p, e, m, hs);
+        const int ev = hetero_decide<COUNT, LM>(S, tp, smp, p, e, m, hs);
         if (ev == EV_END) break;
         if (ev == EV_SURF) hetero_surface(S, tp, smp, p, e, m);
         else hetero_medium(S, tp, smp, p, e, m);
@@ -165,16 +183,21 @@ struct HeteroParams {
 }  // namespace vpt
 
 /* vpt_hetero.hip: the persistent-wave render kernel of estimator 10, enqueued on `stream` (the caller owns
- * the queue word and has zeroed it in stream order) */
-int vpt_int_hetero_launch(int device, const vpt::HeteroParams& H, const vpt::Medium& m, const DevScene* S, void* stream);
+ * the queue word and has zeroed it in stream order); lm: the grid has a majorant grid (the kernel's LM
+ * instantiation) */
+int vpt_int_hetero_launch(int device, const vpt::HeteroParams& H, const vpt::Medium& m, const DevScene* S, bool lm,
+                          void* stream);
 /* render_kernel_simple<10> for the same render (counters: vpt_count_work's device counters, else NULL) */
-int vpt_int_hetero_simple_launch(const vpt::HeteroParams& H, const vpt::Medium& m, const DevScene* S,
+int vpt_int_hetero_simple_launch(const vpt::HeteroParams& H, const vpt::Medium& m, const DevScene* S, bool lm,
                                  unsigned long long* counters, void* stream);
 /* the per-sample call and the grid probe on device arrays, default stream (the caller reads hipGetLastError);
- * stats: vpt_debug_hetero_steps' two counters, else NULL */
+ * lm: the grid behind `grid` has a majorant grid; stats: vpt_debug_hetero_steps' two counters, else NULL; steps: the
+ * probe's per-ray tentative steps, else NULL */
 void vpt_int_hetero_trace_launch(const vpt_ray* rays, const uint64_t* states, int n, const vpt::Medium& m, const DevScene* S,
-                                 const vpt_grid_view* grid, double* out, uint64_t* out_states, unsigned long long* stats);
-void vpt_int_grid_probe_launch(const vpt_grid_view* grid, double sigma_t, const vpt_ray* rays, const double* tmax,
-                               const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out);
+                                 const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states,
+                                 unsigned long long* stats);
+void vpt_int_grid_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays, const double* tmax,
+                               const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out,
+                               uint32_t* steps);
 
 #endif

@@ -28,10 +28,15 @@
 #define VPT_HETERO_LDS 1
 #endif
 #define VPT_HETERO_LDS_BYTES 65536
+/* with local majorants: the majorant grid is staged in what the density left of the LDS budget -- all of it
+ * where the density does not fit (DESIGN.md section 4 has the timing that decided the default) */
+#ifndef VPT_HETERO_LDS_MAJ
+#define VPT_HETERO_LDS_MAJ 1
+#endif
 
 namespace vpt {
 
-template <bool COUNT, int FB>
+template <bool COUNT, int FB, bool LM>
 __global__ __launch_bounds__(256, 2) void hetero_kernel(HeteroParams P, Medium m, const DevScene* __restrict__ S)
 {
     const int lane = threadIdx.x & 63;
@@ -40,8 +45,7 @@ __global__ __launch_bounds__(256, 2) void hetero_kernel(HeteroParams P, Medium m
     const dv3 cd = mk(P.d[0], P.d[1], P.d[2]);
     const dv3 cx = mk(P.cx[0], P.cx[1], P.cx[2]), cy = mk(P.cy[0], P.cy[1], P.cy[2]);
     const unsigned npix = (unsigned)P.tiles_x * (unsigned)P.tiles_y * 64u;
-    GridTr tp;
-    tp.G = *P.grid;
+    GridTr tp = GridTr::load<LM>(P.grid);
 #if VPT_HETERO_LDS
     __shared__ float lds_rho[VPT_HETERO_LDS_BYTES / sizeof(float)];
     {
@@ -51,6 +55,18 @@ __global__ __launch_bounds__(256, 2) void hetero_kernel(HeteroParams P, Medium m
             __syncthreads();
             tp.G.rho = lds_rho;
         }
+#if VPT_HETERO_LDS_MAJ
+        if (LM) {  /* the majorant grid goes into what the density left of the budget */
+            const int64_t cap = (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float));
+            const int64_t used = nv <= cap ? nv : 0;
+            const int64_t nbv = (int64_t)tp.G.nb[0] * tp.G.nb[1] * tp.G.nb[2];
+            if (nbv <= cap - used) {  /* workgroup-uniform */
+                for (int k = threadIdx.x; k < (int)nbv; k += blockDim.x) lds_rho[used + k] = tp.G.maj[k];
+                __syncthreads();
+                tp.G.maj = lds_rho + used;
+            }
+        }
+#endif
     }
 #endif
 
@@ -139,7 +155,7 @@ __global__ __launch_bounds__(256, 2) void hetero_kernel(HeteroParams P, Medium m
                     in_path = false;
                     continue;
                 }
-                const int ev = hetero_decide(S, tp, smp, p, e, m);
+                const int ev = hetero_decide<COUNT, LM>(S, tp, smp, p, e, m);
                 if (ev == EV_END) {
                     acc = add(p.L, acc);
                     in_path = false;
@@ -175,6 +191,7 @@ using namespace vpt;
 namespace {
 
 /* estimator 10's per-sample call (vpt_hetero.h) */
+template <bool LM>
 __global__ __launch_bounds__(256) void trace_batch_hetero_kernel(const vpt_ray* __restrict__ rays,
                                                                  const uint64_t* __restrict__ states, int n, Medium m,
                                                                  const DevScene* __restrict__ S,
@@ -187,7 +204,7 @@ __global__ __launch_bounds__(256) void trace_batch_hetero_kernel(const vpt_ray* 
     smp.X = states[i] & 0xFFFFFFFFFFFFull;
     smp.g = m.g;
     HeteroStats hs{0, 0};
-    dv3 L = trace_hetero<false>(S, GridTr{*grid}, smp, ld3(rays[i].o), ld3(rays[i].d), m, stats ? &hs : nullptr);
+    dv3 L = trace_hetero<false, LM>(S, GridTr::load<LM>(grid), smp, ld3(rays[i].o), ld3(rays[i].d), m, stats ? &hs : nullptr);
     if (stats) {  /* vpt_debug_hetero_steps */
         atomicAdd(&stats[0], hs.tracks);
         atomicAdd(&stats[1], hs.steps);
@@ -198,11 +215,12 @@ __global__ __launch_bounds__(256) void trace_batch_hetero_kernel(const vpt_ray* 
     out_states[i] = smp.X;
 }
 
-/* the density grid's walkers (vpt_grid.h), one ray per lane (vpt_grid_probe) */
+/* the density grid's walkers (vpt_grid.h), one ray per lane (vpt_grid_probe, vpt_grid_probe_lm) */
+template <bool LM>
 __global__ __launch_bounds__(256) void grid_probe_kernel(const vpt_grid_view* __restrict__ grid, double sigma_t,
                                                          const vpt_ray* __restrict__ rays, const double* __restrict__ tmax,
                                                          const uint64_t* __restrict__ states, int n, double* tau,
-                                                         double* t_coll, uint64_t* states_out)
+                                                         double* t_coll, uint64_t* states_out, uint32_t* steps)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -210,37 +228,45 @@ __global__ __launch_bounds__(256) void grid_probe_kernel(const vpt_grid_view* __
     const double o[3] = {rays[i].o[0], rays[i].o[1], rays[i].o[2]}, d[3] = {rays[i].d[0], rays[i].d[1], rays[i].d[2]};
     uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
     tau[i] = vpt_grid_tau(&G, o, d, tmax[i]);
-    t_coll[i] = vpt_grid_track(&G, o, d, tmax[i], sigma_t, &X, (uint32_t*)nullptr);
+    uint32_t ns = 0;
+    t_coll[i] = LM ? vpt_grid_track_lm(&G, o, d, tmax[i], sigma_t, &X, &ns) : vpt_grid_track(&G, o, d, tmax[i], sigma_t, &X, &ns);
     states_out[i] = X;
+    if (steps) steps[i] = ns;
 }
 
 }  // namespace
 
 void vpt_int_hetero_trace_launch(const vpt_ray* rays, const uint64_t* states, int n, const Medium& m, const DevScene* S,
-                                 const vpt_grid_view* grid, double* out, uint64_t* out_states, unsigned long long* stats)
+                                 const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states,
+                                 unsigned long long* stats)
 {
-    trace_batch_hetero_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(rays, states, n, m, S, grid, out, out_states, stats);
+    const dim3 g((unsigned)((n + 255) / 256)), b(256);
+    if (lm) trace_batch_hetero_kernel<true><<<g, b>>>(rays, states, n, m, S, grid, out, out_states, stats);
+    else trace_batch_hetero_kernel<false><<<g, b>>>(rays, states, n, m, S, grid, out, out_states, stats);
 }
 
-void vpt_int_grid_probe_launch(const vpt_grid_view* grid, double sigma_t, const vpt_ray* rays, const double* tmax,
-                               const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out)
+void vpt_int_grid_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays, const double* tmax,
+                               const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out,
+                               uint32_t* steps)
 {
-    grid_probe_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(grid, sigma_t, rays, tmax, states, n, tau, t_coll, states_out);
+    const dim3 g((unsigned)((n + 255) / 256)), b(256);
+    if (lm) grid_probe_kernel<true><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, steps);
+    else grid_probe_kernel<false><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, steps);
 }
 
 /* render_kernel_simple<10> (vpt_render_simple.h): counting mode (counters != NULL) and VPT_SIMPLE_KERNEL=1 */
-template <bool COUNT, int FB>
+template <bool COUNT, int FB, bool LM>
 static int launch_simple(const KParams& K, const DevScene* S, hipStream_t stream)
 {
     dim3 grid((unsigned)((K.w + 15) / 16), (unsigned)((K.shard_rows + 15) / 16));
-    render_kernel_simple<VPT_HETERO_FREE, COUNT, FB><<<grid, dim3(256), 0, stream>>>(K, S);
+    render_kernel_simple<VPT_HETERO_FREE, COUNT, FB, LM><<<grid, dim3(256), 0, stream>>>(K, S);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "render_kernel_simple<10> launch: %s", hipGetErrorString(e));
     return VPT_OK;
 }
 
-int vpt_int_hetero_simple_launch(const HeteroParams& H, const Medium& m, const DevScene* S, unsigned long long* counters,
-                                 void* stream)
+int vpt_int_hetero_simple_launch(const HeteroParams& H, const Medium& m, const DevScene* S, bool lm,
+                                 unsigned long long* counters, void* stream)
 {
     KParams K;
     memset(&K, 0, sizeof K);
@@ -272,15 +298,20 @@ int vpt_int_hetero_simple_launch(const HeteroParams& H, const Medium& m, const D
     K.tiles_y = H.tiles_y;
     K.grid = H.grid;
     hipStream_t st = (hipStream_t)stream;
-    if (counters) return H.fb == VPT_FB_F32 ? launch_simple<true, VPT_FB_F32>(K, S, st) : launch_simple<true, VPT_FB_F64>(K, S, st);
-    return H.fb == VPT_FB_F32 ? launch_simple<false, VPT_FB_F32>(K, S, st) : launch_simple<false, VPT_FB_F64>(K, S, st);
+    const bool f32 = H.fb == VPT_FB_F32;
+    if (lm) {
+        if (counters) return f32 ? launch_simple<true, VPT_FB_F32, true>(K, S, st) : launch_simple<true, VPT_FB_F64, true>(K, S, st);
+        return f32 ? launch_simple<false, VPT_FB_F32, true>(K, S, st) : launch_simple<false, VPT_FB_F64, true>(K, S, st);
+    }
+    if (counters) return f32 ? launch_simple<true, VPT_FB_F32, false>(K, S, st) : launch_simple<true, VPT_FB_F64, false>(K, S, st);
+    return f32 ? launch_simple<false, VPT_FB_F32, false>(K, S, st) : launch_simple<false, VPT_FB_F64, false>(K, S, st);
 }
 
-template <int FB>
+template <int FB, bool LM>
 static int launch(int device, const HeteroParams& H, const Medium& m, const DevScene* S, hipStream_t stream)
 {
     int per_cu = 0, cus = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hetero_kernel<false, FB>, 256, 0);
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hetero_kernel<false, FB, LM>, 256, 0);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
     if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_kernel: %s", hipGetErrorString(e));
     int blocks = (per_cu < 1 ? 1 : per_cu) * cus;
@@ -288,14 +319,15 @@ static int launch(int device, const HeteroParams& H, const Medium& m, const DevS
     const int need = (tiles + 3) / 4;  /* 4 waves per block, one tile per wave to start */
     if (blocks > need) blocks = need;
     if (blocks < 1) blocks = 1;
-    hetero_kernel<false, FB><<<dim3((unsigned)blocks), dim3(256), 0, stream>>>(H, m, S);
+    hetero_kernel<false, FB, LM><<<dim3((unsigned)blocks), dim3(256), 0, stream>>>(H, m, S);
     e = hipGetLastError();
     if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_kernel launch: %s", hipGetErrorString(e));
     return VPT_OK;
 }
 
-int vpt_int_hetero_launch(int device, const HeteroParams& H, const Medium& m, const DevScene* S, void* stream)
+int vpt_int_hetero_launch(int device, const HeteroParams& H, const Medium& m, const DevScene* S, bool lm, void* stream)
 {
-    if (H.fb == VPT_FB_F32) return launch<VPT_FB_F32>(device, H, m, S, (hipStream_t)stream);
-    return launch<VPT_FB_F64>(device, H, m, S, (hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (lm) return H.fb == VPT_FB_F32 ? launch<VPT_FB_F32, true>(device, H, m, S, st) : launch<VPT_FB_F64, true>(device, H, m, S, st);
+    return H.fb == VPT_FB_F32 ? launch<VPT_FB_F32, false>(device, H, m, S, st) : launch<VPT_FB_F64, false>(device, H, m, S, st);
 }

@@ -376,6 +376,11 @@ struct vpt_context {
     vpt_grid_view* d_grid = nullptr;
     float* d_rho = nullptr;
     int has_grid = 0;
+    /* local majorants (vpt_set_grid_majorant_block): the context's block size (0: off), the current grid's
+     * block maxima on the device and the host's copy of its view */
+    int maj_block = 0;
+    float* d_maj = nullptr;
+    vpt_grid_view h_grid = {};
 };
 
 /* The stream's slot, created on first use (or taken over from an idle stream once MAX_STREAM_SLOTS
@@ -619,14 +624,14 @@ static int launch_hetero(vpt_context* ctx, const KParams& K, bool count, hipStre
     H.out = K.out;
     H.grid = K.grid;
     const Medium m{K.sigma_a, K.sigma_s, K.g, K.max_depth, K.march_step, K.march_light};
-    if (count || hetero_simple_kernel()) return vpt_int_hetero_simple_launch(H, m, ctx->d_scene, count ? K.counters : nullptr, stream);
+    if (count || hetero_simple_kernel()) return vpt_int_hetero_simple_launch(H, m, ctx->d_scene, ctx->h_grid.block > 0, count ? K.counters : nullptr, stream);
     std::lock_guard<std::mutex> lock(ctx->mu);
     StreamSlot* sl = nullptr;
     int rc = stream_slot(ctx, stream, 0, &sl);
     if (rc) return rc;
     H.queue = sl->d_queue;
     HIP_OK(hipMemsetAsync(H.queue, 0, sizeof(unsigned), stream));
-    rc = vpt_int_hetero_launch(ctx->device, H, m, ctx->d_scene, stream);
+    rc = vpt_int_hetero_launch(ctx->device, H, m, ctx->d_scene, ctx->h_grid.block > 0, stream);
     if (rc) return rc;
     return slot_done(sl, stream);
 }
@@ -926,6 +931,7 @@ void vpt_context_destroy(vpt_context* ctx)
     if (ctx->d_guard) (void)hipFree(ctx->d_guard);
     if (ctx->d_grid) (void)hipFree(ctx->d_grid);
     if (ctx->d_rho) (void)hipFree(ctx->d_rho);
+    if (ctx->d_maj) (void)hipFree(ctx->d_maj);
     for (auto& sl : ctx->slots) {
         if (sl->done) (void)hipEventSynchronize(sl->done);
         if (sl->d_partials) (void)hipFree(sl->d_partials);
@@ -986,6 +992,20 @@ int vpt_set_scene(vpt_context* ctx, const vpt_sphere* s, int n)
     return VPT_OK;
 }
 
+/* the block maxima of `density` (host) for block size B >= 1 on the device (*d_maj, the caller frees) and in
+ * the view */
+static hipError_t majorant_upload(vpt_grid_view* G, int B, const float* density, float** d_maj)
+{
+    int32_t nb[3];
+    vpt_grid_majorant_counts(G->n, B, nb);
+    std::vector<float> maj((size_t)nb[0] * (size_t)nb[1] * (size_t)nb[2]);
+    vpt_grid_majorant_build(G->n, B, density, maj.data());
+    hipError_t e = hipMalloc((void**)d_maj, maj.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(*d_maj, maj.data(), maj.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) vpt_grid_view_set_majorant(G, B, *d_maj);
+    return e;
+}
+
 int vpt_set_density_grid(vpt_context* ctx, const vpt_grid_desc* desc, const float* density)
 {
     vpt_clear_error();
@@ -994,8 +1014,10 @@ int vpt_set_density_grid(vpt_context* ctx, const vpt_grid_desc* desc, const floa
     if (!desc) {  /* clear */
         HIP_OK(hipDeviceSynchronize());
         if (ctx->d_rho) (void)hipFree(ctx->d_rho);
+        if (ctx->d_maj) (void)hipFree(ctx->d_maj);
         ctx->d_rho = nullptr;
-        ctx->has_grid = 0;
+        ctx->d_maj = nullptr;
+        ctx->has_grid = 0;  /* maj_block stays: the next grid gets its majorant grid */
         return VPT_OK;
     }
     int rc = vpt_int_grid_check(desc, density, "vpt_set_density_grid");
@@ -1007,28 +1029,74 @@ int vpt_set_density_grid(vpt_context* ctx, const vpt_grid_desc* desc, const floa
     vpt_grid_view G;
     vpt_grid_view_init(&G, dims, desc->lo, desc->hi, density, d_rho);  /* the majorant: scanned on the host */
     hipError_t e = hipMemcpy(d_rho, density, bytes, hipMemcpyHostToDevice);
+    float* d_maj = nullptr;
+    if (e == hipSuccess && ctx->maj_block) e = majorant_upload(&G, ctx->maj_block, density, &d_maj);
     if (e == hipSuccess && !ctx->d_grid) e = hipMalloc((void**)&ctx->d_grid, sizeof(vpt_grid_view));
     if (e == hipSuccess) e = hipDeviceSynchronize();  /* nothing in flight reads the previous grid */
     if (e == hipSuccess) e = hipMemcpy(ctx->d_grid, &G, sizeof G, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         (void)hipFree(d_rho);
+        if (d_maj) (void)hipFree(d_maj);
         return vpt_fail(VPT_E_HIP, "vpt_set_density_grid: %s", hipGetErrorString(e));
     }
     if (ctx->d_rho) (void)hipFree(ctx->d_rho);
+    if (ctx->d_maj) (void)hipFree(ctx->d_maj);
     ctx->d_rho = d_rho;
+    ctx->d_maj = d_maj;
+    ctx->h_grid = G;
     ctx->has_grid = 1;
     return VPT_OK;
 }
 
-int vpt_grid_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
-                   int n, double* tau, double* t_coll, uint64_t* states_out)
+int vpt_set_grid_majorant_block(vpt_context* ctx, int block)
 {
     vpt_clear_error();
+    if (!ctx) return vpt_fail(VPT_E_INVALID, "vpt_set_grid_majorant_block: NULL context");
+    if (block < 0) return vpt_fail(VPT_E_INVALID, "vpt_set_grid_majorant_block: block %d (0 = off, else >= 1 voxels per axis)", block);
+    if (!ctx->has_grid) {  /* applied when a grid is set */
+        ctx->maj_block = block;
+        return VPT_OK;
+    }
+    HIP_OK(hipSetDevice(ctx->device));
+    HIP_OK(hipDeviceSynchronize());  /* nothing in flight reads the view or the previous majorant grid */
+    vpt_grid_view G = ctx->h_grid;
+    float* d_maj = nullptr;
+    hipError_t e = hipSuccess;
+    if (block) {  /* the block maxima are scanned on the host, from the device's copy of the voxels */
+        const size_t nv = (size_t)G.n[0] * (size_t)G.n[1] * (size_t)G.n[2];
+        std::vector<float> rho(nv);
+        e = hipMemcpy(rho.data(), ctx->d_rho, nv * sizeof(float), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = majorant_upload(&G, block, rho.data(), &d_maj);
+    } else {
+        vpt_grid_view_set_majorant(&G, 0, nullptr);
+    }
+    if (e == hipSuccess) e = hipMemcpy(ctx->d_grid, &G, sizeof G, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (d_maj) (void)hipFree(d_maj);
+        return vpt_fail(VPT_E_HIP, "vpt_set_grid_majorant_block: %s", hipGetErrorString(e));
+    }
+    if (ctx->d_maj) (void)hipFree(ctx->d_maj);
+    ctx->d_maj = d_maj;
+    ctx->h_grid = G;
+    ctx->maj_block = block;
+    return VPT_OK;
+}
+
+/* vpt_grid_probe (lm false: the global-majorant track whatever the context's setting) and vpt_grid_probe_lm */
+static int grid_probe(vpt_context* ctx, bool lm, double sigma_t, const vpt_ray* rays, const double* tmax,
+                      const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out, uint32_t* steps)
+{
+    const char* who = lm ? "vpt_grid_probe_lm" : "vpt_grid_probe";
+    vpt_clear_error();
     if (!ctx || !rays || !tmax || !states || !tau || !t_coll || !states_out || n < 0)
-        return vpt_fail(VPT_E_INVALID, "vpt_grid_probe: bad arguments");
-    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "vpt_grid_probe: no density grid set (vpt_set_density_grid)");
+        return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
+    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "%s: no density grid set (vpt_set_density_grid)", who);
     if (n == 0) return VPT_OK;
     HIP_OK(hipSetDevice(ctx->device));
+    /* the existing probe keeps its global-majorant behaviour: a copy of the view without the majorant grid */
+    vpt_grid_view* dview = ctx->d_grid;
+    vpt_grid_view* dplain = nullptr;
+    uint32_t* dst = nullptr;
     vpt_ray* dr = nullptr;
     uint64_t *ds = nullptr, *dso = nullptr;
     double *dtm = nullptr, *dtau = nullptr, *dtc = nullptr;
@@ -1039,24 +1107,47 @@ int vpt_grid_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const 
     if (e == hipSuccess) e = hipMalloc((void**)&dtm, sizeof(double) * nn);
     if (e == hipSuccess) e = hipMalloc((void**)&dtau, sizeof(double) * nn);
     if (e == hipSuccess) e = hipMalloc((void**)&dtc, sizeof(double) * nn);
+    if (e == hipSuccess && steps) e = hipMalloc((void**)&dst, sizeof(uint32_t) * nn);
+    if (e == hipSuccess && !lm && ctx->h_grid.block > 0) {
+        vpt_grid_view G = ctx->h_grid;
+        vpt_grid_view_set_majorant(&G, 0, nullptr);
+        e = hipMalloc((void**)&dplain, sizeof G);
+        if (e == hipSuccess) e = hipMemcpy(dplain, &G, sizeof G, hipMemcpyHostToDevice);
+        dview = dplain;
+    }
     if (e == hipSuccess) e = hipMemcpy(dr, rays, sizeof(vpt_ray) * nn, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ds, states, sizeof(uint64_t) * nn, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dtm, tmax, sizeof(double) * nn, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        vpt_int_grid_probe_launch(ctx->d_grid, sigma_t, dr, dtm, ds, n, dtau, dtc, dso);
+        vpt_int_grid_probe_launch(dview, lm && ctx->h_grid.block > 0, sigma_t, dr, dtm, ds, n, dtau, dtc, dso, dst);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(tau, dtau, sizeof(double) * nn, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(t_coll, dtc, sizeof(double) * nn, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(states_out, dso, sizeof(uint64_t) * nn, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && steps) e = hipMemcpy(steps, dst, sizeof(uint32_t) * nn, hipMemcpyDeviceToHost);
+    if (dplain) (void)hipFree(dplain);
+    if (dst) (void)hipFree(dst);
     (void)hipFree(dr);
     (void)hipFree(ds);
     (void)hipFree(dso);
     (void)hipFree(dtm);
     (void)hipFree(dtau);
     (void)hipFree(dtc);
-    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "vpt_grid_probe: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "%s: %s", who, hipGetErrorString(e));
     return VPT_OK;
+}
+
+int vpt_grid_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
+                   int n, double* tau, double* t_coll, uint64_t* states_out)
+{
+    return grid_probe(ctx, false, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, nullptr);
+}
+
+int vpt_grid_probe_lm(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
+                      int n, double* tau, double* t_coll, uint64_t* states_out, uint32_t* steps)
+{
+    return grid_probe(ctx, true, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, steps);
 }
 
 int vpt_render_device(vpt_context* ctx, const vpt_params* p, void* d_out, void* stream)
@@ -1170,7 +1261,7 @@ static int trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* ray
         case 6: trace_batch_kernel<6><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         case 7: trace_batch_kernel<7><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         case 8: trace_batch_kernel<8><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
-        case VPT_HETERO_FREE: vpt_int_hetero_trace_launch(dr, ds, n, mm, ctx->d_scene, ctx->d_grid, dout, dso, stats); break;
+        case VPT_HETERO_FREE: vpt_int_hetero_trace_launch(dr, ds, n, mm, ctx->d_scene, ctx->d_grid, ctx->h_grid.block > 0, dout, dso, stats); break;
         default: trace_batch_kernel<9><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         }
         e = hipGetLastError();

@@ -35,7 +35,8 @@ struct KParams {
     const vpt_grid_view* grid;     /* estimator 10: the context's density grid (device), else NULL */
 };
 
-template <int EST, bool COUNT, int FB>
+/* LM: estimator 10 only -- the grid has a majorant grid (vpt_hetero.h) */
+template <int EST, bool COUNT, int FB, bool LM = false>
 __global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const DevScene* __restrict__ S)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const Dev
         dv3 dir = add(add(scl(cx, (((double)x + jx - 0.5) / P.w - .5)), scl(cy, (((double)y + jy - 0.5) / P.h - .5))), cd);
         dir = nrm(dir);
         dv3 L;
-        if constexpr (EST == VPT_HETERO_FREE) L = trace_hetero<COUNT>(S, GridTr{*P.grid}, smp, o, dir, m);
+        if constexpr (EST == VPT_HETERO_FREE) L = trace_hetero<COUNT, LM>(S, GridTr::load<LM>(P.grid), smp, o, dir, m);
         else L = trace_sample<EST, COUNT>(S, smp, o, dir, m, EST == 6 ? march_oc : nullptr);
         acc = add(L, acc);
         if (COUNT) {

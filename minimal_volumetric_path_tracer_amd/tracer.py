@@ -86,15 +86,32 @@ def _probe_args(rays, tmax, states):
     return r, t, s, np.zeros(len(r)), np.zeros(len(r)), np.zeros(len(r), dtype=np.uint64)
 
 
-def grid_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, states):
+def grid_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, states, majorant_block: int = 0, return_steps: bool = False):
     """csrc/vpt_grid.h on the host (vpt_grid_probe_host, no GPU): per ray (unit direction) the optical depth of
     the grid over t in [0, tmax], the delta-tracking result from `states` (-1: none, NaN: step cap) and the
-    erand48 states after the track."""
+    erand48 states after the track.  majorant_block > 0 tracks with local majorants on super-voxels of that
+    many voxels per axis (vpt_grid_probe_host_lm); return_steps appends the tentative steps of each track."""
     d, r = _grid_args(rho, lo, hi)
     ry, t, s, tau, tc, so = _probe_args(rays, tmax, states)
-    check(lib().vpt_grid_probe_host(byref(d), r.ctypes.data, float(sigma_t), ry.ctypes.data, t.ctypes.data, s.ctypes.data,
-                                    len(ry), tau.ctypes.data, tc.ctypes.data, so.ctypes.data))
-    return tau, tc, so
+    if not majorant_block and not return_steps:
+        check(lib().vpt_grid_probe_host(byref(d), r.ctypes.data, float(sigma_t), ry.ctypes.data, t.ctypes.data,
+                                        s.ctypes.data, len(ry), tau.ctypes.data, tc.ctypes.data, so.ctypes.data))
+        return tau, tc, so
+    steps = np.zeros(len(ry), dtype=np.uint32)
+    check(lib().vpt_grid_probe_host_lm(byref(d), r.ctypes.data, int(majorant_block), float(sigma_t), ry.ctypes.data,
+                                       t.ctypes.data, s.ctypes.data, len(ry), tau.ctypes.data, tc.ctypes.data,
+                                       so.ctypes.data, steps.ctypes.data))
+    return (tau, tc, so, steps) if return_steps else (tau, tc, so)
+
+
+def _set_grid_with_block(owner, block, upload) -> None:
+    """set_density_grid(..., majorant_block=block) of Tracer and MultiTracer: the grid first -- a rejected grid
+    leaves the grid and the block size as they were -- then the block size, where it changes."""
+    if block is not None and int(block) < 0:
+        owner.set_majorant_block(block)  # raises VPT_E_INVALID before anything is uploaded
+    upload()
+    if block is not None and int(block) != owner._majorant_block:
+        owner.set_majorant_block(block)
 
 
 @dataclass
@@ -147,6 +164,7 @@ class Tracer:
         check(lib().vpt_context_create(device, byref(h)))
         self._ctx = h
         self.device = device
+        self._majorant_block = 0  # the context's setting (vpt_set_grid_majorant_block)
         self.set_scene(default_scene() if spheres is None else spheres)
 
     def close(self) -> None:
@@ -166,21 +184,32 @@ class Tracer:
         self.spheres = s
 
     # ---- heterogeneous medium (estimator "hetero") ----
-    def set_density_grid(self, rho, lo, hi) -> None:
+    def set_density_grid(self, rho, lo, hi, majorant_block: Optional[int] = None) -> None:
         """The density grid of estimator "hetero": rho of shape [nz, ny, nx] (float32, finite, >= 0) in the world
-        box [lo, hi], zero outside; sigma_a / sigma_s are then per unit density.  Kept across set_scene."""
+        box [lo, hi], zero outside; sigma_a / sigma_s are then per unit density.  Kept across set_scene.
+        majorant_block: set_majorant_block for this and later grids (None leaves the tracer's setting alone); a
+        grid that is rejected leaves the setting as it was."""
         d, r = _grid_args(rho, lo, hi)
-        check(lib().vpt_set_density_grid(self._ctx, byref(d), r.ctypes.data))
+        _set_grid_with_block(self, majorant_block, lambda: check(lib().vpt_set_density_grid(self._ctx, byref(d), r.ctypes.data)))
+
+    def set_majorant_block(self, block: int) -> None:
+        """Local majorants for delta tracking: super-voxels of `block` voxels per axis, each with its own
+        majorant (0, the default: the global majorant only).  Belongs to the tracer: applied to the current grid
+        and to every later one.  Fewer null collisions on sparse fields; the same estimator, other draws."""
+        check(lib().vpt_set_grid_majorant_block(self._ctx, int(block)))
+        self._majorant_block = int(block)
 
     def clear_density_grid(self) -> None:
         check(lib().vpt_set_density_grid(self._ctx, None, None))
 
-    def grid_probe(self, sigma_t: float, rays, tmax, states):
-        """grid_probe_host's quantities for the tracer's grid, computed on the GPU (vpt_grid_probe)."""
+    def grid_probe(self, sigma_t: float, rays, tmax, states, return_steps: bool = False):
+        """grid_probe_host's quantities for the tracer's grid and its majorant block, computed on the GPU
+        (vpt_grid_probe_lm); return_steps appends the tentative steps of each track."""
         ry, t, s, tau, tc, so = _probe_args(rays, tmax, states)
-        check(lib().vpt_grid_probe(self._ctx, float(sigma_t), ry.ctypes.data, t.ctypes.data, s.ctypes.data, len(ry),
-                                   tau.ctypes.data, tc.ctypes.data, so.ctypes.data))
-        return tau, tc, so
+        steps = np.zeros(len(ry), dtype=np.uint32)
+        check(lib().vpt_grid_probe_lm(self._ctx, float(sigma_t), ry.ctypes.data, t.ctypes.data, s.ctypes.data, len(ry),
+                                      tau.ctypes.data, tc.ctypes.data, so.ctypes.data, steps.ctypes.data))
+        return (tau, tc, so, steps) if return_steps else (tau, tc, so)
 
     # ---- main()'s pixel loop (src/rt.cpp:767-805) ----
     def render(self, cfg: Optional[RenderConfig] = None, **kw) -> np.ndarray:
@@ -413,14 +442,20 @@ class MultiTracer:
             check(lib().vpt_multi_create(n_gpus, byref(h)))
         self._m = h
         self.n_gpus = n_gpus
+        self._majorant_block = 0
         s = np.ascontiguousarray(default_scene() if spheres is None else spheres, dtype=SPHERE_DTYPE)
         check(lib().vpt_multi_set_scene(self._m, s.ctypes.data, len(s)))
         self.spheres = s
 
-    def set_density_grid(self, rho, lo, hi) -> None:
+    def set_density_grid(self, rho, lo, hi, majorant_block: Optional[int] = None) -> None:
         """Tracer.set_density_grid on every rank's context."""
         d, r = _grid_args(rho, lo, hi)
-        check(lib().vpt_multi_set_density_grid(self._m, byref(d), r.ctypes.data))
+        _set_grid_with_block(self, majorant_block, lambda: check(lib().vpt_multi_set_density_grid(self._m, byref(d), r.ctypes.data)))
+
+    def set_majorant_block(self, block: int) -> None:
+        """Tracer.set_majorant_block on every rank's context."""
+        check(lib().vpt_multi_set_grid_majorant_block(self._m, int(block)))
+        self._majorant_block = int(block)
 
     def clear_density_grid(self) -> None:
         check(lib().vpt_multi_set_density_grid(self._m, None, None))

@@ -11,8 +11,16 @@ each of b, c, b16, c16 with hetero_kernel and with VPT_SIMPLE_KERNEL=1 (render_k
 hetero_kernel on --nolds-lib, a build that reads every grid from global memory
 (bash scripts/build_variant.sh hetero_nolds -DVPT_HETERO_LDS=0; the default stages grids of at most 64 KiB -- b, b16
 and c16 -- in LDS).
+  c_B<k>, c16_B<k>   c and c16 with local majorants on super-voxels of k = 2, 4, 8, 16 voxels per axis
+             (Tracer.set_majorant_block; hetero_kernel only), with the steps per track; and, where
+             --noldsmaj-lib is built (bash scripts/build_variant.sh hetero_noldsmaj -DVPT_HETERO_LDS_MAJ=0), the same
+             rows on that build, which reads the majorant grid from global memory (the default stages it in what
+             the density left of the 64 KiB of LDS)
 Every row runs in a child process of its own under a timeout, and the driver stops at the first failure.
-Prints one JSON line.  usage: python scripts/hetero_time.py [--reps N] [--size WxH] [--spp N] [--nolds-lib PATH]"""
+Prints one JSON line.
+--only takes a comma-separated subset of the row groups base (a, b, c, b16, c16), simple, nolds, lm, noldsmaj.
+usage: python scripts/hetero_time.py [--reps N] [--size WxH] [--spp N] [--only GROUPS] [--nolds-lib PATH]
+       [--noldsmaj-lib PATH]"""
 import argparse
 import json
 import os
@@ -25,6 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 SIGMA = dict(sigma_a=0.003, sigma_s=0.027, max_depth=8)
+BLOCKS = (2, 4, 8, 16)
 ROOM_LO, ROOM_HI = (-60.0, -50.0, -100.0), (60.0, 50.0, 230.0)
 BIG_LO, BIG_HI = (-4096.0,) * 3, (4096.0,) * 3
 
@@ -90,6 +99,9 @@ def step(args):
         cfg = vpt.RenderConfig(width=w, height=h, spp=args.spp, estimator="ff", seed=0x5EED0001, **SIGMA)
     else:
         rho, lo, hi = grids(args.step)
+        if args.block:
+            tr.set_majorant_block(args.block)
+            res["majorant_block"] = args.block
         tr.set_density_grid(rho, lo, hi)
         cfg = vpt.RenderConfig(width=w, height=h, spp=args.spp, estimator="hetero", seed=0x5EED0001, **SIGMA)
         res.update(grid=list(rho.shape), rho_max_over_mean=round(float(rho.max() / rho.mean()), 3))
@@ -124,7 +136,7 @@ def step(args):
     print(json.dumps(res))
 
 
-def child(args, row, simple=False, lib=None, timeout=240):
+def child(args, row, simple=False, lib=None, block=0, timeout=240):
     env = dict(os.environ)
     env.pop("VPT_SIMPLE_KERNEL", None)
     if simple:
@@ -132,7 +144,7 @@ def child(args, row, simple=False, lib=None, timeout=240):
     if lib:
         env["VPT_LIB"] = lib
     cmd = [sys.executable, os.path.abspath(__file__), "--step", row, "--reps", str(args.reps), "--size", args.size,
-           "--spp", str(args.spp)]
+           "--spp", str(args.spp), "--block", str(block)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
     if r.returncode != 0:
         raise RuntimeError(f"row {row} failed with status {r.returncode}: {r.stderr[-2000:]}")
@@ -145,21 +157,38 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--size", default="1024x1024")
     ap.add_argument("--spp", type=int, default=64)
+    ap.add_argument("--only", default="base,simple,nolds,lm,noldsmaj")
+    ap.add_argument("--block", type=int, default=0, help="with --step: the majorant block size (0: off)")
     ap.add_argument("--nolds-lib", default=os.path.join(ROOT, "build_variants", "libvpt_hetero_nolds.so"))
+    ap.add_argument("--noldsmaj-lib", default=os.path.join(ROOT, "build_variants", "libvpt_hetero_noldsmaj.so"))
     args = ap.parse_args()
     if args.step:
         return step(args)
     out = {"command": "python scripts/hetero_time.py " + " ".join(sys.argv[1:]), "size": args.size, "spp": args.spp}
+    groups = set(args.only.split(","))
     try:  # the first failure (or timeout) ends the run: nothing more is started on the GPU
-        out["a"] = child(args, "a")
+        if "base" in groups:
+            out["a"] = child(args, "a")
         for row in ("b", "c", "b16", "c16"):
-            out[row] = child(args, row)
-            out[row + "_simple"] = child(args, row, simple=True)
-        if os.path.exists(args.nolds_lib):
+            if "base" in groups:
+                out[row] = child(args, row)
+            if "simple" in groups:
+                out[row + "_simple"] = child(args, row, simple=True)
+        if "nolds" in groups and os.path.exists(args.nolds_lib):
             for row in ("b", "c", "b16", "c16"):
                 out[row + "_nolds"] = child(args, row, lib=args.nolds_lib)
-        else:
+        elif "nolds" in groups:
             out["nolds"] = f"{os.path.relpath(args.nolds_lib, ROOT)} is not built"
+        if "lm" in groups:
+            for row in ("c", "c16"):
+                for b in BLOCKS:
+                    out[f"{row}_B{b}"] = child(args, row, block=b)
+        if "noldsmaj" in groups and os.path.exists(args.noldsmaj_lib):
+            for row in ("c", "c16"):
+                for b in BLOCKS:
+                    out[f"{row}_B{b}_noldsmaj"] = child(args, row, lib=args.noldsmaj_lib, block=b)
+        elif "noldsmaj" in groups:
+            out["noldsmaj"] = f"{os.path.relpath(args.noldsmaj_lib, ROOT)} is not built"
     except (RuntimeError, subprocess.TimeoutExpired) as e:
         out["error"] = str(e)
         print(json.dumps(out))
