@@ -168,28 +168,40 @@ __device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridTr&
     return p.L;
 }
 
-/* what hetero_kernel (vpt_hetero.hip) needs of a render: vpt_kernels.hip fills it from its own parameters */
-struct HeteroParams {
-    int32_t w, h, spp, fb;
-    int32_t band_rows, band_stride, band_offset, shard_rows;
-    int32_t tiles_x, tiles_y;
-    uint64_t seed;
-    double o[3], d[3], cx[3], cy[3];
-    void* out;
-    unsigned* queue;               /* pixel work queue head (zeroed before the launch) */
-    const vpt_grid_view* grid;     /* device */
+/* the three steps as the persistent-wave loop (vpt_wave.h) calls them, on the kernel's view of the grid */
+template <bool LM>
+struct HeteroSteps {
+    GridTr tp;
+    template <bool COUNT>
+    __device__ __forceinline__ int decide(const DevScene* __restrict__ S, Sampler<COUNT>& smp, Path& p, Event& e,
+                                          const Medium& m) const
+    {
+        return hetero_decide<COUNT, LM>(S, tp, smp, p, e, m);
+    }
+    template <bool COUNT>
+    __device__ __forceinline__ void surface(const DevScene* __restrict__ S, Sampler<COUNT>& smp, Path& p, const Event& e,
+                                            const Medium& m) const
+    {
+        hetero_surface(S, tp, smp, p, e, m);
+    }
+    template <bool COUNT>
+    __device__ __forceinline__ void medium(const DevScene* __restrict__ S, Sampler<COUNT>& smp, Path& p, const Event& e,
+                                           const Medium& m) const
+    {
+        hetero_medium(S, tp, smp, p, e, m);
+    }
 };
+
+struct KParams;  /* a render's launch parameters (vpt_render_simple.h) */
 
 }  // namespace vpt
 
 /* vpt_hetero.hip: the persistent-wave render kernel of estimator 10, enqueued on `stream` (the caller owns
- * the queue word and has zeroed it in stream order); lm: the grid has a majorant grid (the kernel's LM
+ * the queue word K.queue and has zeroed it in stream order); lm: the grid has a majorant grid (the kernel's LM
  * instantiation) */
-int vpt_int_hetero_launch(int device, const vpt::HeteroParams& H, const vpt::Medium& m, const DevScene* S, bool lm,
-                          void* stream);
-/* render_kernel_simple<10> for the same render (counters: vpt_count_work's device counters, else NULL) */
-int vpt_int_hetero_simple_launch(const vpt::HeteroParams& H, const vpt::Medium& m, const DevScene* S, bool lm,
-                                 unsigned long long* counters, void* stream);
+int vpt_int_hetero_launch(int device, const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
+/* render_kernel_simple<10> for the same render; counting iff K.counters (vpt_count_work's device counters) is set */
+int vpt_int_hetero_simple_launch(const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
 /* the per-sample call and the grid probe on device arrays, default stream (the caller reads hipGetLastError);
  * lm: the grid behind `grid` has a majorant grid; stats: vpt_debug_hetero_steps' two counters, else NULL; steps: the
  * probe's per-ray tentative steps, else NULL */

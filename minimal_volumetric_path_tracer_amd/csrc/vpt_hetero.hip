@@ -4,12 +4,10 @@
  * stepping through a voxel grid, latency-bound and divergent, not ray/sphere arithmetic, and the unit can
  * take compile flags of its own.
  *
- * hetero_kernel: persistent waves, the scheme of vpt_kernels.hip's render_kernel.  A lane owns one pixel and
- * runs that pixel's samples strictly in order (acc = L + acc, then * (1 / (double)spp)), so the image is
- * render_kernel_simple<10>'s bit for bit; a lane regenerates a path the moment one ends, and takes its next
- * pixel from a device-wide queue in 8x8-tile order (one atomic per wave).  After decide (intersection, light
- * pick, delta tracking) a lane holds a pending surface or medium event and the wave runs one of the two
- * shading blocks per round, the one more lanes wait for.
+ * hetero_kernel: the persistent-wave loop of vpt_wave.h on estimator 10's steps (HeteroSteps, vpt_hetero.h).  A
+ * lane owns one pixel and runs that pixel's samples strictly in order (acc = L + acc, then * (1 / (double)spp)),
+ * so the image is render_kernel_simple<10>'s bit for bit.  What the kernel adds to the loop is the prologue
+ * that stages the grid in LDS.
  *
  * Density reads: a grid of at most 64 KiB (16 384 voxels) is staged in LDS once per workgroup
  * (VPT_HETERO_LDS, on by default); a larger one is read from global memory, where the L2 holds the grids of
@@ -19,9 +17,9 @@
  */
 #include <hip/hip_runtime.h>
 
-#include <string.h>
+#include <type_traits>
 
-#include "vpt_render_simple.h"
+#include "vpt_wave.h"
 #include "vpt_internal.h"
 
 #ifndef VPT_HETERO_LDS
@@ -37,15 +35,12 @@
 namespace vpt {
 
 template <bool COUNT, int FB, bool LM>
-__global__ __launch_bounds__(256, 2) void hetero_kernel(HeteroParams P, Medium m, const DevScene* __restrict__ S)
+__global__ __launch_bounds__(256, 2) void hetero_kernel(KParams P, const DevScene* __restrict__ S)
 {
-    const int lane = threadIdx.x & 63;
-    const uint64_t below = (1ull << lane) - 1ull;
-    const dv3 o0 = mk(P.o[0], P.o[1], P.o[2]);
-    const dv3 cd = mk(P.d[0], P.d[1], P.d[2]);
-    const dv3 cx = mk(P.cx[0], P.cx[1], P.cx[2]), cy = mk(P.cy[0], P.cy[1], P.cy[2]);
-    const unsigned npix = (unsigned)P.tiles_x * (unsigned)P.tiles_y * 64u;
-    GridTr tp = GridTr::load<LM>(P.grid);
+    /* the view lives in the steps object from the start: the walkers take its address, so a copy made after the
+     * prologue is a second stack object (416 against 288 bytes of scratch, 9 against 4 spilled VGPRs) */
+    HeteroSteps<LM> st{GridTr::load<LM>(P.grid)};
+    [[maybe_unused]] GridTr& tp = st.tp;
 #if VPT_HETERO_LDS
     __shared__ float lds_rho[VPT_HETERO_LDS_BYTES / sizeof(float)];
     {
@@ -69,119 +64,7 @@ __global__ __launch_bounds__(256, 2) void hetero_kernel(HeteroParams P, Medium m
 #endif
     }
 #endif
-
-    int x = 0, y = 0, lr = 0;
-    uint64_t idx = 0;
-    int i = 0;                 /* next sample to start */
-    bool done = false, need_pixel = true, in_path = false;
-    int pending = EV_END;
-    dv3 acc = mk(0, 0, 0);
-    Path p;
-    Event e;
-    e.pdf = 0;
-    Sampler<COUNT> smp;
-    smp.X = 0;
-    smp.g = m.g;
-    smp.cnt.tests = 0;
-    smp.cnt.iterations = 0;
-    smp.cnt.draw_mismatch = 0;
-
-    while (true) {
-        /* (1) converged: lanes without a pixel take the next ones from the queue */
-        const uint64_t needm = __ballot(need_pixel && !done);
-        if (needm) {
-            const int leader = __ffsll((unsigned long long)needm) - 1;
-            unsigned base = 0;
-            if (lane == leader) base = atomicAdd(P.queue, (unsigned)__popcll(needm));
-            base = __shfl(base, leader);
-            if (need_pixel && !done) {
-                const unsigned q = base + (unsigned)__popcll(needm & below);
-                if (q >= npix) {
-                    done = true;
-                } else {
-                    const unsigned tile = q >> 6, within = q & 63u;
-                    x = (int)(tile % (unsigned)P.tiles_x) * 8 + (int)(within & 7u);
-                    lr = (int)(tile / (unsigned)P.tiles_x) * 8 + (int)(within >> 3);
-                    if (x < P.w && lr < P.shard_rows) {
-                        const int k = lr / P.band_rows, r = lr - k * P.band_rows;
-                        const int fr = (P.band_offset + k * P.band_stride) * P.band_rows + r; /* file row */
-                        y = P.h - 1 - fr;                                                       /* camera row */
-                        idx = (uint64_t)fr * (uint64_t)P.w + (uint64_t)x;                       /* src/rt.cpp:773 */
-                        i = 0;
-                        acc = mk(0, 0, 0);
-                        need_pixel = false;
-                    }
-                }
-            }
-        }
-        if (__ballot(!done) == 0) break;
-
-        /* (2) lanes without a pending event advance their path to the next event */
-        if (!done && !need_pixel && pending == EV_END) {
-            while (true) {
-                if (!in_path) {
-                    if (i == P.spp) {
-                        acc = scl(acc, (1 / (double)P.spp));  /* src/rt.cpp:800 */
-                        const size_t oi = ((size_t)lr * (size_t)P.w + (size_t)x) * 3;
-                        if (FB == VPT_FB_F32) {
-                            float* out = (float*)P.out;
-                            out[oi] = (float)acc.x;
-                            out[oi + 1] = (float)acc.y;
-                            out[oi + 2] = (float)acc.z;
-                        } else {
-                            double* out = (double*)P.out;
-                            out[oi] = acc.x;
-                            out[oi + 1] = acc.y;
-                            out[oi + 2] = acc.z;
-                        }
-                        need_pixel = true;
-                        break;
-                    }
-                    smp.X = vpt_stream_start(P.seed, idx, (uint64_t)i);
-                    ++i;
-                    /* jittered camera ray, src/rt.cpp:787, x draw first */
-                    const double jx = smp.next();
-                    const double jy = smp.next();
-                    const dv3 dir = add(add(scl(cx, (((double)x + jx - 0.5) / P.w - .5)), scl(cy, (((double)y + jy - 0.5) / P.h - .5))), cd);
-                    p.o = o0;
-                    p.d = nrm(dir);
-                    p.beta = mk(1, 1, 1);
-                    p.L = mk(0, 0, 0);
-                    p.depth = 0;
-                    in_path = true;
-                }
-                if (!continue_path(smp, p, m)) {
-                    acc = add(p.L, acc);  /* src/rt.cpp:794 */
-                    in_path = false;
-                    continue;
-                }
-                const int ev = hetero_decide<COUNT, LM>(S, tp, smp, p, e, m);
-                if (ev == EV_END) {
-                    acc = add(p.L, acc);
-                    in_path = false;
-                    continue;
-                }
-                pending = ev;
-                break;
-            }
-        }
-
-        /* (3) run one shading block: the one more lanes wait for */
-        const int ns = __popcll(__ballot(pending == EV_SURF));
-        const int nm = __popcll(__ballot(pending == EV_MED));
-        if (ns + nm == 0) continue;
-        if (ns >= nm) {
-            if (pending == EV_SURF) {
-                hetero_surface(S, tp, smp, p, e, m);
-                pending = EV_END;
-            }
-        } else {
-            if (pending == EV_MED) {
-                hetero_medium(S, tp, smp, p, e, m);
-                pending = EV_END;
-            }
-        }
-    }
+    wave_render<HeteroSteps<LM>, COUNT, FB>(P, S, st);
 }
 
 }  // namespace vpt
@@ -253,81 +136,48 @@ void vpt_int_grid_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_
     if (lm) grid_probe_kernel<true><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, steps);
     else grid_probe_kernel<false><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, steps);
 }
-
-/* render_kernel_simple<10> (vpt_render_simple.h): counting mode (counters != NULL) and VPT_SIMPLE_KERNEL=1 */
-template <bool COUNT, int FB, bool LM>
-static int launch_simple(const KParams& K, const DevScene* S, hipStream_t stream)
+/* run-time flags as compile-time constants: f(std::bool_constant<flag>{}...) */
+template <class F>
+static int with_flags(F f)
 {
-    dim3 grid((unsigned)((K.w + 15) / 16), (unsigned)((K.shard_rows + 15) / 16));
-    render_kernel_simple<VPT_HETERO_FREE, COUNT, FB, LM><<<grid, dim3(256), 0, stream>>>(K, S);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "render_kernel_simple<10> launch: %s", hipGetErrorString(e));
-    return VPT_OK;
+    return f();
+}
+template <class F, class... Bools>
+static int with_flags(F f, bool flag, Bools... rest)
+{
+    if (flag) return with_flags([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
+    return with_flags([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
 }
 
-int vpt_int_hetero_simple_launch(const HeteroParams& H, const Medium& m, const DevScene* S, bool lm,
-                                 unsigned long long* counters, void* stream)
+/* render_kernel_simple<10> (vpt_render_simple.h): counting mode (K.counters != NULL) and VPT_SIMPLE_KERNEL=1 */
+int vpt_int_hetero_simple_launch(const KParams& K, const DevScene* S, bool lm, void* stream)
 {
-    KParams K;
-    memset(&K, 0, sizeof K);
-    K.w = H.w;
-    K.h = H.h;
-    K.spp = H.spp;
-    K.fb = H.fb;
-    K.band_rows = H.band_rows;
-    K.band_stride = H.band_stride;
-    K.band_offset = H.band_offset;
-    K.shard_rows = H.shard_rows;
-    K.sigma_a = m.sigma_a;
-    K.sigma_s = m.sigma_s;
-    K.g = m.g;
-    K.max_depth = m.max_depth;
-    K.est = VPT_HETERO_FREE;
-    K.march_step = m.march_step;
-    K.march_light = m.march_light;
-    K.seed = H.seed;
-    for (int i = 0; i < 3; ++i) {
-        K.o[i] = H.o[i];
-        K.d[i] = H.d[i];
-        K.cx[i] = H.cx[i];
-        K.cy[i] = H.cy[i];
-    }
-    K.out = H.out;
-    K.counters = counters;
-    K.tiles_x = H.tiles_x;
-    K.tiles_y = H.tiles_y;
-    K.grid = H.grid;
-    hipStream_t st = (hipStream_t)stream;
-    const bool f32 = H.fb == VPT_FB_F32;
-    if (lm) {
-        if (counters) return f32 ? launch_simple<true, VPT_FB_F32, true>(K, S, st) : launch_simple<true, VPT_FB_F64, true>(K, S, st);
-        return f32 ? launch_simple<false, VPT_FB_F32, true>(K, S, st) : launch_simple<false, VPT_FB_F64, true>(K, S, st);
-    }
-    if (counters) return f32 ? launch_simple<true, VPT_FB_F32, false>(K, S, st) : launch_simple<true, VPT_FB_F64, false>(K, S, st);
-    return f32 ? launch_simple<false, VPT_FB_F32, false>(K, S, st) : launch_simple<false, VPT_FB_F64, false>(K, S, st);
+    return with_flags([&](auto lmc, auto count, auto f32) {
+        constexpr int FB = decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64;
+        dim3 grid((unsigned)((K.w + 15) / 16), (unsigned)((K.shard_rows + 15) / 16));
+        render_kernel_simple<VPT_HETERO_FREE, decltype(count)::value, FB, decltype(lmc)::value><<<grid, dim3(256), 0, (hipStream_t)stream>>>(K, S);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "render_kernel_simple<10> launch: %s", hipGetErrorString(e));
+        return (int)VPT_OK;
+    }, lm, K.counters != nullptr, K.fb == VPT_FB_F32);
 }
 
-template <int FB, bool LM>
-static int launch(int device, const HeteroParams& H, const Medium& m, const DevScene* S, hipStream_t stream)
+int vpt_int_hetero_launch(int device, const KParams& K, const DevScene* S, bool lm, void* stream)
 {
-    int per_cu = 0, cus = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hetero_kernel<false, FB, LM>, 256, 0);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_kernel: %s", hipGetErrorString(e));
-    int blocks = (per_cu < 1 ? 1 : per_cu) * cus;
-    const int tiles = H.tiles_x * H.tiles_y;
-    const int need = (tiles + 3) / 4;  /* 4 waves per block, one tile per wave to start */
-    if (blocks > need) blocks = need;
-    if (blocks < 1) blocks = 1;
-    hetero_kernel<false, FB, LM><<<dim3((unsigned)blocks), dim3(256), 0, stream>>>(H, m, S);
-    e = hipGetLastError();
-    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_kernel launch: %s", hipGetErrorString(e));
-    return VPT_OK;
-}
-
-int vpt_int_hetero_launch(int device, const HeteroParams& H, const Medium& m, const DevScene* S, bool lm, void* stream)
-{
-    hipStream_t st = (hipStream_t)stream;
-    if (lm) return H.fb == VPT_FB_F32 ? launch<VPT_FB_F32, true>(device, H, m, S, st) : launch<VPT_FB_F64, true>(device, H, m, S, st);
-    return H.fb == VPT_FB_F32 ? launch<VPT_FB_F32, false>(device, H, m, S, st) : launch<VPT_FB_F64, false>(device, H, m, S, st);
+    return with_flags([&](auto lmc, auto f32) {
+        const auto kern = hetero_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value>;
+        int per_cu = 0, cus = 0;
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0);
+        if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+        if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_kernel: %s", hipGetErrorString(e));
+        int blocks = (per_cu < 1 ? 1 : per_cu) * cus;
+        const int tiles = K.tiles_x * K.tiles_y;
+        const int need = (tiles + 3) / 4;  /* 4 waves per block, one tile per wave to start */
+        if (blocks > need) blocks = need;
+        if (blocks < 1) blocks = 1;
+        kern<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(K, S);
+        e = hipGetLastError();
+        if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_kernel launch: %s", hipGetErrorString(e));
+        return (int)VPT_OK;
+    }, lm, K.fb == VPT_FB_F32);
 }

@@ -1,11 +1,10 @@
 /*
  * vpt_kernels.hip -- HIP kernels (gfx950) and the device half of the C ABI (include/vpt.h).
  *
- * render_kernel replaces main()'s OpenMP pixel loop (src/rt.cpp:767-805): one lane owns one
- * pixel and runs its spp camera samples (src/rt.cpp:786-798) through the estimator, accumulating
- * in FP64 in the reference's order, then writes the average (src/rt.cpp:800) once.  A wave
- * covers an 8x8 pixel tile (neighbouring camera rays hit the same surfaces, which keeps the
- * sphere loop and the shading branches coherent); a 256-thread workgroup covers 16x16.
+ * A render of the estimators 0-5 runs on the workgroup task pool (pool_kernel, vpt_pool.h) and reduce_kernel;
+ * ray marching (6-9), counting mode and VPT_SIMPLE_KERNEL=1 run render_kernel_simple (vpt_render_simple.h), one
+ * lane per pixel; estimator 10's kernels live in vpt_hetero.hip.  render_kernel, the persistent-wave loop of
+ * vpt_wave.h, is compiled only into -DVPT_DEBUG_ENV=1 builds.  The rest are the per-sample calls and the probes.
  */
 #include <hip/hip_runtime.h>
 
@@ -19,7 +18,7 @@
 
 #include "vpt_device.h"
 #include "vpt_pool.h"
-#include "vpt_render_simple.h"
+#include "vpt_wave.h"
 #include "vpt_internal.h"
 
 /* the EST = 1 pool kernel comes from vpt_pool_mis.hip, compiled with flags of its own (VPT_MIS_TU;
@@ -50,158 +49,12 @@ namespace {
             return vpt_fail(VPT_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));       \
     } while (0)
 
-/* camera ray of one sample, src/rt.cpp:787 (x draw first) */
-template <bool COUNT>
-__device__ __forceinline__ dv3 camera_dir(const KParams& P, Sampler<COUNT>& smp, int x, int y)
-{
-    const dv3 cd = mk(P.d[0], P.d[1], P.d[2]);
-    const dv3 cx = mk(P.cx[0], P.cx[1], P.cx[2]), cy = mk(P.cy[0], P.cy[1], P.cy[2]);
-    double jx = smp.next();
-    double jy = smp.next();
-    dv3 dir = add(add(scl(cx, (((double)x + jx - 0.5) / P.w - .5)), scl(cy, (((double)y + jy - 0.5) / P.h - .5))), cd);
-    return nrm(dir);
-}
-
-template <int FB>
-__device__ __forceinline__ void store_pixel(const KParams& P, int x, int lr, dv3 acc)
-{
-    acc = scl(acc, (1 / (double)P.spp));  /* src/rt.cpp:800 */
-    const size_t oi = ((size_t)lr * (size_t)P.w + (size_t)x) * 3;
-    if (FB == VPT_FB_F32) {
-        float* out = (float*)P.out;
-        out[oi] = (float)acc.x;
-        out[oi + 1] = (float)acc.y;
-        out[oi + 2] = (float)acc.z;
-    } else {
-        double* out = (double*)P.out;
-        out[oi] = acc.x;
-        out[oi + 1] = acc.y;
-        out[oi + 2] = acc.z;
-    }
-}
-
-/*
- * Persistent wavefront scheduler.  Every lane owns one pixel at a time and runs that pixel's
- * camera samples strictly in order (so the per-pixel FP64 sum is the reference's, bit for bit),
- * but the wave no longer waits for its longest path:
- *   - path regeneration: a lane whose path ends starts its next sample at once;
- *   - a lane that finishes its pixel takes the next one from a device-wide queue (one atomic per
- *     wave, 8x8-tile order for coherent camera rays), so waves drain together at the very end;
- *   - deferred events: after the common part of an iteration (roulette, intersection, light and
- *     distance sampling) a lane holds a pending SURFACE or MEDIUM event; each round the wave runs
- *     only ONE of the two shading blocks -- the one with more lanes per unit of cost -- and the
- *     other lanes keep their event for a later round (no data moves, no divergence between the
- *     two blocks).
- */
+/* the persistent-wave loop (vpt_wave.h) on the estimators 0-9: the round-1 design, which the pool kernel
+ * replaced; an A/B path of -DVPT_DEBUG_ENV=1 builds (launch_wave) */
 template <int EST, bool COUNT, int FB>
 __global__ __launch_bounds__(256) void render_kernel(KParams P, const DevScene* __restrict__ S)
 {
-    const int lane = threadIdx.x & 63;
-    const uint64_t below = (1ull << lane) - 1ull;
-    const Medium m{P.sigma_a, P.sigma_s, P.g, P.max_depth, P.march_step, P.march_light};
-    const dv3 o0 = mk(P.o[0], P.o[1], P.o[2]);
-    const unsigned npix = (unsigned)P.tiles_x * (unsigned)P.tiles_y * 64u;
-
-    int x = 0, y = 0, lr = 0;
-    uint64_t idx = 0;
-    int i = 0;                 /* next sample to start */
-    bool done = false, need_pixel = true, in_path = false;
-    int pending = EV_END;
-    dv3 acc = mk(0, 0, 0);
-    Path p;
-    Event e;
-    e.pdf = 0;
-    Sampler<COUNT> smp;
-    smp.X = 0;
-    smp.g = P.g;
-    smp.cnt.tests = 0;
-    smp.cnt.iterations = 0;
-    smp.cnt.draw_mismatch = 0;
-
-    while (true) {
-        /* (1) converged: lanes without a pixel take the next ones from the queue */
-        const uint64_t needm = __ballot(need_pixel && !done);
-        if (needm) {
-            const int leader = __ffsll((unsigned long long)needm) - 1;
-            unsigned base = 0;
-            if (lane == leader) base = atomicAdd(P.queue, (unsigned)__popcll(needm));
-            base = __shfl(base, leader);
-            if (need_pixel && !done) {
-                const unsigned q = base + (unsigned)__popcll(needm & below);
-                if (q >= npix) {
-                    done = true;
-                } else {
-                    const unsigned tile = q >> 6, within = q & 63u;
-                    x = (int)(tile % (unsigned)P.tiles_x) * 8 + (int)(within & 7u);
-                    lr = (int)(tile / (unsigned)P.tiles_x) * 8 + (int)(within >> 3);
-                    if (x < P.w && lr < P.shard_rows) {
-                        const int k = lr / P.band_rows, r = lr - k * P.band_rows;
-                        const int fr = (P.band_offset + k * P.band_stride) * P.band_rows + r; /* file row */
-                        y = P.h - 1 - fr;                                                       /* camera row */
-                        idx = (uint64_t)fr * (uint64_t)P.w + (uint64_t)x;                       /* src/rt.cpp:773 */
-                        i = 0;
-                        acc = mk(0, 0, 0);
-                        need_pixel = false;
-                    }
-                }
-            }
-        }
-        if (__ballot(!done) == 0) break;
-
-        /* (2) lanes without a pending event advance their path to the next event */
-        if (!done && !need_pixel && pending == EV_END) {
-            while (true) {
-                if (!in_path) {
-                    if (i == P.spp) {
-                        store_pixel<FB>(P, x, lr, acc);
-                        need_pixel = true;
-                        break;
-                    }
-                    smp.X = vpt_stream_start(P.seed, idx, (uint64_t)i);
-                    ++i;
-                    p.o = o0;
-                    p.d = camera_dir(P, smp, x, y);
-                    p.beta = mk(1, 1, 1);
-                    p.L = mk(0, 0, 0);
-                    p.depth = 0;
-                    in_path = true;
-                }
-                if (!continue_path(smp, p, m)) {
-                    acc = add(p.L, acc);  /* src/rt.cpp:794 */
-                    in_path = false;
-                    continue;
-                }
-                const int ev = decide<EST>(S, smp, p, e, m);
-                if (ev == EV_END) {
-                    acc = add(p.L, acc);
-                    in_path = false;
-                    continue;
-                }
-                pending = ev;
-                break;
-            }
-        }
-
-        /* (3) run one shading block: the one with more pending lanes per unit of cost */
-        const int ns = __popcll(__ballot(pending == EV_SURF));
-        const int nm = __popcll(__ballot(pending == EV_MED));
-        if (ns + nm == 0) continue;
-        if (ns * P.cost_med >= nm * P.cost_surf) {
-            if (pending == EV_SURF) {
-                surface_event<EST>(S, smp, p, e, m);
-                pending = EV_END;
-            }
-        } else {
-            if (pending == EV_MED) {
-                medium_event<EST>(S, smp, p, e, m);
-                pending = EV_END;
-            }
-        }
-    }
-    if (COUNT) {
-        atomicAdd(&P.counters[0], (unsigned long long)smp.cnt.tests);
-        atomicAdd(&P.counters[1], (unsigned long long)smp.cnt.iterations);
-    }
+    wave_render<EstSteps<EST>, COUNT, FB>(P, S, {});
 }
 
 template <int EST>
@@ -600,38 +453,17 @@ static bool hetero_simple_kernel()
 
 /* estimator 10 (vpt_hetero.hip): hetero_kernel on the stream's queue word; counting mode and
  * VPT_SIMPLE_KERNEL=1: render_kernel_simple<10> */
-static int launch_hetero(vpt_context* ctx, const KParams& K, bool count, hipStream_t stream)
+static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
 {
-    HeteroParams H;
-    memset(&H, 0, sizeof H);
-    H.w = K.w;
-    H.h = K.h;
-    H.spp = K.spp;
-    H.fb = K.fb;
-    H.band_rows = K.band_rows;
-    H.band_stride = K.band_stride;
-    H.band_offset = K.band_offset;
-    H.shard_rows = K.shard_rows;
-    H.tiles_x = K.tiles_x;
-    H.tiles_y = K.tiles_y;
-    H.seed = K.seed;
-    for (int i = 0; i < 3; ++i) {
-        H.o[i] = K.o[i];
-        H.d[i] = K.d[i];
-        H.cx[i] = K.cx[i];
-        H.cy[i] = K.cy[i];
-    }
-    H.out = K.out;
-    H.grid = K.grid;
-    const Medium m{K.sigma_a, K.sigma_s, K.g, K.max_depth, K.march_step, K.march_light};
-    if (count || hetero_simple_kernel()) return vpt_int_hetero_simple_launch(H, m, ctx->d_scene, ctx->h_grid.block > 0, count ? K.counters : nullptr, stream);
+    const bool lm = ctx->h_grid.block > 0;
+    if (K.counters || hetero_simple_kernel()) return vpt_int_hetero_simple_launch(K, ctx->d_scene, lm, stream);
     std::lock_guard<std::mutex> lock(ctx->mu);
     StreamSlot* sl = nullptr;
     int rc = stream_slot(ctx, stream, 0, &sl);
     if (rc) return rc;
-    H.queue = sl->d_queue;
-    HIP_OK(hipMemsetAsync(H.queue, 0, sizeof(unsigned), stream));
-    rc = vpt_int_hetero_launch(ctx->device, H, m, ctx->d_scene, ctx->h_grid.block > 0, stream);
+    K.queue = sl->d_queue;
+    HIP_OK(hipMemsetAsync(K.queue, 0, sizeof(unsigned), stream));
+    rc = vpt_int_hetero_launch(ctx->device, K, ctx->d_scene, lm, stream);
     if (rc) return rc;
     return slot_done(sl, stream);
 }
@@ -640,7 +472,7 @@ template <int EST, bool COUNT, int FB>
 static int launch_one(vpt_context* ctx, KParams K, hipStream_t stream)
 {
     if constexpr (EST == VPT_HETERO_FREE) {  /* its kernels live in vpt_hetero.hip */
-        return launch_hetero(ctx, K, COUNT, stream);
+        return launch_hetero(ctx, K, stream);
     } else {
         const DevScene* S = ctx->d_scene;
         /* counting (vpt_count_work) needs only the totals: the one-lane-per-pixel kernel, which is
@@ -718,7 +550,7 @@ static int pool_enqueue(vpt_context* ctx, const KParams& K, PoolParams& Q, uint6
     Q.queue = queue;
     Q.guard = ctx->d_guard;
     Q.guard_bias = ctx->guard_bias;
-    const Medium m{K.sigma_a, K.sigma_s, K.g, K.max_depth, K.march_step, K.march_light};
+    const Medium m = medium_of(K);
     /* a pass over a tile list runs pool_kernel<EST, false, true>, which exists for the estimators 0 and 1 */
     constexpr bool HAS_TILES = EST <= 1;
     const bool tiles = Q.tile_map != nullptr;

@@ -1,6 +1,7 @@
 /*
- * vpt_render_simple.h -- the one-lane-per-pixel render kernel and its launch parameters, shared by the two
- * translation units that instantiate it: vpt_kernels.hip (estimators 0-9) and vpt_hetero.hip (estimator 10,
+ * vpt_render_simple.h -- a render's launch parameters (KParams), the per-pixel helpers every render kernel but
+ * the pool kernel uses (row mapping, camera ray, pixel store), and the one-lane-per-pixel render kernel, shared by
+ * the two translation units that instantiate it: vpt_kernels.hip (estimators 0-9) and vpt_hetero.hip (estimator 10,
  * so that the code object of vpt_kernels.hip -- the tuned pool kernels and their placement -- stays what it was
  * before estimator 10 existed).  render_kernel_simple replaces main()'s OpenMP pixel loop (src/rt.cpp:767-805):
  * one lane owns one pixel and runs its spp camera samples (src/rt.cpp:786-798) through the estimator,
@@ -12,9 +13,7 @@
 #include "vpt_device.h"
 #include "vpt_hetero.h"
 
-namespace {
-
-using namespace vpt;
+namespace vpt {
 
 struct KParams {
     int32_t w, h, spp, fb;
@@ -35,6 +34,61 @@ struct KParams {
     const vpt_grid_view* grid;     /* estimator 10: the context's density grid (device), else NULL */
 };
 
+__host__ __device__ __forceinline__ Medium medium_of(const KParams& P)
+{
+    return Medium{P.sigma_a, P.sigma_s, P.g, P.max_depth, P.march_step, P.march_light};
+}
+
+/* where row lr of the shard lies in the image: the bands of band_rows rows are dealt out band_stride apart */
+struct PixelRow {
+    int fr, y;     /* file row, camera row */
+    uint64_t idx;  /* the pixel's stream index, src/rt.cpp:773 */
+};
+
+__device__ __forceinline__ PixelRow pixel_row(const KParams& P, int x, int lr)
+{
+    const int k = lr / P.band_rows, r = lr - k * P.band_rows;
+    const int fr = (P.band_offset + k * P.band_stride) * P.band_rows + r;
+    return PixelRow{fr, P.h - 1 - fr, (uint64_t)fr * (uint64_t)P.w + (uint64_t)x};
+}
+
+/* camera ray of one sample, src/rt.cpp:787 (x draw first) */
+template <bool COUNT>
+__device__ __forceinline__ dv3 camera_dir(const KParams& P, Sampler<COUNT>& smp, int x, int y)
+{
+    const dv3 cd = mk(P.d[0], P.d[1], P.d[2]);
+    const dv3 cx = mk(P.cx[0], P.cx[1], P.cx[2]), cy = mk(P.cy[0], P.cy[1], P.cy[2]);
+    double jx = smp.next();
+    double jy = smp.next();
+    dv3 dir = add(add(scl(cx, (((double)x + jx - 0.5) / P.w - .5)), scl(cy, (((double)y + jy - 0.5) / P.h - .5))), cd);
+    return nrm(dir);
+}
+
+/* the pixel's average (src/rt.cpp:800) into row lr of the shard's framebuffer */
+template <int FB>
+__device__ __forceinline__ void store_pixel(const KParams& P, int x, int lr, dv3 acc)
+{
+    acc = scl(acc, (1 / (double)P.spp));
+    const size_t oi = ((size_t)lr * (size_t)P.w + (size_t)x) * 3;
+    if (FB == VPT_FB_F32) {
+        float* out = (float*)P.out;
+        out[oi] = (float)acc.x;
+        out[oi + 1] = (float)acc.y;
+        out[oi + 2] = (float)acc.z;
+    } else {
+        double* out = (double*)P.out;
+        out[oi] = acc.x;
+        out[oi + 1] = acc.y;
+        out[oi + 2] = acc.z;
+    }
+}
+
+}  // namespace vpt
+
+namespace {
+
+using namespace vpt;
+
 /* LM: estimator 10 only -- the grid has a majorant grid (vpt_hetero.h) */
 template <int EST, bool COUNT, int FB, bool LM = false>
 __global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const DevScene* __restrict__ S)
@@ -50,27 +104,19 @@ __global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const Dev
         __syncthreads();
     }
     if (x >= P.w || lr >= P.shard_rows) return;
-    const int k = lr / P.band_rows, r = lr - k * P.band_rows;
-    const int fr = (P.band_offset + k * P.band_stride) * P.band_rows + r;  /* file row */
-    const int y = P.h - 1 - fr;                                              /* camera row */
-    const uint64_t idx = (uint64_t)fr * (uint64_t)P.w + (uint64_t)x;          /* src/rt.cpp:773 */
-    const Medium m{P.sigma_a, P.sigma_s, P.g, P.max_depth, P.march_step, P.march_light};
-    const dv3 o = mk(P.o[0], P.o[1], P.o[2]), cd = mk(P.d[0], P.d[1], P.d[2]);
-    const dv3 cx = mk(P.cx[0], P.cx[1], P.cx[2]), cy = mk(P.cy[0], P.cy[1], P.cy[2]);
+    const PixelRow row = pixel_row(P, x, lr);
+    const Medium m = medium_of(P);
+    const dv3 o = mk(P.o[0], P.o[1], P.o[2]);
     dv3 acc = mk(0, 0, 0);
     uint64_t tests = 0, iters = 0, mism = 0;
     for (int i = 0; i < P.spp; ++i) {
         Sampler<COUNT> smp;
-        smp.X = vpt_stream_start(P.seed, idx, (uint64_t)i);
+        smp.X = vpt_stream_start(P.seed, row.idx, (uint64_t)i);
         smp.g = P.g;
         smp.cnt.tests = 0;
         smp.cnt.iterations = 0;
         smp.cnt.draw_mismatch = 0;
-        /* jittered camera ray, src/rt.cpp:787, x draw first */
-        double jx = smp.next();
-        double jy = smp.next();
-        dv3 dir = add(add(scl(cx, (((double)x + jx - 0.5) / P.w - .5)), scl(cy, (((double)y + jy - 0.5) / P.h - .5))), cd);
-        dir = nrm(dir);
+        const dv3 dir = camera_dir(P, smp, x, row.y);
         dv3 L;
         if constexpr (EST == VPT_HETERO_FREE) L = trace_hetero<COUNT, LM>(S, GridTr::load<LM>(P.grid), smp, o, dir, m);
         else L = trace_sample<EST, COUNT>(S, smp, o, dir, m, EST == 6 ? march_oc : nullptr);
@@ -81,19 +127,7 @@ __global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const Dev
             mism += smp.cnt.draw_mismatch;
         }
     }
-    acc = scl(acc, (1 / (double)P.spp));
-    const size_t oi = ((size_t)lr * (size_t)P.w + (size_t)x) * 3;
-    if (FB == VPT_FB_F32) {
-        float* out = (float*)P.out;
-        out[oi] = (float)acc.x;
-        out[oi + 1] = (float)acc.y;
-        out[oi + 2] = (float)acc.z;
-    } else {
-        double* out = (double*)P.out;
-        out[oi] = acc.x;
-        out[oi + 1] = acc.y;
-        out[oi + 2] = acc.z;
-    }
+    store_pixel<FB>(P, x, lr, acc);
     if (COUNT) {
         atomicAdd(&P.counters[0], (unsigned long long)tests);
         atomicAdd(&P.counters[1], (unsigned long long)iters);

@@ -2,8 +2,10 @@
 kept structural knob (VPT_KILL_RINGS=0, the pool without kill-predicting rings), the forms the round-6
 changes replaced, and the debug / measurement builds (section timers, scheduler statistics and
 timelines, the round-1 wave kernel behind VPT_DEBUG_ENV, a VPT_DUP build).
-A device-side syntax and template-instantiation check of csrc/vpt_kernels.hip for gfx950 -- seconds,
-no GPU; the A/B builds themselves go through scripts/build_variant.sh."""
+The debug_env arm also compiles the persistent-wave loop (vpt_wave.h) through render_kernel.  The arms of
+csrc/vpt_hetero.hip: the default, and the builds that read the density or the majorant grid from global memory.
+A device-side syntax and template-instantiation check of each file for gfx950 -- seconds, no GPU; the A/B
+builds themselves go through scripts/build_variant.sh."""
 import os
 import shutil
 import subprocess
@@ -30,12 +32,19 @@ ARMS = {
                    "-DVPT_SS_FUSE=0"],
     "dup_sections": ["-DVPT_DUP=3"],  # a VPT_DUP measurement build (scripts/dup_pmc.sh)
 }
+HETERO_ARMS = {
+    "hetero": [],
+    "hetero_no_lds": ["-DVPT_HETERO_LDS=0"],
+    "hetero_no_lds_maj": ["-DVPT_HETERO_LDS_MAJ=0"],
+}
+CASES = [("vpt_kernels.hip", a, ARMS[a]) for a in sorted(ARMS)] + \
+    [("vpt_hetero.hip", a, HETERO_ARMS[a]) for a in sorted(HETERO_ARMS)]
 
 
 @pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="hipcc not installed")
-@pytest.mark.parametrize("arm", sorted(ARMS))
-def test_knob_arm_compiles(arm):
+@pytest.mark.parametrize("file,flags", [pytest.param(f, fl, id=a) for f, a, fl in CASES])
+def test_knob_arm_compiles(file, flags):
     cmd = [HIPCC, "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-fsyntax-only", "--cuda-device-only",
-           "-Wno-unused-command-line-argument", "-DVPT_MIS_TU=0"] + ARMS[arm] + ["vpt_kernels.hip"]
+           "-Wno-unused-command-line-argument", "-DVPT_MIS_TU=0"] + flags + [file]
     r = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
