@@ -84,14 +84,21 @@ typedef enum {
     VPT_RAY_MARCHING_EXPLICIT = 9, /* rayMarching, rayMarchingMethods.h:34: the Color it returns for the camera
                                     * ray with sigma_t = sigma_a + sigma_s, steps = march_step (a count),
                                     * light = sphere 5; its out-parameters: vpt_ray_marching_batch */
-    VPT_HETERO_FREE = 10           /* extension: iterativeVPTracerFree's control flow in a heterogeneous medium, the
+    VPT_HETERO_FREE = 10,          /* extension: iterativeVPTracerFree's control flow in a heterogeneous medium, the
                                     * density grid of vpt_set_density_grid (VPT_E_INVALID without one): delta
                                     * tracking for freeFlightSample, the grid's transmittance for every
                                     * transmittance factor; sigma_a, sigma_s are per unit density; a ray that
                                     * leaves the grid without a hit ends its path; rendered by a kernel of its own
                                     * (chunk_spp is ignored, as for 6-9); csrc/vpt_grid.h, csrc/vpt_hetero.h */
+    VPT_HETERO_RATIO = 11          /* extension: VPT_HETERO_FREE statement for statement, with every transmittance
+                                    * factor a ratio-tracking estimate over the same segment, drawn from the
+                                    * sample's own stream where estimator 10 evaluates the factor (a factor it skips
+                                    * as an exact zero and a zero-length segment draw nothing): the same
+                                    * expectation, other draws, a cost that follows the majorant optical depth and
+                                    * not the grid's resolution; honours vpt_set_grid_majorant_block; not in the
+                                    * accumulator (VPT_E_UNSUPPORTED) */
 } vpt_estimator;
-#define VPT_NUM_ESTIMATORS 11
+#define VPT_NUM_ESTIMATORS 12
 
 typedef enum {
     VPT_FB_F32 = 0,            /* framebuffer: 3 x float per pixel */
@@ -153,7 +160,7 @@ void vpt_context_destroy(vpt_context* ctx);
 /* Copies the scene to the device (replaces the reference's global `spheres`). */
 int vpt_set_scene(vpt_context* ctx, const vpt_sphere* spheres, int n);
 
-/* ---- heterogeneous medium (estimator VPT_HETERO_FREE) ----
+/* ---- heterogeneous medium (estimators VPT_HETERO_FREE, VPT_HETERO_RATIO) ----
  * nx x ny x nz float32 voxels of density rho >= 0 (finite), x fastest, piecewise constant inside the world box
  * [lo, hi]; rho = 0 outside.  The medium's coefficients are rho(x) sigma_a and rho(x) sigma_s. */
 typedef struct vpt_grid_desc {
@@ -164,7 +171,8 @@ typedef struct vpt_grid_desc {
  * must not change while a render is in flight.  A dimension < 1, hi <= lo, a NaN, negative or infinite density
  * or more than 2^27 voxels -> VPT_E_INVALID (the previous grid stays). */
 int vpt_set_density_grid(vpt_context* ctx, const vpt_grid_desc* desc, const float* density);
-/* Local majorants for the delta tracking of estimator VPT_HETERO_FREE (csrc/vpt_grid.h): the voxels are grouped
+/* Local majorants for the delta tracking of estimators VPT_HETERO_FREE and VPT_HETERO_RATIO (and the ratio tracking
+ * of the latter; csrc/vpt_grid.h): the voxels are grouped
  * into cubic super-voxels of `block` voxels per axis, each with the maximum density of its voxels, and a track
  * steps with the majorant of the super-voxel it is in (empty ones are skipped).  Fewer null collisions on sparse
  * fields; the same estimator in distribution, other draws.  block 0 (the default) turns it off: the single
@@ -330,6 +338,16 @@ int vpt_grid_probe_lm(vpt_context* ctx, double sigma_t, const vpt_ray* rays, con
 int vpt_grid_probe_host_lm(const vpt_grid_desc* desc, const float* density, int block, double sigma_t, const vpt_ray* rays,
                            const double* tmax, const uint64_t* states, int n, double* tau, double* t_coll,
                            uint64_t* states_out, uint32_t* steps);
+/* Ratio-tracking probe (csrc/vpt_grid.h: vpt_grid_ratio, vpt_grid_ratio_lm; estimator VPT_HETERO_RATIO's
+ * transmittance): that[i] = the estimate of exp(-sigma_t tau) over t in [0, tmax[i]] from states[i] (in [0, 1];
+ * NaN: the 2^22-step cap), states_out[i] = the state after it, steps[i] (may be NULL) = its draws.  The GPU probe
+ * honours the context's vpt_set_grid_majorant_block setting; the host probe takes the block size (0: the global
+ * majorant, < 0 -> VPT_E_INVALID).  Host arrays, synchronous. */
+int vpt_grid_ratio_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax,
+                         const uint64_t* states, int n, double* that, uint64_t* states_out, uint32_t* steps);
+int vpt_grid_ratio_probe_host(const vpt_grid_desc* desc, const float* density, int block, double sigma_t,
+                              const vpt_ray* rays, const double* tmax, const uint64_t* states, int n, double* that,
+                              uint64_t* states_out, uint32_t* steps);
 
 /* PPM writer of main() (src/rt.cpp:812-820): clamp to [0,1] (src/rt.cpp:803), gamma 1/2.2,
  * int(v*255 + .5) (include/mathUtilities.h:43-45), "P3\n%d %d\n255\n" then "%d %d %d " per

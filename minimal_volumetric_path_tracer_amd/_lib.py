@@ -24,6 +24,7 @@ VPT_MAX_SPHERES = 64
 FREE_FLIGHT, MIS_EQUIANGULAR, EXPLICIT_FREE, IMPLICIT_FREE, EXPLICIT_EQUIANGULAR, SURFACE_PT, RAY_MARCHING = 0, 1, 2, 3, 4, 5, 6  # vpt_estimator
 RAY_MARCHING_SA, RAY_MARCHING_GLOBAL, RAY_MARCHING_EXPLICIT = 7, 8, 9
 HETERO_FREE = 10
+HETERO_RATIO = 11
 FB_F32, FB_F64 = 0, 1
 
 # numpy view of vpt_sphere == reference Sphere (include/Sphere.h:12-21), 144 bytes
@@ -139,6 +140,9 @@ PROTOTYPES = [
                                   c_void_p]),
     ("vpt_grid_probe_host_lm", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p,
                                        c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vpt_grid_ratio_probe", c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    ("vpt_grid_ratio_probe_host", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p,
+                                          c_int, c_void_p, c_void_p, c_void_p]),
     ("vpt_write_ppm", c_int, [c_char_p, c_void_p, c_int, c_int, c_int]),
     ("vpt_encode_ppm", c_int64, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64]),
     ("vpt_last_error", c_char_p, []),

@@ -536,9 +536,12 @@ VPT_DEV double transmitance(dv3 a, dv3 b, double sigma_t)
 
 /* Transmittance policy of the helpers estimator 10 (vpt_hetero.h) shares with the homogeneous estimators:
  * TrHom (the default) selects the code above, unchanged; a policy with hom == false supplies
- * between(a, b, sigma_t) and along(o, unit d, dist, sigma_t) -- the density grid's transmittance. */
+ * between(a, b, sigma_t) and along(o, unit d, dist, sigma_t) -- the density grid's transmittance.  A policy
+ * with draws == true estimates the factor stochastically and takes the sampler as its first argument (estimator
+ * 11's ratio tracking): the draws are taken where the factor is evaluated. */
 struct TrHom {
     static constexpr bool hom = true;
+    static constexpr bool draws = false;
 };
 
 /* multipleT, include/volumetricBasicFunctions.h:26-57 (material-3 spheres only) */
@@ -932,6 +935,8 @@ VPT_DEV dv3 mis_v2(const DevScene* __restrict__ S, Sampler<COUNT>& smp, int obj,
         dv3 f = light_sample_sa(S, smp, light, x, obj, omat, n, wray, wiLight, cmax, alpha);
         if constexpr (TP::hom) {
             if (TR) f = scl(f, transmitance(x, sph_p(S, light), sigma_t));
+        } else if constexpr (TP::draws) {
+            if (TR) f = scl(f, tp.between(smp, x, sph_p(S, light), sigma_t));
         } else {
             if (TR) f = scl(f, tp.between(x, sph_p(S, light), sigma_t));
         }
@@ -1419,6 +1424,7 @@ VPT_DEV dv3 point_shadow_value(const DevScene* __restrict__ S, Sampler<COUNT>& s
     double ph = smp.g == 0.0 ? 1 / (4 * VPT_PI) : phase_value(smp.g, din, VPT_PL_REUSE ? wl : nrm(sub(lp, xt)));
     dv3 Ls;
     if constexpr (TP::hom) Ls = scl(scl(Le, VPT_PL_REUSE ? lm_exp(sigma_t * mag * -1.0) : transmitance(xt, lp, sigma_t)), ph);
+    else if constexpr (TP::draws) Ls = scl(scl(Le, tp.between(smp, xt, lp, sigma_t)), ph);
     else Ls = scl(scl(Le, tp.between(xt, lp, sigma_t)), ph);
     if (with_sigma) return scl(scl(scl(Ls, trxt), sigma_s), (1 / probSource));
     return scl(Ls, (1 / probSource));
@@ -1531,6 +1537,7 @@ VPT_DEV dv3 single_scattering(const DevScene* __restrict__ S, Sampler<COUNT>& sm
         if (!(point && zero_ok && cmax == 1.0)) {
             double it;
             if constexpr (TP::hom) it = lm_exp(sigma_t * tdist * -1.0);
+            else if constexpr (TP::draws) it = tp.along(smp, xt, wl, tdist, sigma_t);
             else it = tp.along(xt, wl, tdist, sigma_t);
             double ph = smp.g == 0.0 ? 1 / (4 * VPT_PI) : phase_value(smp.g, din, wl);
             dv3 Ls = scl(scl(rad, it), ph);

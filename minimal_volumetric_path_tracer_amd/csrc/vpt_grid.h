@@ -52,6 +52,16 @@
  * and the candidate as t + (rem / s), the global track's t + (-log(1 - xi) / (rho_max * sigma_t)); a NaN
  * candidate fails tc < te and ends at the boundary test as "none".  With B = 1 the majorant is the voxel's own
  * density, no collision is null, and a track takes exactly one draw: analytic inversion of the optical depth.
+ *
+ * Ratio tracking (Novak et al. 2014; vpt_grid_ratio, vpt_grid_ratio_lm; estimator 11, vpt_hetero.h): a stochastic,
+ * unbiased estimate That of exp(-sigma_t tau(o, d, tmax)) whose cost follows the majorant optical depth, not the
+ * grid's resolution.  That = 1.0 with no draw exactly where the track returns "none" without one; else the
+ * track's tentative points from the same state (step 1 and 2 above, with the global or the local majorant mu):
+ * wherever the track returns "none" the estimate returns That; at a tentative point with density rho:
+ * rho >= mu returns +0.0, else That = That * (1.0 - rho / mu) and the walk goes on.  There is NO second draw, so
+ * `steps` is the number of draws.  Capped like the track (NaN).  With B >= max(n) the local estimate is the global
+ * one bit for bit; with B = 1 a ray takes one draw and That is 1.0 where the track (B = 1) from the same state
+ * returns "none" and +0.0 where it collides, with the same end state.
  */
 #ifndef VPT_GRID_H
 #define VPT_GRID_H
@@ -327,6 +337,82 @@ VPT_GR double vpt_grid_track_lm(const vpt_grid_view* G, const double o[3], const
         const double rho = vpt_grid_density(G, o[0] + d[0] * tc, o[1] + d[1] * tc, o[2] + d[2] * tc);
         if (rho >= mu) return tc;
         if (vpt_erand48(X) * mu < rho) return tc;
+        t = tc;
+    }
+    return (double)NAN;
+}
+
+/* ratio tracking (header comment): the estimate That of exp(-sigma_t tau(o, d, tmax)), NaN for a capped walk;
+ * *X is the erand48 state, advanced by the draws taken; *steps (optional) counts them */
+VPT_GR double vpt_grid_ratio(const vpt_grid_view* G, const double o[3], const double d[3], double tmax, double sigma_t,
+                             uint64_t* X, uint32_t* steps)
+{
+    double t0, t1;
+    if (steps) *steps = 0;
+    if (!(G->rho_max > 0.0)) return 1.0;
+    if (!vpt_grid_slab(G, o, d, &t0, &t1)) return 1.0;
+    double t = t0, That = 1.0;
+    for (int k = 0; k < VPT_GRID_MAX_TRACK_STEPS; ++k) {
+        t = t + (-VPT_GRID_LOG(1 - vpt_erand48(X)) / (G->rho_max * sigma_t));
+        if (steps) *steps = (uint32_t)(k + 1);
+        if (t > tmax || t >= t1 || t != t) return That;
+        const double rho = vpt_grid_density(G, o[0] + d[0] * t, o[1] + d[1] * t, o[2] + d[2] * t);
+        if (rho >= G->rho_max) return 0.0;
+        That = That * (1.0 - rho / G->rho_max);
+    }
+    return (double)NAN;
+}
+
+/* ratio tracking with local majorants (header comment; G->block >= 1): vpt_grid_ratio's arguments and results.
+ * The walk is vpt_grid_track_lm's, restated: sharing it would put the weight into the track's loop */
+VPT_GR double vpt_grid_ratio_lm(const vpt_grid_view* G, const double o[3], const double d[3], double tmax,
+                                double sigma_t, uint64_t* X, uint32_t* steps)
+{
+    double t0, t1;
+    if (steps) *steps = 0;
+    if (!(G->rho_max > 0.0)) return 1.0;
+    if (!vpt_grid_slab(G, o, d, &t0, &t1)) return 1.0;
+    int i[3], step[3];
+    double tn[3], inv[3];
+    for (int a = 0; a < 3; ++a) {
+        i[a] = vpt_grid_axis_index(G, a, o[a] + d[a] * t0) / G->block;
+        step[a] = d[a] > 0.0 ? 1 : (d[a] < 0.0 ? -1 : 0);
+        inv[a] = step[a] ? 1.0 / d[a] : 0.0;
+        tn[a] = step[a] ? (vpt_grid_block_plane(G, a, i[a] + (step[a] > 0)) - o[a]) * inv[a] : VPT_GRID_BIG;
+    }
+    const int max_cross = G->nb[0] + G->nb[1] + G->nb[2] + 4;
+    double t = t0, That = 1.0;
+    int a = tn[0] <= tn[1] ? (tn[0] <= tn[2] ? 0 : 2) : (tn[1] <= tn[2] ? 1 : 2);
+    double te = tn[a];
+    double mu = te > t ? (double)G->maj[((int64_t)i[2] * G->nb[1] + i[1]) * G->nb[0] + i[0]] : 0.0;
+    for (int k = 0; k < VPT_GRID_MAX_TRACK_STEPS; ++k) {
+        double rem = -VPT_GRID_LOG(1 - vpt_erand48(X));
+        if (steps) *steps = (uint32_t)(k + 1);
+        double tc = 0.0;
+        int c = 0;
+        for (; c < max_cross; ++c) {
+            if (te > t) {
+                if (mu > 0.0) {
+                    const double s = mu * sigma_t;
+                    tc = t + (rem / s);
+                    if (tc < te) break;  /* a tentative collision */
+                    rem = rem - s * (te - t);
+                }
+                t = te;
+            }
+            if (!(te < t1) || te > tmax) return That;
+            i[a] += step[a];
+            if (i[a] < 0 || i[a] >= G->nb[a]) return That;
+            tn[a] = (vpt_grid_block_plane(G, a, i[a] + (step[a] > 0)) - o[a]) * inv[a];
+            a = tn[0] <= tn[1] ? (tn[0] <= tn[2] ? 0 : 2) : (tn[1] <= tn[2] ? 1 : 2);
+            te = tn[a];
+            mu = te > t ? (double)G->maj[((int64_t)i[2] * G->nb[1] + i[1]) * G->nb[0] + i[0]] : 0.0;
+        }
+        if (c == max_cross) return That;
+        if (tc > tmax || tc >= t1) return That;
+        const double rho = vpt_grid_density(G, o[0] + d[0] * tc, o[1] + d[1] * tc, o[2] + d[2] * tc);
+        if (rho >= mu) return 0.0;
+        That = That * (1.0 - rho / mu);
         t = tc;
     }
     return (double)NAN;

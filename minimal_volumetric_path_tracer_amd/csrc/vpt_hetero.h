@@ -33,6 +33,7 @@ namespace vpt {
 /* the grid's transmittance as the TP policy of mis_v2 / single_scattering (vpt_device.h TrHom) */
 struct GridTr {
     static constexpr bool hom = false;
+    static constexpr bool draws = false;
     vpt_grid_view G;
     /* the context's view from device memory.  Without local majorants only the fields the global-majorant
      * walkers read are copied (everything before `maj`): block, nb and maj stay unset and nothing reads them, so
@@ -60,14 +61,49 @@ struct GridTr {
     }
 };
 
+/* estimator 11's policy: every factor is a ratio-tracking estimate (vpt_grid.h) over the same segment, drawn from
+ * the sample's own stream where GridTr evaluates the factor -- a policy with draws == true takes the sampler first.
+ * A zero-length segment is 1.0 without a draw, as vpt_grid_tau's is exp(-0).  LM: the grid has a majorant grid. */
+template <bool LM>
+struct GridRatioTr {
+    static constexpr bool hom = false;
+    static constexpr bool draws = true;
+    vpt_grid_view G;
+    template <bool LM_>
+    __device__ __forceinline__ static GridRatioTr load(const vpt_grid_view* __restrict__ g)
+    {
+        static_assert(LM_ == LM, "the policy's LM is the kernel's");
+        GridRatioTr tp;
+        if (LM) tp.G = *g;
+        else __builtin_memcpy(&tp.G, g, offsetof(vpt_grid_view, maj));
+        return tp;
+    }
+    template <bool COUNT>
+    __device__ __forceinline__ double along(Sampler<COUNT>& smp, dv3 o, dv3 d, double dist, double sigma_t) const
+    {
+        if (!(dist > 0)) return lm_exp(sigma_t * 0.0 * -1.0);
+        const double oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
+        return LM ? vpt_grid_ratio_lm(&G, oo, dd, dist, sigma_t, &smp.X, (uint32_t*)nullptr)
+                  : vpt_grid_ratio(&G, oo, dd, dist, sigma_t, &smp.X, (uint32_t*)nullptr);
+    }
+    template <bool COUNT>
+    __device__ __forceinline__ double between(Sampler<COUNT>& smp, dv3 a, dv3 b, double sigma_t) const
+    {
+        const dv3 aux = sub(b, a);
+        const double dist = vm_sqrt(dot(aux, aux));
+        if (!(dist > 0)) return lm_exp(sigma_t * 0.0 * -1.0);
+        return along(smp, a, nrm(aux), dist, sigma_t);
+    }
+};
+
 /* measurement only (vpt_debug_hetero_steps): delta-tracking calls and their tentative steps */
 struct HeteroStats {
     unsigned long long tracks, steps;
 };
 
 /* decide<0> with delta tracking in freeFlightSample's place */
-template <bool COUNT, bool LM = false>
-VPT_DEV int hetero_decide(const DevScene* __restrict__ S, const GridTr& tp, Sampler<COUNT>& smp, Path& p, Event& e,
+template <bool COUNT, bool LM = false, class TP = GridTr>
+VPT_DEV int hetero_decide(const DevScene* __restrict__ S, const TP& tp, Sampler<COUNT>& smp, Path& p, Event& e,
                           const Medium& m, HeteroStats* hs = nullptr)
 {
     const double sigma_t = m.sigma_a + m.sigma_s;
@@ -105,8 +141,8 @@ VPT_DEV int hetero_decide(const DevScene* __restrict__ S, const GridTr& tp, Samp
 }
 
 /* surface_event<0> (MK = -1, PT = -1) */
-template <bool COUNT>
-VPT_DEV void hetero_surface(const DevScene* __restrict__ S, const GridTr& tp, Sampler<COUNT>& smp, Path& p,
+template <bool COUNT, class TP>
+VPT_DEV void hetero_surface(const DevScene* __restrict__ S, const TP& tp, Sampler<COUNT>& smp, Path& p,
                             const Event& e, const Medium& m)
 {
     const double sigma_t = m.sigma_a + m.sigma_s;
@@ -116,9 +152,11 @@ VPT_DEV void hetero_surface(const DevScene* __restrict__ S, const GridTr& tp, Sa
     const dv3 nx = nrm(sub(xs, sph_p(S, id)));
     const double probSource = 1.0 / S->n_emit;
     const double alpha = S->sph[id].alpha;
-    const double Trs = tp.between(xs, sph_p(S, src), sigma_t);
+    double Trs;
+    if constexpr (TP::draws) Trs = tp.between(smp, xs, sph_p(S, src), sigma_t);
+    else Trs = tp.between(xs, sph_p(S, src), sigma_t);
     const dv3 Ldp = scl(scl(p_light<COUNT>(S, smp, id, xs, nx, p.d, src, alpha), Trs), (1 / probSource));
-    const dv3 Ld = mis_v2<COUNT, -1, true, GridTr>(S, smp, id, xs, nx, p.d, alpha, sigma_t, tp);
+    const dv3 Ld = mis_v2<COUNT, -1, true, TP>(S, smp, id, xs, nx, p.d, alpha, sigma_t, tp);
     p.L = add(p.L, scl(mul(add(Ldp, Ld), p.beta), (1 / continueprob)));
     dv3 wi = mk(0, 0, 0);
     double pdf = 0;
@@ -133,15 +171,15 @@ VPT_DEV void hetero_surface(const DevScene* __restrict__ S, const GridTr& tp, Sa
 
 /* medium_event<0> (LT = -1): freeSingleScattering toward the picked light, the phase continuation; the
  * local albedo rho sigma_s / (rho sigma_t) is medium_tail's sigma_s / sigma_t */
-template <bool COUNT>
-VPT_DEV void hetero_medium(const DevScene* __restrict__ S, const GridTr& tp, Sampler<COUNT>& smp, Path& p,
+template <bool COUNT, class TP>
+VPT_DEV void hetero_medium(const DevScene* __restrict__ S, const TP& tp, Sampler<COUNT>& smp, Path& p,
                            const Event& e, const Medium& m)
 {
     const double sigma_t = m.sigma_a + m.sigma_s;
     const dv3 xt = add(p.o, scl(p.d, e.dist));
     const double probSource = 1.0 / S->n_emit;
     const bool zero_ok = p.beta.x - p.beta.x == 0 && p.beta.y - p.beta.y == 0 && p.beta.z - p.beta.z == 0;
-    const dv3 Ld = single_scattering<COUNT, -1, GridTr>(S, smp, xt, p.d, e.src, sigma_t, false, m.sigma_s, 1.0, probSource,
+    const dv3 Ld = single_scattering<COUNT, -1, TP>(S, smp, xt, p.d, e.src, sigma_t, false, m.sigma_s, 1.0, probSource,
                                                         zero_ok, tp);
     medium_tail<0, COUNT>(smp, p, Ld, 1.0, e.pdf, xt, m, true);
 }
@@ -168,15 +206,38 @@ __device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridTr&
     return p.L;
 }
 
+/* the same for estimator 11 (render_kernel_simple<11>).  Restated, not a shared template: estimator 10's function
+ * above is an out-of-line function of its kernels, and its name and code are to stay what they were */
+template <bool COUNT, bool LM = false>
+__device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridRatioTr<LM>& tp, Sampler<COUNT>& smp, dv3 o,
+                                   dv3 d, const Medium& m, HeteroStats* hs = nullptr)
+{
+    Path p;
+    p.o = o;
+    p.d = d;
+    p.beta = mk(1, 1, 1);
+    p.L = mk(0, 0, 0);
+    p.depth = 0;
+    Event e;
+    e.pdf = 0;
+    while (continue_path(smp, p, m)) {
+        const int ev = hetero_decide<COUNT, LM, GridRatioTr<LM>>(S, tp, smp, p, e, m, hs);
+        if (ev == EV_END) break;
+        if (ev == EV_SURF) hetero_surface(S, tp, smp, p, e, m);
+        else hetero_medium(S, tp, smp, p, e, m);
+    }
+    return p.L;
+}
+
 /* the three steps as the persistent-wave loop (vpt_wave.h) calls them, on the kernel's view of the grid */
-template <bool LM>
+template <bool LM, class TP = GridTr>
 struct HeteroSteps {
-    GridTr tp;
+    TP tp;
     template <bool COUNT>
     __device__ __forceinline__ int decide(const DevScene* __restrict__ S, Sampler<COUNT>& smp, Path& p, Event& e,
                                           const Medium& m) const
     {
-        return hetero_decide<COUNT, LM>(S, tp, smp, p, e, m);
+        return hetero_decide<COUNT, LM, TP>(S, tp, smp, p, e, m);
     }
     template <bool COUNT>
     __device__ __forceinline__ void surface(const DevScene* __restrict__ S, Sampler<COUNT>& smp, Path& p, const Event& e,
@@ -196,20 +257,23 @@ struct KParams;  /* a render's launch parameters (vpt_render_simple.h) */
 
 }  // namespace vpt
 
-/* vpt_hetero.hip: the persistent-wave render kernel of estimator 10, enqueued on `stream` (the caller owns
+/* vpt_hetero.hip: the persistent-wave render kernel of estimator 10 or 11 (K.est), enqueued on `stream` (the caller owns
  * the queue word K.queue and has zeroed it in stream order); lm: the grid has a majorant grid (the kernel's LM
  * instantiation) */
 int vpt_int_hetero_launch(int device, const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
-/* render_kernel_simple<10> for the same render; counting iff K.counters (vpt_count_work's device counters) is set */
+/* render_kernel_simple<10 or 11> for the same render; counting iff K.counters (vpt_count_work's device counters) is set */
 int vpt_int_hetero_simple_launch(const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
-/* the per-sample call and the grid probe on device arrays, default stream (the caller reads hipGetLastError);
- * lm: the grid behind `grid` has a majorant grid; stats: vpt_debug_hetero_steps' two counters, else NULL; steps: the
+/* the per-sample call (est: 10 or 11) and the grid probes on device arrays, default stream (the caller reads hipGetLastError);
+ * lm: the grid behind `grid` has a majorant grid; stats: vpt_debug_hetero_steps' two counters (estimator 10), else NULL; steps: the
  * probe's per-ray tentative steps, else NULL */
-void vpt_int_hetero_trace_launch(const vpt_ray* rays, const uint64_t* states, int n, const vpt::Medium& m, const DevScene* S,
-                                 const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states,
+void vpt_int_hetero_trace_launch(int est, const vpt_ray* rays, const uint64_t* states, int n, const vpt::Medium& m,
+                                 const DevScene* S, const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states,
                                  unsigned long long* stats);
 void vpt_int_grid_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays, const double* tmax,
                                const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out,
                                uint32_t* steps);
+void vpt_int_grid_ratio_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
+                                     const double* tmax, const uint64_t* states, int n, double* that, uint64_t* states_out,
+                                     uint32_t* steps);
 
 #endif

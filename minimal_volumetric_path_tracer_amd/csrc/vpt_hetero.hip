@@ -1,5 +1,6 @@
 /*
- * vpt_hetero.hip -- the render kernel of estimator 10 (VPT_HETERO_FREE, vpt_hetero.h) in a translation unit
+ * vpt_hetero.hip -- the render kernels of estimator 10 (VPT_HETERO_FREE, vpt_hetero.h) and of estimator 11
+ * (VPT_HETERO_RATIO: the same kernels on the ratio-tracking policy, chosen on the host as LM is) in a translation unit
  * of its own, as vpt_pool_mis.hip is for the north-star kernel: the hot loop here is null-collision
  * stepping through a voxel grid, latency-bound and divergent, not ray/sphere arithmetic, and the unit can
  * take compile flags of its own.
@@ -67,6 +68,40 @@ __global__ __launch_bounds__(256, 2) void hetero_kernel(KParams P, const DevScen
     wave_render<HeteroSteps<LM>, COUNT, FB>(P, S, st);
 }
 
+/* estimator 11 (VPT_HETERO_RATIO): hetero_kernel on the ratio-tracking policy.  The prologue is restated, not shared:
+ * with estimator 10's kernel calling a common body template its code moves (commuted v_mul_f64 operands, swapped
+ * v_add_f64 pairs, up to three instructions more or fewer), and that kernel is to stay what it was */
+template <bool COUNT, int FB, bool LM>
+__global__ __launch_bounds__(256, 2) void hetero_ratio_kernel(KParams P, const DevScene* __restrict__ S)
+{
+    HeteroSteps<LM, GridRatioTr<LM>> st{GridRatioTr<LM>::template load<LM>(P.grid)};
+    [[maybe_unused]] GridRatioTr<LM>& tp = st.tp;
+#if VPT_HETERO_LDS
+    __shared__ float lds_rho[VPT_HETERO_LDS_BYTES / sizeof(float)];
+    {
+        const int64_t nv = (int64_t)tp.G.n[0] * tp.G.n[1] * tp.G.n[2];
+        if (nv <= (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float))) {  /* workgroup-uniform */
+            for (int k = threadIdx.x; k < (int)nv; k += blockDim.x) lds_rho[k] = tp.G.rho[k];
+            __syncthreads();
+            tp.G.rho = lds_rho;
+        }
+#if VPT_HETERO_LDS_MAJ
+        if (LM) {  /* the majorant grid goes into what the density left of the budget */
+            const int64_t cap = (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float));
+            const int64_t used = nv <= cap ? nv : 0;
+            const int64_t nbv = (int64_t)tp.G.nb[0] * tp.G.nb[1] * tp.G.nb[2];
+            if (nbv <= cap - used) {  /* workgroup-uniform */
+                for (int k = threadIdx.x; k < (int)nbv; k += blockDim.x) lds_rho[used + k] = tp.G.maj[k];
+                __syncthreads();
+                tp.G.maj = lds_rho + used;
+            }
+        }
+#endif
+    }
+#endif
+    wave_render<HeteroSteps<LM, GridRatioTr<LM>>, COUNT, FB>(P, S, st);
+}
+
 }  // namespace vpt
 
 using namespace vpt;
@@ -98,6 +133,26 @@ __global__ __launch_bounds__(256) void trace_batch_hetero_kernel(const vpt_ray* 
     out_states[i] = smp.X;
 }
 
+/* estimator 11's per-sample call: the same on the ratio-tracking policy (no step statistics) */
+template <bool LM>
+__global__ __launch_bounds__(256) void trace_batch_hetero_ratio_kernel(const vpt_ray* __restrict__ rays,
+                                                                       const uint64_t* __restrict__ states, int n, Medium m,
+                                                                       const DevScene* __restrict__ S,
+                                                                       const vpt_grid_view* __restrict__ grid, double* out,
+                                                                       uint64_t* out_states)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Sampler<false> smp;
+    smp.X = states[i] & 0xFFFFFFFFFFFFull;
+    smp.g = m.g;
+    dv3 L = trace_hetero<false, LM>(S, GridRatioTr<LM>::template load<LM>(grid), smp, ld3(rays[i].o), ld3(rays[i].d), m);
+    out[3 * i] = L.x;
+    out[3 * i + 1] = L.y;
+    out[3 * i + 2] = L.z;
+    out_states[i] = smp.X;
+}
+
 /* the density grid's walkers (vpt_grid.h), one ray per lane (vpt_grid_probe, vpt_grid_probe_lm) */
 template <bool LM>
 __global__ __launch_bounds__(256) void grid_probe_kernel(const vpt_grid_view* __restrict__ grid, double sigma_t,
@@ -117,12 +172,38 @@ __global__ __launch_bounds__(256) void grid_probe_kernel(const vpt_grid_view* __
     if (steps) steps[i] = ns;
 }
 
+/* the ratio-tracking walkers (vpt_grid.h), one ray per lane (vpt_grid_ratio_probe) */
+template <bool LM>
+__global__ __launch_bounds__(256) void grid_ratio_probe_kernel(const vpt_grid_view* __restrict__ grid, double sigma_t,
+                                                               const vpt_ray* __restrict__ rays, const double* __restrict__ tmax,
+                                                               const uint64_t* __restrict__ states, int n, double* that,
+                                                               uint64_t* states_out, uint32_t* steps)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const vpt_grid_view G = *grid;
+    const double o[3] = {rays[i].o[0], rays[i].o[1], rays[i].o[2]}, d[3] = {rays[i].d[0], rays[i].d[1], rays[i].d[2]};
+    uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
+    uint32_t ns = 0;
+    that[i] = LM ? vpt_grid_ratio_lm(&G, o, d, tmax[i], sigma_t, &X, &ns) : vpt_grid_ratio(&G, o, d, tmax[i], sigma_t, &X, &ns);
+    states_out[i] = X;
+    if (steps) steps[i] = ns;
+}
+
 }  // namespace
 
-void vpt_int_hetero_trace_launch(const vpt_ray* rays, const uint64_t* states, int n, const Medium& m, const DevScene* S,
-                                 const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states,
+/* estimator 11's launches stand at the end of the unit (below): the kernels are instantiated in the order of their
+ * first use, and estimator 10's keep the places -- and with them the label numbers -- they had */
+static void ratio_trace_launch(const vpt_ray* rays, const uint64_t* states, int n, const Medium& m, const DevScene* S,
+                               const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states);
+static int ratio_simple_launch(const KParams& K, const DevScene* S, bool lm, void* stream);
+static int ratio_launch(int device, const KParams& K, const DevScene* S, bool lm, void* stream);
+
+void vpt_int_hetero_trace_launch(int est, const vpt_ray* rays, const uint64_t* states, int n, const Medium& m,
+                                 const DevScene* S, const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states,
                                  unsigned long long* stats)
 {
+    if (est == VPT_HETERO_RATIO) return ratio_trace_launch(rays, states, n, m, S, grid, lm, out, out_states);
     const dim3 g((unsigned)((n + 255) / 256)), b(256);
     if (lm) trace_batch_hetero_kernel<true><<<g, b>>>(rays, states, n, m, S, grid, out, out_states, stats);
     else trace_batch_hetero_kernel<false><<<g, b>>>(rays, states, n, m, S, grid, out, out_states, stats);
@@ -149,35 +230,81 @@ static int with_flags(F f, bool flag, Bools... rest)
     return with_flags([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
 }
 
-/* render_kernel_simple<10> (vpt_render_simple.h): counting mode (K.counters != NULL) and VPT_SIMPLE_KERNEL=1 */
-int vpt_int_hetero_simple_launch(const KParams& K, const DevScene* S, bool lm, void* stream)
+/* render_kernel_simple<EST> (vpt_render_simple.h): counting mode (K.counters != NULL) and VPT_SIMPLE_KERNEL=1 */
+template <int EST>
+static int simple_launch(const KParams& K, const DevScene* S, bool lm, void* stream)
 {
     return with_flags([&](auto lmc, auto count, auto f32) {
         constexpr int FB = decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64;
         dim3 grid((unsigned)((K.w + 15) / 16), (unsigned)((K.shard_rows + 15) / 16));
-        render_kernel_simple<VPT_HETERO_FREE, decltype(count)::value, FB, decltype(lmc)::value><<<grid, dim3(256), 0, (hipStream_t)stream>>>(K, S);
+        render_kernel_simple<EST, decltype(count)::value, FB, decltype(lmc)::value><<<grid, dim3(256), 0, (hipStream_t)stream>>>(K, S);
         const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "render_kernel_simple<10> launch: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "render_kernel_simple<%d> launch: %s", EST, hipGetErrorString(e));
         return (int)VPT_OK;
     }, lm, K.counters != nullptr, K.fb == VPT_FB_F32);
 }
 
+int vpt_int_hetero_simple_launch(const KParams& K, const DevScene* S, bool lm, void* stream)
+{
+    if (K.est == VPT_HETERO_RATIO) return ratio_simple_launch(K, S, lm, stream);
+    return simple_launch<VPT_HETERO_FREE>(K, S, lm, stream);
+}
+
+/* a persistent-wave kernel on as many workgroups as the device holds, at most one per four tiles */
+static int persistent_launch(void (*kern)(KParams, const DevScene*), int device, const KParams& K, const DevScene* S,
+                             void* stream)
+{
+    int per_cu = 0, cus = 0;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_kernel: %s", hipGetErrorString(e));
+    int blocks = (per_cu < 1 ? 1 : per_cu) * cus;
+    const int tiles = K.tiles_x * K.tiles_y;
+    const int need = (tiles + 3) / 4;  /* 4 waves per block, one tile per wave to start */
+    if (blocks > need) blocks = need;
+    if (blocks < 1) blocks = 1;
+    kern<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(K, S);
+    e = hipGetLastError();
+    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_kernel launch: %s", hipGetErrorString(e));
+    return (int)VPT_OK;
+}
+
 int vpt_int_hetero_launch(int device, const KParams& K, const DevScene* S, bool lm, void* stream)
 {
+    if (K.est == VPT_HETERO_RATIO) return ratio_launch(device, K, S, lm, stream);
     return with_flags([&](auto lmc, auto f32) {
-        const auto kern = hetero_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value>;
-        int per_cu = 0, cus = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-        if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_kernel: %s", hipGetErrorString(e));
-        int blocks = (per_cu < 1 ? 1 : per_cu) * cus;
-        const int tiles = K.tiles_x * K.tiles_y;
-        const int need = (tiles + 3) / 4;  /* 4 waves per block, one tile per wave to start */
-        if (blocks > need) blocks = need;
-        if (blocks < 1) blocks = 1;
-        kern<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(K, S);
-        e = hipGetLastError();
-        if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_kernel launch: %s", hipGetErrorString(e));
-        return (int)VPT_OK;
+        return persistent_launch(hetero_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value>,
+                                 device, K, S, stream);
+    }, lm, K.fb == VPT_FB_F32);
+}
+
+/* ---- estimator 11 ---- */
+static void ratio_trace_launch(const vpt_ray* rays, const uint64_t* states, int n, const Medium& m, const DevScene* S,
+                               const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states)
+{
+    const dim3 g((unsigned)((n + 255) / 256)), b(256);
+    if (lm) trace_batch_hetero_ratio_kernel<true><<<g, b>>>(rays, states, n, m, S, grid, out, out_states);
+    else trace_batch_hetero_ratio_kernel<false><<<g, b>>>(rays, states, n, m, S, grid, out, out_states);
+}
+
+void vpt_int_grid_ratio_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
+                                     const double* tmax, const uint64_t* states, int n, double* that, uint64_t* states_out,
+                                     uint32_t* steps)
+{
+    const dim3 g((unsigned)((n + 255) / 256)), b(256);
+    if (lm) grid_ratio_probe_kernel<true><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, that, states_out, steps);
+    else grid_ratio_probe_kernel<false><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, that, states_out, steps);
+}
+
+static int ratio_simple_launch(const KParams& K, const DevScene* S, bool lm, void* stream)
+{
+    return simple_launch<VPT_HETERO_RATIO>(K, S, lm, stream);
+}
+
+static int ratio_launch(int device, const KParams& K, const DevScene* S, bool lm, void* stream)
+{
+    return with_flags([&](auto lmc, auto f32) {
+        return persistent_launch(hetero_ratio_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value>,
+                                 device, K, S, stream);
     }, lm, K.fb == VPT_FB_F32);
 }

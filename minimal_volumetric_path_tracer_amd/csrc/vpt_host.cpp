@@ -239,6 +239,38 @@ int vpt_grid_probe_host_lm(const vpt_grid_desc* desc, const float* density, int 
     return VPT_OK;
 }
 
+int vpt_grid_ratio_probe_host(const vpt_grid_desc* desc, const float* density, int block, double sigma_t,
+                              const vpt_ray* rays, const double* tmax, const uint64_t* states, int n, double* that,
+                              uint64_t* states_out, uint32_t* steps)
+{
+    vpt_clear_error();
+    if (!rays || !tmax || !states || n < 0) return vpt_fail(VPT_E_INVALID, "vpt_grid_ratio_probe_host: bad arguments");
+    if (block < 0) return vpt_fail(VPT_E_INVALID, "vpt_grid_ratio_probe_host: block %d (0 = the global majorant, else >= 1)", block);
+    int rc = vpt_int_grid_check(desc, density, "vpt_grid_ratio_probe_host");
+    if (rc) return rc;
+    const int32_t dims[3] = {desc->nx, desc->ny, desc->nz};
+    vpt_grid_view G;
+    vpt_grid_view_init(&G, dims, desc->lo, desc->hi, density, density);
+    std::vector<float> maj;
+    if (block) {
+        int32_t nb[3];
+        vpt_grid_majorant_counts(dims, block, nb);
+        maj.resize((size_t)nb[0] * (size_t)nb[1] * (size_t)nb[2]);
+        vpt_grid_majorant_build(dims, block, density, maj.data());
+        vpt_grid_view_set_majorant(&G, block, maj.data());
+    }
+    for (int i = 0; i < n; ++i) {
+        uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
+        uint32_t ns = 0;
+        const double T = block ? vpt_grid_ratio_lm(&G, rays[i].o, rays[i].d, tmax[i], sigma_t, &X, &ns)
+                               : vpt_grid_ratio(&G, rays[i].o, rays[i].d, tmax[i], sigma_t, &X, &ns);
+        if (that) that[i] = T;
+        if (states_out) states_out[i] = X;
+        if (steps) steps[i] = ns;
+    }
+    return VPT_OK;
+}
+
 /* ---- PPM ---- */
 static inline double clamp01(double x) { return x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x); }
 static inline int to_display(double x) { return (int)(pow(clamp01(x), 1.0 / 2.2) * 255 + .5); }

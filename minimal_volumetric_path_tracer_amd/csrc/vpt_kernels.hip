@@ -305,7 +305,7 @@ static int check_medium(const vpt_medium* m)
  * (include/rayMarchingMethods.h:64,153), so the scene needs at least 6 spheres */
 static int check_march(const vpt_context* ctx, const vpt_medium* m)
 {
-    if (m->estimator == VPT_HETERO_FREE) {
+    if (m->estimator == VPT_HETERO_FREE || m->estimator == VPT_HETERO_RATIO) {
         if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "estimator %d needs a density grid (vpt_set_density_grid)", m->estimator);
         return VPT_OK;
     }
@@ -451,8 +451,8 @@ static bool hetero_simple_kernel()
     return v && *v && atoi(v) != 0;
 }
 
-/* estimator 10 (vpt_hetero.hip): hetero_kernel on the stream's queue word; counting mode and
- * VPT_SIMPLE_KERNEL=1: render_kernel_simple<10> */
+/* estimators 10 and 11 (vpt_hetero.hip, by K.est): hetero_kernel / hetero_ratio_kernel on the stream's queue word;
+ * counting mode and VPT_SIMPLE_KERNEL=1: render_kernel_simple<10 or 11> */
 static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
 {
     const bool lm = ctx->h_grid.block > 0;
@@ -471,7 +471,7 @@ static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
 template <int EST, bool COUNT, int FB>
 static int launch_one(vpt_context* ctx, KParams K, hipStream_t stream)
 {
-    if constexpr (EST == VPT_HETERO_FREE) {  /* its kernels live in vpt_hetero.hip */
+    if constexpr (EST == VPT_HETERO_FREE || EST == VPT_HETERO_RATIO) {  /* their kernels live in vpt_hetero.hip */
         return launch_hetero(ctx, K, stream);
     } else {
         const DevScene* S = ctx->d_scene;
@@ -673,6 +673,7 @@ static int launch_render(vpt_context* ctx, KParams K, hipStream_t stream)
         VPT_LAUNCH_EST(8)
         VPT_LAUNCH_EST(9)
         VPT_LAUNCH_EST(10)
+        VPT_LAUNCH_EST(11)
     }
 #undef VPT_LAUNCH_EST
     return vpt_fail(VPT_E_INVALID, "unknown estimator %d", K.est);
@@ -982,6 +983,46 @@ int vpt_grid_probe_lm(vpt_context* ctx, double sigma_t, const vpt_ray* rays, con
     return grid_probe(ctx, true, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, steps);
 }
 
+int vpt_grid_ratio_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax,
+                         const uint64_t* states, int n, double* that, uint64_t* states_out, uint32_t* steps)
+{
+    vpt_clear_error();
+    if (!ctx || !rays || !tmax || !states || !that || !states_out || n < 0)
+        return vpt_fail(VPT_E_INVALID, "vpt_grid_ratio_probe: bad arguments");
+    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "vpt_grid_ratio_probe: no density grid set (vpt_set_density_grid)");
+    if (n == 0) return VPT_OK;
+    HIP_OK(hipSetDevice(ctx->device));
+    uint32_t* dst = nullptr;
+    vpt_ray* dr = nullptr;
+    uint64_t *ds = nullptr, *dso = nullptr;
+    double *dtm = nullptr, *dth = nullptr;
+    const size_t nn = (size_t)n;
+    hipError_t e = hipMalloc((void**)&dr, sizeof(vpt_ray) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&ds, sizeof(uint64_t) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&dso, sizeof(uint64_t) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&dtm, sizeof(double) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&dth, sizeof(double) * nn);
+    if (e == hipSuccess && steps) e = hipMalloc((void**)&dst, sizeof(uint32_t) * nn);
+    if (e == hipSuccess) e = hipMemcpy(dr, rays, sizeof(vpt_ray) * nn, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ds, states, sizeof(uint64_t) * nn, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dtm, tmax, sizeof(double) * nn, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        vpt_int_grid_ratio_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, sigma_t, dr, dtm, ds, n, dth, dso, dst);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(that, dth, sizeof(double) * nn, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(states_out, dso, sizeof(uint64_t) * nn, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && steps) e = hipMemcpy(steps, dst, sizeof(uint32_t) * nn, hipMemcpyDeviceToHost);
+    if (dst) (void)hipFree(dst);
+    (void)hipFree(dr);
+    (void)hipFree(ds);
+    (void)hipFree(dso);
+    (void)hipFree(dtm);
+    (void)hipFree(dth);
+    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "vpt_grid_ratio_probe: %s", hipGetErrorString(e));
+    return VPT_OK;
+}
+
 int vpt_render_device(vpt_context* ctx, const vpt_params* p, void* d_out, void* stream)
 {
     vpt_clear_error();
@@ -1093,7 +1134,8 @@ static int trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* ray
         case 6: trace_batch_kernel<6><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         case 7: trace_batch_kernel<7><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         case 8: trace_batch_kernel<8><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
-        case VPT_HETERO_FREE: vpt_int_hetero_trace_launch(dr, ds, n, mm, ctx->d_scene, ctx->d_grid, ctx->h_grid.block > 0, dout, dso, stats); break;
+        case VPT_HETERO_FREE:
+        case VPT_HETERO_RATIO: vpt_int_hetero_trace_launch(m->estimator, dr, ds, n, mm, ctx->d_scene, ctx->d_grid, ctx->h_grid.block > 0, dout, dso, stats); break;
         default: trace_batch_kernel<9><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         }
         e = hipGetLastError();

@@ -31,7 +31,7 @@ struct KParams {
     int32_t cost_surf, cost_med;   /* event scheduler weights */
     int32_t chunk;                 /* samples per partial sum (pool kernel) */
     int32_t taper;                 /* tapered chunk layout (auto mode, vpt_chunks.h) */
-    const vpt_grid_view* grid;     /* estimator 10: the context's density grid (device), else NULL */
+    const vpt_grid_view* grid;     /* estimators 10, 11: the context's density grid (device), else NULL */
 };
 
 __host__ __device__ __forceinline__ Medium medium_of(const KParams& P)
@@ -89,7 +89,7 @@ namespace {
 
 using namespace vpt;
 
-/* LM: estimator 10 only -- the grid has a majorant grid (vpt_hetero.h) */
+/* LM: estimators 10 and 11 only -- the grid has a majorant grid (vpt_hetero.h) */
 template <int EST, bool COUNT, int FB, bool LM = false>
 __global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const DevScene* __restrict__ S)
 {
@@ -119,6 +119,8 @@ __global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const Dev
         const dv3 dir = camera_dir(P, smp, x, row.y);
         dv3 L;
         if constexpr (EST == VPT_HETERO_FREE) L = trace_hetero<COUNT, LM>(S, GridTr::load<LM>(P.grid), smp, o, dir, m);
+        else if constexpr (EST == VPT_HETERO_RATIO)
+            L = trace_hetero<COUNT, LM>(S, GridRatioTr<LM>::template load<LM>(P.grid), smp, o, dir, m);
         else L = trace_sample<EST, COUNT>(S, smp, o, dir, m, EST == 6 ? march_oc : nullptr);
         acc = add(L, acc);
         if (COUNT) {

@@ -23,7 +23,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (EXPLICIT_EQUIANGULAR, EXPLICIT_FREE, FB_F32, FB_F64, FREE_FLIGHT, HETERO_FREE, IMPLICIT_FREE, MIS_EQUIANGULAR,
+from ._lib import (EXPLICIT_EQUIANGULAR, EXPLICIT_FREE, FB_F32, FB_F64, FREE_FLIGHT, HETERO_FREE, HETERO_RATIO, IMPLICIT_FREE, MIS_EQUIANGULAR,
                    RAY_DTYPE, RAY_MARCHING, RAY_MARCHING_EXPLICIT, RAY_MARCHING_GLOBAL, RAY_MARCHING_SA, SPHERE_DTYPE,
                    SURFACE_PT, check, lib)
 
@@ -31,7 +31,8 @@ ESTIMATORS = {"ff": FREE_FLIGHT, "free_flight": FREE_FLIGHT, "mis": MIS_EQUIANGU
               "explicit_free": EXPLICIT_FREE, "implicit_free": IMPLICIT_FREE, "explicit": EXPLICIT_EQUIANGULAR,
               "explicit_equiangular": EXPLICIT_EQUIANGULAR, "surface_pt": SURFACE_PT, "path_tracer": SURFACE_PT,
               "ray_marching": RAY_MARCHING, "ray_marching_sa": RAY_MARCHING_SA, "ray_marching_global": RAY_MARCHING_GLOBAL,
-              "ray_marching_explicit": RAY_MARCHING_EXPLICIT, "hetero": HETERO_FREE, "hetero_free": HETERO_FREE}
+              "ray_marching_explicit": RAY_MARCHING_EXPLICIT, "hetero": HETERO_FREE, "hetero_free": HETERO_FREE,
+              "hetero_ratio": HETERO_RATIO}
 
 
 def Sphere(r, p, c=(0, 0, 0), radiance=(0, 0, 0), material=0, eta=(0, 0, 0), kappa=(0, 0, 0), alpha=0.0) -> np.ndarray:
@@ -102,6 +103,20 @@ def grid_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, states, majorant_bl
                                        t.ctypes.data, s.ctypes.data, len(ry), tau.ctypes.data, tc.ctypes.data,
                                        so.ctypes.data, steps.ctypes.data))
     return (tau, tc, so, steps) if return_steps else (tau, tc, so)
+
+
+def grid_ratio_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, states, majorant_block: int = 0):
+    """csrc/vpt_grid.h's ratio tracking on the host (vpt_grid_ratio_probe_host, no GPU): per ray (unit direction)
+    the estimate That of exp(-sigma_t tau) over t in [0, tmax] from `states` (NaN: step cap), the erand48 states
+    after it and its draws.  majorant_block > 0 walks with local majorants on super-voxels of that many voxels
+    per axis."""
+    d, r = _grid_args(rho, lo, hi)
+    ry, t, s, that, _, so = _probe_args(rays, tmax, states)
+    steps = np.zeros(len(ry), dtype=np.uint32)
+    check(lib().vpt_grid_ratio_probe_host(byref(d), r.ctypes.data, int(majorant_block), float(sigma_t), ry.ctypes.data,
+                                          t.ctypes.data, s.ctypes.data, len(ry), that.ctypes.data, so.ctypes.data,
+                                          steps.ctypes.data))
+    return that, so, steps
 
 
 def _set_grid_with_block(owner, block, upload) -> None:
@@ -210,6 +225,15 @@ class Tracer:
         check(lib().vpt_grid_probe_lm(self._ctx, float(sigma_t), ry.ctypes.data, t.ctypes.data, s.ctypes.data, len(ry),
                                       tau.ctypes.data, tc.ctypes.data, so.ctypes.data, steps.ctypes.data))
         return (tau, tc, so, steps) if return_steps else (tau, tc, so)
+
+    def grid_ratio_probe(self, sigma_t: float, rays, tmax, states):
+        """grid_ratio_probe_host's quantities for the tracer's grid and its majorant block, computed on the GPU
+        (vpt_grid_ratio_probe)."""
+        ry, t, s, that, _, so = _probe_args(rays, tmax, states)
+        steps = np.zeros(len(ry), dtype=np.uint32)
+        check(lib().vpt_grid_ratio_probe(self._ctx, float(sigma_t), ry.ctypes.data, t.ctypes.data, s.ctypes.data, len(ry),
+                                         that.ctypes.data, so.ctypes.data, steps.ctypes.data))
+        return that, so, steps
 
     # ---- main()'s pixel loop (src/rt.cpp:767-805) ----
     def render(self, cfg: Optional[RenderConfig] = None, **kw) -> np.ndarray:
