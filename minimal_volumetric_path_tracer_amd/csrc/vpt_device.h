@@ -66,7 +66,7 @@ enum {
     SECT_SCHED = 0, SECT_LOAD, SECT_S_PLIGHT, SECT_S_MIS, SECT_S_MIS_ISECT, SECT_S_BDSF, SECT_M_SS, SECT_M_SS_DIR,
     SECT_M_SS_ISECT, SECT_M_SS_SHADOW, SECT_M_PHASE, SECT_CONT, SECT_A_PREP, SECT_A_DECIDE, SECT_A_ISECT, SECT_STORE,
     SECT_S_TOTAL, SECT_M_TOTAL, SECT_A_CAMERA, SECT_A_DECIDE_IN, SECT_M_SHADOW_IN, SECT_A_CAMERA_IN, SECT_M_EQA,
-    SECT_M_TR, SECT_A_UNIT, SECT_A_R2, SECT_USED,
+    SECT_M_TR, SECT_A_UNIT, SECT_A_R2, SECT_A_PICK, SECT_A_LOG, SECT_A_CLASS, SECT_A_ALLFRESH, SECT_USED,
     SECT_N = 32
 };
 #if VPT_SECTIONS
@@ -307,9 +307,13 @@ VPT_DEV int scene_intersect(const DevScene* __restrict__ S, Sampler<COUNT>& smp,
 /* scene_intersect (skip3 = false) with the spheres taken G at a time: the G dependency chains
  * up to det are formed first (independent, so they overlap), then the G square-root blocks and
  * the tmin updates in index order -- the same operations per sphere, the same result. */
-template <int G, bool COUNT, bool ZR = false>
+/* cam (wave-uniform; false at every site but the pool's decide()): every active lane's ray leaves the launch's
+ * camera origin, and (o - centre, |o - centre|^2) of sphere i comes from cam_oc[i][0..3] (vpt_cam_table: formed
+ * once per launch with the operations below) through scalar loads -- per sphere only b and det are formed; the
+ * roots and the nearest-contact updates are the one copy both kinds of batch run. */
+template <int G, bool COUNT, bool ZR = false, class TAB = const double (*)[4]>
 VPT_DEV int scene_intersect_grouped(const DevScene* __restrict__ S, Sampler<COUNT>& smp, dv3 o, dv3 d, double& t,
-                                    int& id)
+                                    int& id, bool cam = false, TAB cam_oc = nullptr)
 {
     static_assert(G >= 1, "spheres are taken G >= 1 at a time");
     double tmin = VPT_DBL_MAX;
@@ -318,20 +322,29 @@ VPT_DEV int scene_intersect_grouped(const DevScene* __restrict__ S, Sampler<COUN
     int i = 0;
     for (; i + G <= n; i += G) {
         double b[G], det[G];
+        if (cam) {
 #pragma unroll
-        for (int k = 0; k < G; ++k) {
-            const GeoSphere g = S->geo[i + k];
-            const double ocx = o.x - g.px, ocy = o.y - g.py, ocz = o.z - g.pz;
-            b[k] = ocx * d.x + ocy * d.y + ocz * d.z;
-            const double cc = ocx * ocx + ocy * ocy + ocz * ocz;
-            det[k] = b[k] * b[k] - cc + g.r2;
+            for (int k = 0; k < G; ++k) {
+                const double ocx = cam_oc[i + k][0], ocy = cam_oc[i + k][1], ocz = cam_oc[i + k][2], cc = cam_oc[i + k][3];
+                b[k] = ocx * d.x + ocy * d.y + ocz * d.z;
+                det[k] = b[k] * b[k] - cc + S->geo[i + k].r2;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < G; ++k) {
+                const GeoSphere g = S->geo[i + k];
+                const double ocx = o.x - g.px, ocy = o.y - g.py, ocz = o.z - g.pz;
+                b[k] = ocx * d.x + ocy * d.y + ocz * d.z;
+                const double cc = ocx * ocx + ocy * ocy + ocz * ocz;
+                det[k] = b[k] * b[k] - cc + g.r2;
+            }
         }
 #pragma unroll
         for (int k = 0; k < G; ++k) {
             sphere_test<ZR>(b[k], det[k], i + k, tmin, id, contact);
         }
     }
-    for (; i < n; ++i) {
+    for (; i < n; ++i) {  /* (the camera table is not worth a second copy of the remainder loop) */
         const GeoSphere g = S->geo[i];
         const double ocx = o.x - g.px, ocy = o.y - g.py, ocz = o.z - g.pz;
         const double b = ocx * d.x + ocy * d.y + ocz * d.z;
@@ -1674,12 +1687,34 @@ VPT_DEV constexpr bool est_free_flight() { return EST == 0 || EST == 2 || EST ==
 
 /* vptShadeMethods.h:1284-1307 (FF), :1357-1426 (MIS), :1166-1205 (explicit free), :950-977
  * (implicit free), :1031-1096 (explicit): what happens to the path this iteration. */
-template <int EST, bool COUNT>
-VPT_DEV int decide(const DevScene* __restrict__ S, Sampler<COUNT>& smp, Path& p, Event& e, const Medium& m)
+/* HOIST (the pool's stage A, free-flight estimators 0 and 2): the light-pick and free-flight draws are taken
+ * before the cast -- the cast draws nothing, so they keep their places in the stream -- and what the tail
+ * waits for is issued there: the emit[] entry and the log's table pair (gm_log_pair_of); both are consumed
+ * after the sphere loop, which covers their latency.  m_emitter: the caller's copy of S->m_emitter, loaded
+ * with the scene's other flag words in one batch before the call.
+ * cam, cam_oc: scene_intersect_grouped's (an all-fresh batch of the pool and the launch's camera table).
+ * A/B on the pool kernel: DESIGN section 4 and profiles/decide_hoist/bench_ab.log (the hoist pays only together
+ * with the table).  The one-lane and persistent-wave kernels keep the reference's order (HOIST = false: their
+ * lanes hold a whole path in registers across the cast). */
+template <int EST, bool COUNT, bool HOIST = false, class TAB = const double (*)[4]>
+VPT_DEV int decide(const DevScene* __restrict__ S, Sampler<COUNT>& smp, Path& p, Event& e, const Medium& m,
+                   bool cam = false, TAB cam_oc = nullptr, uint64_t m_emitter = 0)
 {
+    constexpr bool hoist = HOIST && (EST == 0 || EST == 2);
     const double sigma_t = m.sigma_a + m.sigma_s;
     int id = 0;
     double t = 0.0;
+    int h_count = 0, h_src = 0;
+    double h_x = 0;
+    gm_log_pair h_lp = {0, 0};
+    if constexpr (hoist) {
+        h_count = S->n_emit;
+        if (VPT_LIKELY(h_count != 0)) {
+            h_src = emit_pick(S, (int)(smp.next() * h_count), h_count);
+            h_x = 1 - smp.next();
+            h_lp = gm_log_pair_of(h_x);
+        }
+    }
     SECT_BEGIN(di);
 #if VPT_DUP == DUP_DECIDE_ISECT
     {
@@ -1694,7 +1729,7 @@ VPT_DEV int decide(const DevScene* __restrict__ S, Sampler<COUNT>& smp, Path& p,
         vpt_sink(h2);
     }
 #endif
-    const bool hit = scene_intersect_grouped<VPT_DECIDE_GROUP>(S, smp, p.o, p.d, t, id);
+    const bool hit = scene_intersect_grouped<VPT_DECIDE_GROUP>(S, smp, p.o, p.d, t, id, cam, cam_oc);
     SECT_END(di, SECT_A_ISECT);
     if constexpr (EST == 5) {  /* iterativePathTracer (shadeMethods.h:115-125): nearest hit or end */
         if (COUNT) smp.cnt.iterations++;
@@ -1723,12 +1758,19 @@ VPT_DEV int decide(const DevScene* __restrict__ S, Sampler<COUNT>& smp, Path& p,
         }
         return EV_SURF;
     }
-    const int count = S->n_emit;
+    SECT_BEGIN(pk);
+    const int count = hoist ? h_count : S->n_emit;
     if (VPT_UNLIKELY(count == 0)) return EV_END;
-    e.src = emit_pick(S, (int)(smp.next() * count), count);
+    if constexpr (hoist) e.src = h_src;
+    else e.src = emit_pick(S, (int)(smp.next() * count), count);
+    SECT_END(pk, SECT_A_PICK);
     bool surf;
     if (est_free_flight<EST>()) {
-        e.dist = -lm_log(1 - smp.next()) / sigma_t;  /* freeFlightSample, vptSamplingFunctions.h:11-14 */
+        SECT_BEGIN(lg);
+        /* freeFlightSample, vptSamplingFunctions.h:11-14 (lm_log is gm_log = gm_log_finish of gm_log_pair_of) */
+        if constexpr (hoist) e.dist = -gm_log_finish(h_x, h_lp) / sigma_t;
+        else e.dist = -lm_log(1 - smp.next()) / sigma_t;
+        SECT_END(lg, SECT_A_LOG);
         surf = e.dist > t;
     } else {
         /* MIS: psurf = exp(-σt t) (:1419); explicit: TrActual = Tr(x, xs), 0 on a miss (:1033-1041) */
@@ -1739,7 +1781,7 @@ VPT_DEV int decide(const DevScene* __restrict__ S, Sampler<COUNT>& smp, Path& p,
         surf = EST == 1 ? smp.next() < psurf : smp.next() <= psurf;  /* :1423 / :1096 */
     }
     if (!surf) return EV_MED;
-    if (sph_flag(S->m_emitter, id)) {  /* the path ends on a light; only a camera ray sees it */
+    if (sph_flag(hoist ? m_emitter : S->m_emitter, id)) {  /* the path ends on a light; only a camera ray sees it */
         if (p.depth == 0) p.L = EST == 0 ? mul(sph_rad(S, id), p.beta) : sph_rad(S, id);
         return EV_END;
     }

@@ -413,7 +413,25 @@ VM_QUAL double gm_exp(double x)
     return v;
 }
 
-VM_QUAL double gm_log(double x)
+/* gm_log in two halves, for a caller that has other work between the table pair's loads and their use (decide(),
+ * vpt_device.h): gm_log_pair_of(x) forms the table index and loads (invc, logc); gm_log_finish(x, pair) is
+ * everything else -- both common paths, their select and the rare-argument call.  gm_log(x) is
+ * gm_log_finish(x, gm_log_pair_of(x)): one statement of the arithmetic, the same bits either way. */
+typedef struct {
+    double invc, logc;
+} gm_log_pair;
+
+VM_QUAL gm_log_pair gm_log_pair_of(double x)
+{
+    const uint64_t tmp = vm_as_u64(x) + 0xc01a000000000000ull;
+    const uint32_t i = (uint32_t)(tmp >> 45) & 0x7fu;
+    gm_log_pair t;
+    t.invc = vm_as_f64(GM_LOG_T(2 * i));
+    t.logc = vm_as_f64(GM_LOG_T(2 * i + 1));
+    return t;
+}
+
+VM_QUAL double gm_log_finish(double x, gm_log_pair t)
 {
     vm_ct* K = vm_tab(gm_log_tab);
     const uint64_t ix = vm_as_u64(x);
@@ -442,11 +460,10 @@ VM_QUAL double gm_log(double x)
     v1 = ix == 0x3ff0000000000000ull ? 0.0 : v1;
     /* table path: x = 2^k z, z near 1/invc, log x = k ln2 + logc + log(z invc) */
     const uint64_t tmp = ix + 0xc01a000000000000ull;
-    const uint32_t i = (uint32_t)(tmp >> 45) & 0x7fu;
     const int k = (int)((int64_t)tmp >> 52);
     const double zz = vm_as_f64(ix - (tmp & 0xfff0000000000000ull));
     const double kd = (double)k;
-    const double invc = vm_as_f64(GM_LOG_T(2 * i)), logc = vm_as_f64(GM_LOG_T(2 * i + 1));
+    const double invc = t.invc, logc = t.logc;
     const double r = gm_fma(zz, invc, -1.0);
     const double w = gm_fma(kd, VM_T(K, GL_LN2HI), logc);
     const double hi = r + w;
@@ -460,6 +477,8 @@ VM_QUAL double gm_log(double x)
     VM_RARE_FIX(top - 0x0010u >= 0x7ff0u - 0x0010u, v, gl_log(x));
     return v;
 }
+
+VM_QUAL double gm_log(double x) { return gm_log_finish(x, gm_log_pair_of(x)); }
 
 /* ------------------------------------------------------------------ atan2 (e_atan2.c)
  * glibc 2.35's __ieee754_atan2, FMA build, for x > 0: atan(|y|/x) (|y| < x) or pi/2 - atan(x/|y|)

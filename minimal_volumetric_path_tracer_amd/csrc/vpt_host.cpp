@@ -53,7 +53,30 @@ int vpt_int_grid_check(const vpt_grid_desc* desc, const float* density, const ch
     return VPT_OK;
 }
 
+/* The pool kernel's camera table (PoolParams::cam_oc): oc = o - centre and |oc|^2 of n spheres whose centres
+ * are `stride` doubles apart, with the operations and the order of Sphere::intersect (include/Sphere.h:28-30;
+ * scene_intersect_grouped's first loop, march_origin_init on the device).  This unit is compiled with
+ * -ffp-contract=off: every product and sum below is rounded on its own, as on the device. */
+void vpt_int_cam_table(const double* o, const double* centre, size_t stride, int n, double (*oc)[4])
+{
+    for (int i = 0; i < n; ++i, centre += stride) {
+        const double ocx = o[0] - centre[0], ocy = o[1] - centre[1], ocz = o[2] - centre[2];
+        oc[i][0] = ocx;
+        oc[i][1] = ocy;
+        oc[i][2] = ocz;
+        oc[i][3] = ocx * ocx + ocy * ocy + ocz * ocz;
+    }
+}
+
 extern "C" {
+
+/* debug: vpt_int_cam_table for a scene's spheres and a camera origin; out holds 4 n doubles */
+int vpt_debug_cam_table(const vpt_sphere* spheres, int n, const double* o, double* out)
+{
+    if (!spheres || !o || !out || n < 0 || n > VPT_MAX_SPHERES) return vpt_fail(VPT_E_INVALID, "vpt_debug_cam_table: bad arguments");
+    vpt_int_cam_table(o, spheres[0].p, sizeof(vpt_sphere) / sizeof(double), n, (double (*)[4])out);
+    return VPT_OK;
+}
 
 const char* vpt_last_error(void) { return g_err.c_str(); }
 int vpt_abi_version(void) { return VPT_ABI_VERSION; }

@@ -2,6 +2,8 @@
 #ifndef VPT_INTERNAL_H
 #define VPT_INTERNAL_H
 
+#include <stddef.h>
+
 #include "../../include/vpt.h"
 
 /* records a thread-local message for vpt_last_error() and returns `code` */
@@ -15,6 +17,10 @@ int vpt_int_check_guard(vpt_context* ctx, const char* who);   /* after a synchro
 int vpt_int_check_params(const vpt_context* ctx, const vpt_params* p);  /* build_kparams' validation */
 int vpt_int_pool_pass(vpt_context* ctx, const vpt_params* p, int C, int k0, int k1, const unsigned* d_tiles,
                       unsigned n_tiles, double* d_partials, unsigned* d_queue);
+
+/* the pool kernel's camera table for origin o: (o - centre, |o - centre|^2) of n spheres, centres `stride`
+ * doubles apart (vpt_host.cpp) */
+void vpt_int_cam_table(const double* o, const double* centre, size_t stride, int n, double (*oc)[4]);
 
 /* vpt_grid_bad's verdict on a grid as a vpt_status with its message (vpt_host.cpp) */
 int vpt_int_grid_check(const vpt_grid_desc* desc, const float* density, const char* who);

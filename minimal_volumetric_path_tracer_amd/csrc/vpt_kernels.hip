@@ -164,6 +164,13 @@ __global__ void math_probe_kernel(int fn, const double* x, const double* y, doub
     }
     case 21: r = vm_sqrt_isect(a); break;    /* the sphere tests' root (VPT_ISECT_CLASS) */
     case 22: r = vm_sqrt_isect_z(a); break;  /* the shadow rays' (VPT_ISECT_ZERO) */
+    case 23: {  /* log in two halves as decide() takes it: the table pair loaded, other work, then the rest */
+        gm_log_pair lp = gm_log_pair_of(a);
+        vpt_opaque(lp.invc);
+        vpt_opaque(lp.logc);
+        r = gm_log_finish(a, lp);
+        break;
+    }
     default: r = a / b; break;
     }
     out[i] = r;
@@ -550,6 +557,9 @@ static int pool_enqueue(vpt_context* ctx, const KParams& K, PoolParams& Q, uint6
     Q.queue = queue;
     Q.guard = ctx->d_guard;
     Q.guard_bias = ctx->guard_bias;
+    /* this launch's camera and this context's scene: every render, accumulator pass and rank comes through here */
+    memset(Q.cam_oc, 0, sizeof Q.cam_oc);
+    vpt_int_cam_table(K.o, &ctx->h_scene.geo[0].px, sizeof(GeoSphere) / sizeof(double), ctx->h_scene.n, Q.cam_oc);
     const Medium m = medium_of(K);
     /* a pass over a tile list runs pool_kernel<EST, false, true>, which exists for the estimators 0 and 1 */
     constexpr bool HAS_TILES = EST <= 1;

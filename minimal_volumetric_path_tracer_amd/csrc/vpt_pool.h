@@ -175,7 +175,13 @@ struct PoolParams {
     const unsigned* tile_map; /* read by pool_kernel<EST, false, true> only: the level's j-th group of 64 units is tile
                                * tile_map[j] (a pass over a tile subset, vpt_accum.hip; level_units = 64 x the
                                * number of listed tiles); pool_kernel's units cover every tile in order */
+    /* the launch's camera table: (o - centre, |o - centre|^2) of sphere i, formed on the host for this launch's
+     * origin and scene with Sphere::intersect's operations (vpt_int_cam_table).  A stage-A batch whose deciding
+     * lanes all start a sample casts from it (decide(), scene_intersect_grouped's cam).  Last: read at its use
+     * by scalar loads like every other member, and the members above keep their offsets. */
+    double cam_oc[VPT_MAX_SPHERES][4];
 };
+static_assert(sizeof(PoolParams) + sizeof(Medium) + 3 * sizeof(void*) <= 4096, "pool_kernel's arguments: at most 4 KB");
 
 /* VPT_P_KARG: the launch parameters read where they are used, by scalar loads from the kernel-argument
  * segment through an opaque pointer (the kernel's first argument sits at offset 0), instead of held
@@ -590,21 +596,39 @@ __device__ __forceinline__ int stage_a(TaskPool& sh, const PoolParams& P0, const
             vpt_sink(s2.X);
         }
 #endif
-        const int ev = decide<EST>(S, smp, t.p, t.e, m);
+        /* every deciding lane starts a sample (with the kill rings: any ring-A, R_SD or R_MD batch): the cast
+         * takes oc and |oc|^2 from the launch's camera table.  Not for the estimators without kill prediction,
+         * whose batches mix fresh and continuing paths */
+        constexpr bool CAM = kill_predicted_est<EST>() && !COUNT;
+        const bool cam = CAM && __ballot(!fresh) == 0;
+#if VPT_SECTIONS
+        if (__ballot(!fresh) == 0) sect_add(SECT_A_ALLFRESH, sect_now());
+#endif
+        /* the scene's flag words and the kill prediction's jump in one batch of scalar loads before the cast
+         * (free-flight decide, its HOIST), not one load and one wait each after it */
+        constexpr bool HOIST = EST == 0 || EST == 2;
+        uint64_t w_emitter = 0, w_point = 0, w_skey1 = 0, w_skey2 = 0, w_kpa = 0, w_kpc = 0;
+        if constexpr (HOIST) {
+            w_emitter = S->m_emitter, w_point = S->m_point, w_skey1 = S->m_skey1, w_skey2 = S->m_skey2;
+            w_kpa = S->kp_sa, w_kpc = S->kp_sc;
+            __asm__ volatile("" : "+s"(w_emitter), "+s"(w_point), "+s"(w_skey1), "+s"(w_skey2), "+s"(w_kpa), "+s"(w_kpc));
+        }
+        const int ev = decide<EST, COUNT, true>(S, smp, t.p, t.e, m, cam, P.cam_oc, w_emitter);
+        SECT_BEGIN(cl);
         t.X = smp.X;
         if (ev == EV_END) {
             t.acc = add(t.p.L, t.acc);
             t.in_path = false;
             result = R_A;
         } else if (ev == EV_SURF) {  /* (the implicit estimator, EST 3, picks no light) */
-            const int sk = sph_flag(S->m_skey1, t.e.id) | (sph_flag(S->m_skey2, t.e.id) << 1);
-            result = R_S + (sk == 0 ? (EST == 3 || EST == 5 ? 0 : sph_flag(S->m_point, t.e.src)) : sk);
+            const int sk = sph_flag(HOIST ? w_skey1 : S->m_skey1, t.e.id) | (sph_flag(HOIST ? w_skey2 : S->m_skey2, t.e.id) << 1);
+            result = R_S + (sk == 0 ? (EST == 3 || EST == 5 ? 0 : sph_flag(HOIST ? w_point : S->m_point, t.e.src)) : sk);
             /* a diffuse surface event: 2 n_mis + 4 draws, then the roulette (S->kp_sa, kp_sc) */
             if (kill_predicted_est<EST>() && !COUNT && sk == 0 &&
-                path_ends_after_event(t.X, t.p.depth, m, S->kp_sa, S->kp_sc))
+                path_ends_after_event(t.X, t.p.depth, m, HOIST ? w_kpa : S->kp_sa, HOIST ? w_kpc : S->kp_sc))
                 result += R_SD - R_S;
         } else {
-            result = R_M + (EST == 3 ? 0 : sph_flag(S->m_point, t.e.src));
+            result = R_M + (EST == 3 ? 0 : sph_flag(HOIST ? w_point : S->m_point, t.e.src));
             /* one slot (F_TD): stage M reads the sampled distance -- or, for the deferred
              * equi-angular estimators, tMax (with decide()'s psurf in F_PDF) */
             if (!(EST == 1 || EST == 4)) t.e.t = t.e.dist;
@@ -612,9 +636,13 @@ __device__ __forceinline__ int stage_a(TaskPool& sh, const PoolParams& P0, const
             if constexpr (kill_predicted_est<EST>() && !COUNT) {
                 uint64_t ja, jc;
                 vpt_erand48_jump(5, &ja, &jc);
+                /* formed here, in SGPRs: hoisted out of the pool loop into VGPRs, the jump's constants were
+                 * spilled and reloaded from scratch at every medium batch once the draws moved before the cast */
+                if constexpr (HOIST) __asm__ volatile("" : "+s"(ja), "+s"(jc));
                 if (path_ends_after_event(t.X, t.p.depth, m, ja, jc)) result += R_MD - R_M;
             }
         }
+        SECT_END(cl, SECT_A_CLASS);
         SECT_END(dci, SECT_A_DECIDE_IN);
     }
     SECT_END(dc, SECT_A_DECIDE);
