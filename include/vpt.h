@@ -180,6 +180,16 @@ int vpt_set_density_grid(vpt_context* ctx, const vpt_grid_desc* desc, const floa
  * bit for bit; block < 0 -> VPT_E_INVALID.  The setting belongs to the context: it is applied to the current
  * grid at once (synchronous), to every later vpt_set_density_grid, and survives a clear. */
 int vpt_set_grid_majorant_block(vpt_context* ctx, int block);
+/* How estimators VPT_HETERO_FREE and VPT_HETERO_RATIO read the density between the voxel centres (csrc/vpt_grid.h).
+ * VPT_GRID_NEAREST (the default): piecewise constant per voxel, every value as before.  VPT_GRID_TRILINEAR: the
+ * values sit at the voxel centres and are interpolated trilinearly in FP64, clamped (not faded) at the border of the
+ * box and zero outside it; the optical depth stays deterministic and exact (Simpson's rule on the interpolation
+ * cells), the tracks take the same draws in the same places, and local majorants are taken over each super-voxel
+ * dilated by one voxel, so block 1 is no longer free of null collisions.  A uniform grid renders as with
+ * VPT_GRID_NEAREST.  The setting belongs to the context: it is applied to the current grid at once (synchronous), to
+ * every later vpt_set_density_grid, and survives a clear.  Any other mode -> VPT_E_INVALID, nothing changes. */
+typedef enum { VPT_GRID_NEAREST = 0, VPT_GRID_TRILINEAR = 1 } vpt_grid_interp;
+int vpt_set_grid_interpolation(vpt_context* ctx, int mode);
 
 /* Renders into a DEVICE buffer on `stream` (a hipStream_t, NULL = default stream); returns
  * after enqueueing.  d_out: vpt_shard_rows(p) * width * 3 elements of fb_format, the
@@ -207,6 +217,8 @@ int vpt_multi_set_scene(vpt_multi* m, const vpt_sphere* spheres, int n);
 int vpt_multi_set_density_grid(vpt_multi* m, const vpt_grid_desc* desc, const float* density);
 /* vpt_set_grid_majorant_block on every context of the handle */
 int vpt_multi_set_grid_majorant_block(vpt_multi* m, int block);
+/* vpt_set_grid_interpolation on every context of the handle */
+int vpt_multi_set_grid_interpolation(vpt_multi* m, int mode);
 int vpt_multi_render(vpt_multi* m, const vpt_params* p, void* h_out);
 void vpt_multi_destroy(vpt_multi* m);
 /* one-shot: create, set the scene, render, destroy */
@@ -348,6 +360,15 @@ int vpt_grid_ratio_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, 
 int vpt_grid_ratio_probe_host(const vpt_grid_desc* desc, const float* density, int block, double sigma_t,
                               const vpt_ray* rays, const double* tmax, const uint64_t* states, int n, double* that,
                               uint64_t* states_out, uint32_t* steps);
+/* The three GPU probes above honour the context's vpt_set_grid_interpolation setting (the default is nearest).  The
+ * host probes with an explicit mode (a vpt_grid_interp; any other value -> VPT_E_INVALID): vpt_grid_probe_host_lm and
+ * vpt_grid_ratio_probe_host are these with interp = VPT_GRID_NEAREST. */
+int vpt_grid_probe_host_ex(const vpt_grid_desc* desc, const float* density, int block, int interp, double sigma_t,
+                           const vpt_ray* rays, const double* tmax, const uint64_t* states, int n, double* tau,
+                           double* t_coll, uint64_t* states_out, uint32_t* steps);
+int vpt_grid_ratio_probe_host_ex(const vpt_grid_desc* desc, const float* density, int block, int interp, double sigma_t,
+                                 const vpt_ray* rays, const double* tmax, const uint64_t* states, int n, double* that,
+                                 uint64_t* states_out, uint32_t* steps);
 
 /* PPM writer of main() (src/rt.cpp:812-820): clamp to [0,1] (src/rt.cpp:803), gamma 1/2.2,
  * int(v*255 + .5) (include/mathUtilities.h:43-45), "P3\n%d %d\n255\n" then "%d %d %d " per

@@ -62,6 +62,38 @@
  * `steps` is the number of draws.  Capped like the track (NaN).  With B >= max(n) the local estimate is the global
  * one bit for bit; with B = 1 a ray takes one draw and That is 1.0 where the track (B = 1) from the same state
  * returns "none" and +0.0 where it collides, with the same end state.
+ *
+ * Trilinear interpolation (opt-in: vpt_grid_view.interp = 1, carried in the word that was pad_; 0 = nearest, all of
+ * the above).  The voxel values sit at the voxel centres lo + (i + 0.5) cell.  Lookup, per axis, for a point of the box:
+ *   u = (p - lo) * inv_cell - 0.5;  !(u > 0): u = 0 (a NaN too);  u > n - 1: u = n - 1
+ *   i0 = (int)floor(u) held to [0, max(n - 2, 0)];  i1 = min(i0 + 1, n - 1);  f = u - (double)i0, in [0, 1]
+ * so the field is clamped at the border, not faded: constant along an axis in the outer half voxel, and zero outside
+ * the box as before (the support and the slab test do not change).  The eight voxels are widened to double on load
+ * and combined with lerp(a, b, f) = a + f * (b - a): four lerps along x, two along y, one along z.  A lerp returns a
+ * exactly when a == b, so a uniform field's lookup is the nearest one bit for bit.
+ * Overshoot: with 0 <= f <= 1 and b >= a the rounded product f * (b - a) is at most the rounded b - a, so a lerp is
+ * at most fl(a + fl(b - a)), which is b or the double above it (and at most a where b < a: the product is <= 0).  One
+ * ulp per lerp, three lerps deep: the lookup is at most three ulps above the largest of its eight corners -- above
+ * the majorant by that much at most.  The walkers test rho >= mu before they use rho: such a value is a certain
+ * collision (track) or the estimate +0.0 (ratio), never a weight 1 - rho / mu < 0.
+ * Majorants: rho_max stays the global one.  A super-voxel's majorant is the maximum over its voxels dilated by one
+ * voxel on every side (clamped to the grid): a point of super-voxel k has u in [kB - 0.5, (k + 1)B - 0.5), so it reads
+ * voxels kB - 1 .. (k + 1)B, and a tentative point the rounding put a hair past the exit plane still does.  The
+ * majorant grid is rebuilt when the grid, the block or the mode changes.  B >= max(n) is one super-voxel whose
+ * majorant is rho_max: the global walk bit for bit.  B = 1 is no longer analytic inversion: the majorant is the maximum
+ * of 27 voxels, collisions can be null, and a track can take more than one draw.
+ * Track and ratio tracking: the four walkers above statement for statement; only the density at a tentative point is
+ * the trilinear lookup (the walkers take the mode as a constant argument, vpt_grid_*_m).
+ * Optical depth (vpt_grid_tau_tl): vpt_grid_tau's entry logic (tmax, rho_max, the slab test, tend); the DDA walks the
+ * interpolation cells, n + 1 per axis, bounded by lo, lo + ((double)k + 0.5) * cell for k = 0 .. n - 1, and hi
+ * (vpt_grid_tl_plane, the one expression).  Inside a cell the field along the ray is a polynomial of degree <= 3 in t,
+ * which Simpson's rule integrates exactly: for each piece [t, te] with te > t
+ *   tm = 0.5 * (t + te);  r0, rm, r1 = the lookup at o + d t, o + d tm, o + d te
+ *   tau = tau + (((r0 + 4.0 * rm) + r1) * (te - t)) * (1.0 / 6.0)
+ * and r1 is carried into the next piece as its r0 (the same expression, the same bits).  The entry cell of an axis is
+ * floor((p - lo) * inv_cell - 0.5) + 1 held to [0, n]; a cell the rounding left without length is passed over, and
+ * since the integrand is looked up by position, never by cell index, a cut misplaced by an ulp costs an ulp.  Capped
+ * at n[0] + n[1] + n[2] + 7 pieces.  No draw; T = exp(sigma_t * tau * -1.0) as before.
  */
 #ifndef VPT_GRID_H
 #define VPT_GRID_H
@@ -91,7 +123,7 @@
 /* the grid as the walkers read it (host or device pointer in rho); filled by vpt_grid_view_init */
 typedef struct vpt_grid_view {
     int32_t n[3];          /* nx, ny, nz */
-    int32_t pad_;
+    int32_t interp;        /* 0 nearest, 1 trilinear (header comment); the word that was padding */
     double lo[3], hi[3];
     double inv_cell[3];    /* n / (hi - lo) */
     double cell[3];        /* (hi - lo) / n */
@@ -135,7 +167,7 @@ static inline void vpt_grid_view_init(vpt_grid_view* G, const int32_t n[3], cons
         G->inv_cell[a] = (double)n[a] / (hi[a] - lo[a]);
         G->cell[a] = (hi[a] - lo[a]) / (double)n[a];
     }
-    G->pad_ = 0;
+    G->interp = 0;
     G->rho_max = (double)mx;
     G->rho = rho;
     G->maj = 0;
@@ -165,6 +197,32 @@ static inline void vpt_grid_majorant_build(const int32_t n[3], int32_t B, const 
         }
 }
 
+/* the same for the trilinear field (header comment): every block's maximum is taken over its voxels dilated by one
+ * voxel on every side, so a voxel counts for every block that the voxels next to it lie in */
+static inline void vpt_grid_majorant_build_tl(const int32_t n[3], int32_t B, const float* density, float* out)
+{
+    int32_t nb[3];
+    vpt_grid_majorant_counts(n, B, nb);
+    const int64_t nbv = (int64_t)nb[0] * nb[1] * nb[2];
+    for (int64_t i = 0; i < nbv; ++i) out[i] = 0.0f;
+    for (int32_t z = 0; z < n[2]; ++z) {
+        const int32_t bz0 = (z > 0 ? z - 1 : 0) / B, bz1 = (z + 1 < n[2] ? z + 1 : n[2] - 1) / B;
+        for (int32_t y = 0; y < n[1]; ++y) {
+            const int32_t by0 = (y > 0 ? y - 1 : 0) / B, by1 = (y + 1 < n[1] ? y + 1 : n[1] - 1) / B;
+            const float* row = density + ((int64_t)z * n[1] + y) * n[0];
+            for (int32_t x = 0; x < n[0]; ++x) {
+                const int32_t bx0 = (x > 0 ? x - 1 : 0) / B, bx1 = (x + 1 < n[0] ? x + 1 : n[0] - 1) / B;
+                for (int32_t bz = bz0; bz <= bz1; ++bz)
+                    for (int32_t by = by0; by <= by1; ++by) {
+                        float* orow = out + ((int64_t)bz * nb[1] + by) * nb[0];
+                        for (int32_t bx = bx0; bx <= bx1; ++bx)
+                            if (row[x] > orow[bx]) orow[bx] = row[x];
+                    }
+            }
+        }
+    }
+}
+
 /* host: turns the majorant grid of an initialised view on (B >= 1, `maj` the pointer the walkers will read) or
  * off (B == 0) */
 static inline void vpt_grid_view_set_majorant(vpt_grid_view* G, int32_t B, const float* maj)
@@ -187,6 +245,53 @@ VPT_GR double vpt_grid_density(const vpt_grid_view* G, double px, double py, dou
 {
     const int ix = vpt_grid_axis_index(G, 0, px), iy = vpt_grid_axis_index(G, 1, py), iz = vpt_grid_axis_index(G, 2, pz);
     return (double)G->rho[((int64_t)iz * G->n[1] + iy) * G->n[0] + ix];
+}
+
+/* one axis of the trilinear lookup (header comment): the two voxel indices and the weight of the upper one */
+VPT_GR void vpt_grid_tl_axis(const vpt_grid_view* G, int a, double p, int* i0, int* i1, double* f)
+{
+    const int n = G->n[a];
+    double u = (p - G->lo[a]) * G->inv_cell[a] - 0.5;
+    if (!(u > 0.0)) u = 0.0;  /* the outer half voxel below (or NaN) */
+    if (u > (double)(n - 1)) u = (double)(n - 1);
+    int i = (int)floor(u);
+    const int top = n - 2 > 0 ? n - 2 : 0;
+    if (i > top) i = top;
+    if (i < 0) i = 0;
+    *i0 = i;
+    *i1 = i + 1 < n ? i + 1 : n - 1;
+    *f = u - (double)i;
+}
+
+VPT_GR double vpt_grid_lerp(double a, double b, double f)
+{
+    return a + f * (b - a);
+}
+
+/* trilinear density at a point of the box (header comment) */
+VPT_GR double vpt_grid_density_tl(const vpt_grid_view* G, double px, double py, double pz)
+{
+    int x0, x1, y0, y1, z0, z1;
+    double fx, fy, fz;
+    vpt_grid_tl_axis(G, 0, px, &x0, &x1, &fx);
+    vpt_grid_tl_axis(G, 1, py, &y0, &y1, &fy);
+    vpt_grid_tl_axis(G, 2, pz, &z0, &z1, &fz);
+    const int64_t r00 = ((int64_t)z0 * G->n[1] + y0) * G->n[0] + x0, r01 = ((int64_t)z0 * G->n[1] + y1) * G->n[0] + x0;
+    const int64_t r10 = ((int64_t)z1 * G->n[1] + y0) * G->n[0] + x0, r11 = ((int64_t)z1 * G->n[1] + y1) * G->n[0] + x0;
+    /* the eight fetches are four x-adjacent pairs (dx is 0 only where nx == 1).  Plain 32-bit loads: fetching a pair
+     * with one 64-bit load where its address is 8-byte aligned was measured and lost */
+    const int dx = x1 - x0;
+    const double c00 = vpt_grid_lerp((double)G->rho[r00], (double)G->rho[r00 + dx], fx);
+    const double c01 = vpt_grid_lerp((double)G->rho[r01], (double)G->rho[r01 + dx], fx);
+    const double c10 = vpt_grid_lerp((double)G->rho[r10], (double)G->rho[r10 + dx], fx);
+    const double c11 = vpt_grid_lerp((double)G->rho[r11], (double)G->rho[r11 + dx], fx);
+    return vpt_grid_lerp(vpt_grid_lerp(c00, c01, fy), vpt_grid_lerp(c10, c11, fy), fz);
+}
+
+/* the density as the walkers read it at a tentative point; tl is a constant at every call, so one lookup remains */
+VPT_GR double vpt_grid_lookup(const vpt_grid_view* G, const int tl, double px, double py, double pz)
+{
+    return tl ? vpt_grid_density_tl(G, px, py, pz) : vpt_grid_density(G, px, py, pz);
 }
 
 /* slab test of o + d t against the box: the interval [*t0, *t1] with *t0 >= 0; returns 0 when there is none.
@@ -250,15 +355,68 @@ VPT_GR double vpt_grid_tau(const vpt_grid_view* G, const double o[3], const doub
     return tau;
 }
 
+/* plane j of the interpolation cells of axis a, j = 0 .. n + 1: cell c lies between planes c and c + 1 */
+VPT_GR double vpt_grid_tl_plane(const vpt_grid_view* G, int a, int j)
+{
+    if (j <= 0) return G->lo[a];
+    if (j > G->n[a]) return G->hi[a];
+    return G->lo[a] + ((double)(j - 1) + 0.5) * G->cell[a];
+}
+
+/* optical depth of the trilinear field over t in [0, tmax] (header comment) */
+VPT_GR double vpt_grid_tau_tl(const vpt_grid_view* G, const double o[3], const double d[3], double tmax)
+{
+    double t0, t1;
+    if (!(tmax > 0.0) || !(G->rho_max > 0.0)) return 0.0;
+    if (!vpt_grid_slab(G, o, d, &t0, &t1)) return 0.0;
+    const double tend = t1 < tmax ? t1 : tmax;
+    if (!(t0 < tend)) return 0.0;
+    int i[3], step[3];
+    double tn[3], inv[3];
+    for (int a = 0; a < 3; ++a) {
+        const double f = floor(((o[a] + d[a] * t0) - G->lo[a]) * G->inv_cell[a] - 0.5) + 1.0;
+        i[a] = !(f >= 0.0) ? 0 : (f < (double)G->n[a] ? (int)f : G->n[a]);
+        step[a] = d[a] > 0.0 ? 1 : (d[a] < 0.0 ? -1 : 0);
+        inv[a] = step[a] ? 1.0 / d[a] : 0.0;
+        tn[a] = step[a] ? (vpt_grid_tl_plane(G, a, i[a] + (step[a] > 0)) - o[a]) * inv[a] : VPT_GRID_BIG;
+    }
+    double tau = 0.0, t = t0;
+    double r0 = vpt_grid_density_tl(G, o[0] + d[0] * t, o[1] + d[1] * t, o[2] + d[2] * t);
+    const int max_steps = G->n[0] + G->n[1] + G->n[2] + 7;
+    for (int k = 0; k < max_steps; ++k) {
+        const int a = tn[0] <= tn[1] ? (tn[0] <= tn[2] ? 0 : 2) : (tn[1] <= tn[2] ? 1 : 2);
+        const double te = tn[a] < tend ? tn[a] : tend;
+        if (te > t) {
+            const double tm = 0.5 * (t + te);
+            const double rm = vpt_grid_density_tl(G, o[0] + d[0] * tm, o[1] + d[1] * tm, o[2] + d[2] * tm);
+            const double r1 = vpt_grid_density_tl(G, o[0] + d[0] * te, o[1] + d[1] * te, o[2] + d[2] * te);
+            tau = tau + (((r0 + 4.0 * rm) + r1) * (te - t)) * (1.0 / 6.0);
+            t = te;
+            r0 = r1;
+        }
+        if (!(tn[a] < tend)) break;
+        i[a] += step[a];
+        if (i[a] < 0 || i[a] > G->n[a]) break;
+        tn[a] = (vpt_grid_tl_plane(G, a, i[a] + (step[a] > 0)) - o[a]) * inv[a];
+    }
+    return tau;
+}
+
 VPT_GR double vpt_grid_transmittance(const vpt_grid_view* G, const double o[3], const double d[3], double tmax,
                                      double sigma_t)
 {
     return VPT_GRID_EXP(sigma_t * vpt_grid_tau(G, o, d, tmax) * -1.0);
 }
 
+VPT_GR double vpt_grid_transmittance_tl(const vpt_grid_view* G, const double o[3], const double d[3], double tmax,
+                                        double sigma_t)
+{
+    return VPT_GRID_EXP(sigma_t * vpt_grid_tau_tl(G, o, d, tmax) * -1.0);
+}
+
 /* delta tracking (header comment): the collision distance, -1 for "none", NaN for a capped track; *X is the
  * erand48 state, advanced by the draws taken; *steps (optional) counts the tentative steps */
-VPT_GR double vpt_grid_track(const vpt_grid_view* G, const double o[3], const double d[3], double tmax, double sigma_t,
+VPT_GR double vpt_grid_track_m(const vpt_grid_view* G, const int tl, const double o[3], const double d[3], double tmax, double sigma_t,
                              uint64_t* X, uint32_t* steps)
 {
     double t0, t1;
@@ -270,7 +428,7 @@ VPT_GR double vpt_grid_track(const vpt_grid_view* G, const double o[3], const do
         t = t + (-VPT_GRID_LOG(1 - vpt_erand48(X)) / (G->rho_max * sigma_t));
         if (steps) *steps = (uint32_t)(k + 1);
         if (t > tmax || t >= t1 || t != t) return -1.0;
-        const double rho = vpt_grid_density(G, o[0] + d[0] * t, o[1] + d[1] * t, o[2] + d[2] * t);
+        const double rho = vpt_grid_lookup(G, tl, o[0] + d[0] * t, o[1] + d[1] * t, o[2] + d[2] * t);
         if (rho >= G->rho_max) return t;
         if (vpt_erand48(X) * G->rho_max < rho) return t;
     }
@@ -287,7 +445,7 @@ VPT_GR double vpt_grid_block_plane(const vpt_grid_view* G, int a, int kb)
 
 /* delta tracking with local majorants (header comment; G->block >= 1): vpt_grid_track's arguments and
  * results */
-VPT_GR double vpt_grid_track_lm(const vpt_grid_view* G, const double o[3], const double d[3], double tmax,
+VPT_GR double vpt_grid_track_lm_m(const vpt_grid_view* G, const int tl, const double o[3], const double d[3], double tmax,
                                 double sigma_t, uint64_t* X, uint32_t* steps)
 {
     double t0, t1;
@@ -334,7 +492,7 @@ VPT_GR double vpt_grid_track_lm(const vpt_grid_view* G, const double o[3], const
         }
         if (c == max_cross) return -1.0;
         if (tc > tmax || tc >= t1) return -1.0;
-        const double rho = vpt_grid_density(G, o[0] + d[0] * tc, o[1] + d[1] * tc, o[2] + d[2] * tc);
+        const double rho = vpt_grid_lookup(G, tl, o[0] + d[0] * tc, o[1] + d[1] * tc, o[2] + d[2] * tc);
         if (rho >= mu) return tc;
         if (vpt_erand48(X) * mu < rho) return tc;
         t = tc;
@@ -344,7 +502,7 @@ VPT_GR double vpt_grid_track_lm(const vpt_grid_view* G, const double o[3], const
 
 /* ratio tracking (header comment): the estimate That of exp(-sigma_t tau(o, d, tmax)), NaN for a capped walk;
  * *X is the erand48 state, advanced by the draws taken; *steps (optional) counts them */
-VPT_GR double vpt_grid_ratio(const vpt_grid_view* G, const double o[3], const double d[3], double tmax, double sigma_t,
+VPT_GR double vpt_grid_ratio_m(const vpt_grid_view* G, const int tl, const double o[3], const double d[3], double tmax, double sigma_t,
                              uint64_t* X, uint32_t* steps)
 {
     double t0, t1;
@@ -356,7 +514,7 @@ VPT_GR double vpt_grid_ratio(const vpt_grid_view* G, const double o[3], const do
         t = t + (-VPT_GRID_LOG(1 - vpt_erand48(X)) / (G->rho_max * sigma_t));
         if (steps) *steps = (uint32_t)(k + 1);
         if (t > tmax || t >= t1 || t != t) return That;
-        const double rho = vpt_grid_density(G, o[0] + d[0] * t, o[1] + d[1] * t, o[2] + d[2] * t);
+        const double rho = vpt_grid_lookup(G, tl, o[0] + d[0] * t, o[1] + d[1] * t, o[2] + d[2] * t);
         if (rho >= G->rho_max) return 0.0;
         That = That * (1.0 - rho / G->rho_max);
     }
@@ -365,7 +523,7 @@ VPT_GR double vpt_grid_ratio(const vpt_grid_view* G, const double o[3], const do
 
 /* ratio tracking with local majorants (header comment; G->block >= 1): vpt_grid_ratio's arguments and results.
  * The walk is vpt_grid_track_lm's, restated: sharing it would put the weight into the track's loop */
-VPT_GR double vpt_grid_ratio_lm(const vpt_grid_view* G, const double o[3], const double d[3], double tmax,
+VPT_GR double vpt_grid_ratio_lm_m(const vpt_grid_view* G, const int tl, const double o[3], const double d[3], double tmax,
                                 double sigma_t, uint64_t* X, uint32_t* steps)
 {
     double t0, t1;
@@ -410,12 +568,34 @@ VPT_GR double vpt_grid_ratio_lm(const vpt_grid_view* G, const double o[3], const
         }
         if (c == max_cross) return That;
         if (tc > tmax || tc >= t1) return That;
-        const double rho = vpt_grid_density(G, o[0] + d[0] * tc, o[1] + d[1] * tc, o[2] + d[2] * tc);
+        const double rho = vpt_grid_lookup(G, tl, o[0] + d[0] * tc, o[1] + d[1] * tc, o[2] + d[2] * tc);
         if (rho >= mu) return 0.0;
         That = That * (1.0 - rho / mu);
         t = tc;
     }
     return (double)NAN;
+}
+
+/* the nearest-lookup walkers under the names they have always had */
+VPT_GR double vpt_grid_track(const vpt_grid_view* G, const double o[3], const double d[3], double tmax, double sigma_t,
+        uint64_t* X, uint32_t* steps)
+{
+    return vpt_grid_track_m(G, 0, o, d, tmax, sigma_t, X, steps);
+}
+VPT_GR double vpt_grid_track_lm(const vpt_grid_view* G, const double o[3], const double d[3], double tmax, double sigma_t,
+        uint64_t* X, uint32_t* steps)
+{
+    return vpt_grid_track_lm_m(G, 0, o, d, tmax, sigma_t, X, steps);
+}
+VPT_GR double vpt_grid_ratio(const vpt_grid_view* G, const double o[3], const double d[3], double tmax, double sigma_t,
+        uint64_t* X, uint32_t* steps)
+{
+    return vpt_grid_ratio_m(G, 0, o, d, tmax, sigma_t, X, steps);
+}
+VPT_GR double vpt_grid_ratio_lm(const vpt_grid_view* G, const double o[3], const double d[3], double tmax, double sigma_t,
+        uint64_t* X, uint32_t* steps)
+{
+    return vpt_grid_ratio_lm_m(G, 0, o, d, tmax, sigma_t, X, steps);
 }
 
 #endif

@@ -16,6 +16,10 @@
  * vpt_grid_track_lm, else vpt_grid_track.  The choice is the template parameter LM of hetero_decide,
  * trace_hetero and every kernel of estimator 10, made on the host at launch from the context's view, so the
  * LM = false instantiations are the kernels as they were before local majorants existed.
+ * Trilinear interpolation (vpt_grid.h, vpt_set_grid_interpolation): the template parameter TL beside LM, chosen on the
+ * host in the same way from the view's interp word; the walkers and the optical depth take it as a constant, so
+ * there is no test of the mode in a loop.  The TL = true kernels are instantiated in vpt_hetero_tl.hip, a code object
+ * of their own, and the TL = false ones stay in vpt_hetero.hip as they were.
  */
 #ifndef VPT_HETERO_H
 #define VPT_HETERO_H
@@ -30,8 +34,10 @@
 
 namespace vpt {
 
-/* the grid's transmittance as the TP policy of mis_v2 / single_scattering (vpt_device.h TrHom) */
-struct GridTr {
+/* the grid's transmittance as the TP policy of mis_v2 / single_scattering (vpt_device.h TrHom); TL: the trilinear
+ * field (GridTr is the nearest one) */
+template <bool TL>
+struct GridTrT {
     static constexpr bool hom = false;
     static constexpr bool draws = false;
     vpt_grid_view G;
@@ -39,9 +45,9 @@ struct GridTr {
      * walkers read are copied (everything before `maj`): block, nb and maj stay unset and nothing reads them, so
      * the LM = false kernels load what they loaded before local majorants existed */
     template <bool LM>
-    __device__ __forceinline__ static GridTr load(const vpt_grid_view* __restrict__ g)
+    __device__ __forceinline__ static GridTrT load(const vpt_grid_view* __restrict__ g)
     {
-        GridTr tp;
+        GridTrT tp;
         if (LM) tp.G = *g;
         else __builtin_memcpy(&tp.G, g, offsetof(vpt_grid_view, maj));
         return tp;
@@ -49,7 +55,7 @@ struct GridTr {
     __device__ __forceinline__ double along(dv3 o, dv3 d, double dist, double sigma_t) const
     {
         const double oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
-        return vpt_grid_transmittance(&G, oo, dd, dist, sigma_t);
+        return TL ? vpt_grid_transmittance_tl(&G, oo, dd, dist, sigma_t) : vpt_grid_transmittance(&G, oo, dd, dist, sigma_t);
     }
     /* a to b: the distance and the unit direction formed as transmitance() and nrm() form them */
     __device__ __forceinline__ double between(dv3 a, dv3 b, double sigma_t) const
@@ -60,11 +66,13 @@ struct GridTr {
         return along(a, nrm(aux), dist, sigma_t);
     }
 };
+using GridTr = GridTrT<false>;
 
 /* estimator 11's policy: every factor is a ratio-tracking estimate (vpt_grid.h) over the same segment, drawn from
  * the sample's own stream where GridTr evaluates the factor -- a policy with draws == true takes the sampler first.
- * A zero-length segment is 1.0 without a draw, as vpt_grid_tau's is exp(-0).  LM: the grid has a majorant grid. */
-template <bool LM>
+ * A zero-length segment is 1.0 without a draw, as vpt_grid_tau's is exp(-0).  LM: the grid has a majorant grid; TL: the
+ * trilinear field. */
+template <bool LM, bool TL = false>
 struct GridRatioTr {
     static constexpr bool hom = false;
     static constexpr bool draws = true;
@@ -83,8 +91,8 @@ struct GridRatioTr {
     {
         if (!(dist > 0)) return lm_exp(sigma_t * 0.0 * -1.0);
         const double oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
-        return LM ? vpt_grid_ratio_lm(&G, oo, dd, dist, sigma_t, &smp.X, (uint32_t*)nullptr)
-                  : vpt_grid_ratio(&G, oo, dd, dist, sigma_t, &smp.X, (uint32_t*)nullptr);
+        return LM ? vpt_grid_ratio_lm_m(&G, TL, oo, dd, dist, sigma_t, &smp.X, (uint32_t*)nullptr)
+                  : vpt_grid_ratio_m(&G, TL, oo, dd, dist, sigma_t, &smp.X, (uint32_t*)nullptr);
     }
     template <bool COUNT>
     __device__ __forceinline__ double between(Sampler<COUNT>& smp, dv3 a, dv3 b, double sigma_t) const
@@ -102,7 +110,7 @@ struct HeteroStats {
 };
 
 /* decide<0> with delta tracking in freeFlightSample's place */
-template <bool COUNT, bool LM = false, class TP = GridTr>
+template <bool COUNT, bool LM = false, bool TL = false, class TP = GridTrT<TL>>
 VPT_DEV int hetero_decide(const DevScene* __restrict__ S, const TP& tp, Sampler<COUNT>& smp, Path& p, Event& e,
                           const Medium& m, HeteroStats* hs = nullptr)
 {
@@ -118,8 +126,8 @@ VPT_DEV int hetero_decide(const DevScene* __restrict__ S, const TP& tp, Sampler<
     e.src = emit_pick(S, (int)(smp.next() * count), count);
     const double oo[3] = {p.o.x, p.o.y, p.o.z}, dd[3] = {p.d.x, p.d.y, p.d.z};
     uint32_t nsteps = 0;
-    const double tc = LM ? vpt_grid_track_lm(&tp.G, oo, dd, t, sigma_t, &smp.X, hs ? &nsteps : (uint32_t*)nullptr)
-                        : vpt_grid_track(&tp.G, oo, dd, t, sigma_t, &smp.X, hs ? &nsteps : (uint32_t*)nullptr);
+    const double tc = LM ? vpt_grid_track_lm_m(&tp.G, TL, oo, dd, t, sigma_t, &smp.X, hs ? &nsteps : (uint32_t*)nullptr)
+                        : vpt_grid_track_m(&tp.G, TL, oo, dd, t, sigma_t, &smp.X, hs ? &nsteps : (uint32_t*)nullptr);
     if (hs) {
         hs->tracks += 1;
         hs->steps += nsteps;
@@ -185,8 +193,8 @@ VPT_DEV void hetero_medium(const DevScene* __restrict__ S, const TP& tp, Sampler
 }
 
 /* one camera sample, sequentially (vpt_trace_batch, render_kernel_simple<10>) */
-template <bool COUNT, bool LM = false>
-__device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridTr& tp, Sampler<COUNT>& smp, dv3 o, dv3 d,
+template <bool COUNT, bool LM = false, bool TL = false>
+__device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridTrT<TL>& tp, Sampler<COUNT>& smp, dv3 o, dv3 d,
                                    const Medium& m, HeteroStats* hs = nullptr)
 {
     Path p;
@@ -198,7 +206,7 @@ __device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridTr&
     Event e;
     e.pdf = 0;
     while (continue_path(smp, p, m)) {
-        const int ev = hetero_decide<COUNT, LM>(S, tp, smp, p, e, m, hs);
+        const int ev = hetero_decide<COUNT, LM, TL>(S, tp, smp, p, e, m, hs);
         if (ev == EV_END) break;
         if (ev == EV_SURF) hetero_surface(S, tp, smp, p, e, m);
         else hetero_medium(S, tp, smp, p, e, m);
@@ -208,8 +216,8 @@ __device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridTr&
 
 /* the same for estimator 11 (render_kernel_simple<11>).  Restated, not a shared template: estimator 10's function
  * above is an out-of-line function of its kernels, and its name and code are to stay what they were */
-template <bool COUNT, bool LM = false>
-__device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridRatioTr<LM>& tp, Sampler<COUNT>& smp, dv3 o,
+template <bool COUNT, bool LM = false, bool TL = false>
+__device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridRatioTr<LM, TL>& tp, Sampler<COUNT>& smp, dv3 o,
                                    dv3 d, const Medium& m, HeteroStats* hs = nullptr)
 {
     Path p;
@@ -221,7 +229,7 @@ __device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridRat
     Event e;
     e.pdf = 0;
     while (continue_path(smp, p, m)) {
-        const int ev = hetero_decide<COUNT, LM, GridRatioTr<LM>>(S, tp, smp, p, e, m, hs);
+        const int ev = hetero_decide<COUNT, LM, TL, GridRatioTr<LM, TL>>(S, tp, smp, p, e, m, hs);
         if (ev == EV_END) break;
         if (ev == EV_SURF) hetero_surface(S, tp, smp, p, e, m);
         else hetero_medium(S, tp, smp, p, e, m);
@@ -230,14 +238,14 @@ __device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridRat
 }
 
 /* the three steps as the persistent-wave loop (vpt_wave.h) calls them, on the kernel's view of the grid */
-template <bool LM, class TP = GridTr>
+template <bool LM, bool TL = false, class TP = GridTrT<TL>>
 struct HeteroSteps {
     TP tp;
     template <bool COUNT>
     __device__ __forceinline__ int decide(const DevScene* __restrict__ S, Sampler<COUNT>& smp, Path& p, Event& e,
                                           const Medium& m) const
     {
-        return hetero_decide<COUNT, LM, TP>(S, tp, smp, p, e, m);
+        return hetero_decide<COUNT, LM, TL, TP>(S, tp, smp, p, e, m);
     }
     template <bool COUNT>
     __device__ __forceinline__ void surface(const DevScene* __restrict__ S, Sampler<COUNT>& smp, Path& p, const Event& e,
@@ -275,5 +283,18 @@ void vpt_int_grid_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_
 void vpt_int_grid_ratio_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
                                      const double* tmax, const uint64_t* states, int n, double* that, uint64_t* states_out,
                                      uint32_t* steps);
+/* every launch of the list above also exists with the suffix _tl: the same call on the TL = true kernels (vpt_hetero_tl.hip),
+ * which the caller takes where the context's view has interp == 1 */
+int vpt_int_hetero_launch_tl(int device, const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
+int vpt_int_hetero_simple_launch_tl(const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
+void vpt_int_hetero_trace_launch_tl(int est, const vpt_ray* rays, const uint64_t* states, int n, const vpt::Medium& m,
+                                    const DevScene* S, const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states,
+                                    unsigned long long* stats);
+void vpt_int_grid_probe_launch_tl(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays, const double* tmax,
+                                  const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out,
+                                  uint32_t* steps);
+void vpt_int_grid_ratio_probe_launch_tl(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
+                                        const double* tmax, const uint64_t* states, int n, double* that, uint64_t* states_out,
+                                        uint32_t* steps);
 
 #endif

@@ -15,6 +15,12 @@
  * the tests and of the timing.  -DVPT_HETERO_LDS=0 reads every grid from global memory.  DESIGN.md section 4
  * has both timings (LDS won on the 16^3 grids by several times the run-to-run spread).  The 64 KiB do not lower
  * the occupancy: the registers already hold it at two workgroups per CU.
+ *
+ * Trilinear interpolation: every kernel here takes the template parameter TL (vpt_hetero.h) and the unit instantiates
+ * one value of it, VPT_HETERO_TL.  Compiled as it stands (0) the unit holds the nearest-lookup kernels and exports the
+ * vpt_int_* launches; vpt_hetero_tl.hip includes this file with VPT_HETERO_TL = 1 and exports the same launches with
+ * the suffix _tl, so the trilinear kernels are a code object of their own and this unit's stays what it was.  The LDS
+ * prologue serves both lookups as it is.
  */
 #include <hip/hip_runtime.h>
 
@@ -27,6 +33,14 @@
 #define VPT_HETERO_LDS 1
 #endif
 #define VPT_HETERO_LDS_BYTES 65536
+#ifndef VPT_HETERO_TL
+#define VPT_HETERO_TL 0
+#endif
+#if VPT_HETERO_TL
+#define VPT_HX(name) name##_tl
+#else
+#define VPT_HX(name) name
+#endif
 /* with local majorants: the majorant grid is staged in what the density left of the LDS budget -- all of it
  * where the density does not fit (DESIGN.md section 4 has the timing that decided the default) */
 #ifndef VPT_HETERO_LDS_MAJ
@@ -35,13 +49,13 @@
 
 namespace vpt {
 
-template <bool COUNT, int FB, bool LM>
+template <bool COUNT, int FB, bool LM, bool TL>
 __global__ __launch_bounds__(256, 2) void hetero_kernel(KParams P, const DevScene* __restrict__ S)
 {
     /* the view lives in the steps object from the start: the walkers take its address, so a copy made after the
      * prologue is a second stack object (416 against 288 bytes of scratch, 9 against 4 spilled VGPRs) */
-    HeteroSteps<LM> st{GridTr::load<LM>(P.grid)};
-    [[maybe_unused]] GridTr& tp = st.tp;
+    HeteroSteps<LM, TL> st{GridTrT<TL>::template load<LM>(P.grid)};
+    [[maybe_unused]] GridTrT<TL>& tp = st.tp;
 #if VPT_HETERO_LDS
     __shared__ float lds_rho[VPT_HETERO_LDS_BYTES / sizeof(float)];
     {
@@ -65,17 +79,17 @@ __global__ __launch_bounds__(256, 2) void hetero_kernel(KParams P, const DevScen
 #endif
     }
 #endif
-    wave_render<HeteroSteps<LM>, COUNT, FB>(P, S, st);
+    wave_render<HeteroSteps<LM, TL>, COUNT, FB>(P, S, st);
 }
 
 /* estimator 11 (VPT_HETERO_RATIO): hetero_kernel on the ratio-tracking policy.  The prologue is restated, not shared:
  * with estimator 10's kernel calling a common body template its code moves (commuted v_mul_f64 operands, swapped
  * v_add_f64 pairs, up to three instructions more or fewer), and that kernel is to stay what it was */
-template <bool COUNT, int FB, bool LM>
+template <bool COUNT, int FB, bool LM, bool TL>
 __global__ __launch_bounds__(256, 2) void hetero_ratio_kernel(KParams P, const DevScene* __restrict__ S)
 {
-    HeteroSteps<LM, GridRatioTr<LM>> st{GridRatioTr<LM>::template load<LM>(P.grid)};
-    [[maybe_unused]] GridRatioTr<LM>& tp = st.tp;
+    HeteroSteps<LM, TL, GridRatioTr<LM, TL>> st{GridRatioTr<LM, TL>::template load<LM>(P.grid)};
+    [[maybe_unused]] GridRatioTr<LM, TL>& tp = st.tp;
 #if VPT_HETERO_LDS
     __shared__ float lds_rho[VPT_HETERO_LDS_BYTES / sizeof(float)];
     {
@@ -99,7 +113,7 @@ __global__ __launch_bounds__(256, 2) void hetero_ratio_kernel(KParams P, const D
 #endif
     }
 #endif
-    wave_render<HeteroSteps<LM, GridRatioTr<LM>>, COUNT, FB>(P, S, st);
+    wave_render<HeteroSteps<LM, TL, GridRatioTr<LM, TL>>, COUNT, FB>(P, S, st);
 }
 
 }  // namespace vpt
@@ -108,8 +122,10 @@ using namespace vpt;
 
 namespace {
 
+constexpr bool TLU = VPT_HETERO_TL != 0;  /* the unit's value of TL */
+
 /* estimator 10's per-sample call (vpt_hetero.h) */
-template <bool LM>
+template <bool LM, bool TL>
 __global__ __launch_bounds__(256) void trace_batch_hetero_kernel(const vpt_ray* __restrict__ rays,
                                                                  const uint64_t* __restrict__ states, int n, Medium m,
                                                                  const DevScene* __restrict__ S,
@@ -122,7 +138,7 @@ __global__ __launch_bounds__(256) void trace_batch_hetero_kernel(const vpt_ray* 
     smp.X = states[i] & 0xFFFFFFFFFFFFull;
     smp.g = m.g;
     HeteroStats hs{0, 0};
-    dv3 L = trace_hetero<false, LM>(S, GridTr::load<LM>(grid), smp, ld3(rays[i].o), ld3(rays[i].d), m, stats ? &hs : nullptr);
+    dv3 L = trace_hetero<false, LM, TL>(S, GridTrT<TL>::template load<LM>(grid), smp, ld3(rays[i].o), ld3(rays[i].d), m, stats ? &hs : nullptr);
     if (stats) {  /* vpt_debug_hetero_steps */
         atomicAdd(&stats[0], hs.tracks);
         atomicAdd(&stats[1], hs.steps);
@@ -134,7 +150,7 @@ __global__ __launch_bounds__(256) void trace_batch_hetero_kernel(const vpt_ray* 
 }
 
 /* estimator 11's per-sample call: the same on the ratio-tracking policy (no step statistics) */
-template <bool LM>
+template <bool LM, bool TL>
 __global__ __launch_bounds__(256) void trace_batch_hetero_ratio_kernel(const vpt_ray* __restrict__ rays,
                                                                        const uint64_t* __restrict__ states, int n, Medium m,
                                                                        const DevScene* __restrict__ S,
@@ -146,7 +162,7 @@ __global__ __launch_bounds__(256) void trace_batch_hetero_ratio_kernel(const vpt
     Sampler<false> smp;
     smp.X = states[i] & 0xFFFFFFFFFFFFull;
     smp.g = m.g;
-    dv3 L = trace_hetero<false, LM>(S, GridRatioTr<LM>::template load<LM>(grid), smp, ld3(rays[i].o), ld3(rays[i].d), m);
+    dv3 L = trace_hetero<false, LM, TL>(S, GridRatioTr<LM, TL>::template load<LM>(grid), smp, ld3(rays[i].o), ld3(rays[i].d), m);
     out[3 * i] = L.x;
     out[3 * i + 1] = L.y;
     out[3 * i + 2] = L.z;
@@ -154,7 +170,7 @@ __global__ __launch_bounds__(256) void trace_batch_hetero_ratio_kernel(const vpt
 }
 
 /* the density grid's walkers (vpt_grid.h), one ray per lane (vpt_grid_probe, vpt_grid_probe_lm) */
-template <bool LM>
+template <bool LM, bool TL>
 __global__ __launch_bounds__(256) void grid_probe_kernel(const vpt_grid_view* __restrict__ grid, double sigma_t,
                                                          const vpt_ray* __restrict__ rays, const double* __restrict__ tmax,
                                                          const uint64_t* __restrict__ states, int n, double* tau,
@@ -165,15 +181,16 @@ __global__ __launch_bounds__(256) void grid_probe_kernel(const vpt_grid_view* __
     const vpt_grid_view G = *grid;
     const double o[3] = {rays[i].o[0], rays[i].o[1], rays[i].o[2]}, d[3] = {rays[i].d[0], rays[i].d[1], rays[i].d[2]};
     uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
-    tau[i] = vpt_grid_tau(&G, o, d, tmax[i]);
+    tau[i] = TL ? vpt_grid_tau_tl(&G, o, d, tmax[i]) : vpt_grid_tau(&G, o, d, tmax[i]);
     uint32_t ns = 0;
-    t_coll[i] = LM ? vpt_grid_track_lm(&G, o, d, tmax[i], sigma_t, &X, &ns) : vpt_grid_track(&G, o, d, tmax[i], sigma_t, &X, &ns);
+    t_coll[i] = LM ? vpt_grid_track_lm_m(&G, TL, o, d, tmax[i], sigma_t, &X, &ns)
+                   : vpt_grid_track_m(&G, TL, o, d, tmax[i], sigma_t, &X, &ns);
     states_out[i] = X;
     if (steps) steps[i] = ns;
 }
 
 /* the ratio-tracking walkers (vpt_grid.h), one ray per lane (vpt_grid_ratio_probe) */
-template <bool LM>
+template <bool LM, bool TL>
 __global__ __launch_bounds__(256) void grid_ratio_probe_kernel(const vpt_grid_view* __restrict__ grid, double sigma_t,
                                                                const vpt_ray* __restrict__ rays, const double* __restrict__ tmax,
                                                                const uint64_t* __restrict__ states, int n, double* that,
@@ -185,7 +202,8 @@ __global__ __launch_bounds__(256) void grid_ratio_probe_kernel(const vpt_grid_vi
     const double o[3] = {rays[i].o[0], rays[i].o[1], rays[i].o[2]}, d[3] = {rays[i].d[0], rays[i].d[1], rays[i].d[2]};
     uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
     uint32_t ns = 0;
-    that[i] = LM ? vpt_grid_ratio_lm(&G, o, d, tmax[i], sigma_t, &X, &ns) : vpt_grid_ratio(&G, o, d, tmax[i], sigma_t, &X, &ns);
+    that[i] = LM ? vpt_grid_ratio_lm_m(&G, TL, o, d, tmax[i], sigma_t, &X, &ns)
+                 : vpt_grid_ratio_m(&G, TL, o, d, tmax[i], sigma_t, &X, &ns);
     states_out[i] = X;
     if (steps) steps[i] = ns;
 }
@@ -199,23 +217,23 @@ static void ratio_trace_launch(const vpt_ray* rays, const uint64_t* states, int 
 static int ratio_simple_launch(const KParams& K, const DevScene* S, bool lm, void* stream);
 static int ratio_launch(int device, const KParams& K, const DevScene* S, bool lm, void* stream);
 
-void vpt_int_hetero_trace_launch(int est, const vpt_ray* rays, const uint64_t* states, int n, const Medium& m,
+void VPT_HX(vpt_int_hetero_trace_launch)(int est, const vpt_ray* rays, const uint64_t* states, int n, const Medium& m,
                                  const DevScene* S, const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states,
                                  unsigned long long* stats)
 {
     if (est == VPT_HETERO_RATIO) return ratio_trace_launch(rays, states, n, m, S, grid, lm, out, out_states);
     const dim3 g((unsigned)((n + 255) / 256)), b(256);
-    if (lm) trace_batch_hetero_kernel<true><<<g, b>>>(rays, states, n, m, S, grid, out, out_states, stats);
-    else trace_batch_hetero_kernel<false><<<g, b>>>(rays, states, n, m, S, grid, out, out_states, stats);
+    if (lm) trace_batch_hetero_kernel<true, TLU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states, stats);
+    else trace_batch_hetero_kernel<false, TLU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states, stats);
 }
 
-void vpt_int_grid_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays, const double* tmax,
+void VPT_HX(vpt_int_grid_probe_launch)(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays, const double* tmax,
                                const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out,
                                uint32_t* steps)
 {
     const dim3 g((unsigned)((n + 255) / 256)), b(256);
-    if (lm) grid_probe_kernel<true><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, steps);
-    else grid_probe_kernel<false><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, steps);
+    if (lm) grid_probe_kernel<true, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, steps);
+    else grid_probe_kernel<false, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, steps);
 }
 /* run-time flags as compile-time constants: f(std::bool_constant<flag>{}...) */
 template <class F>
@@ -237,14 +255,14 @@ static int simple_launch(const KParams& K, const DevScene* S, bool lm, void* str
     return with_flags([&](auto lmc, auto count, auto f32) {
         constexpr int FB = decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64;
         dim3 grid((unsigned)((K.w + 15) / 16), (unsigned)((K.shard_rows + 15) / 16));
-        render_kernel_simple<EST, decltype(count)::value, FB, decltype(lmc)::value><<<grid, dim3(256), 0, (hipStream_t)stream>>>(K, S);
+        render_kernel_simple<EST, decltype(count)::value, FB, decltype(lmc)::value, TLU><<<grid, dim3(256), 0, (hipStream_t)stream>>>(K, S);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "render_kernel_simple<%d> launch: %s", EST, hipGetErrorString(e));
         return (int)VPT_OK;
     }, lm, K.counters != nullptr, K.fb == VPT_FB_F32);
 }
 
-int vpt_int_hetero_simple_launch(const KParams& K, const DevScene* S, bool lm, void* stream)
+int VPT_HX(vpt_int_hetero_simple_launch)(const KParams& K, const DevScene* S, bool lm, void* stream)
 {
     if (K.est == VPT_HETERO_RATIO) return ratio_simple_launch(K, S, lm, stream);
     return simple_launch<VPT_HETERO_FREE>(K, S, lm, stream);
@@ -269,11 +287,11 @@ static int persistent_launch(void (*kern)(KParams, const DevScene*), int device,
     return (int)VPT_OK;
 }
 
-int vpt_int_hetero_launch(int device, const KParams& K, const DevScene* S, bool lm, void* stream)
+int VPT_HX(vpt_int_hetero_launch)(int device, const KParams& K, const DevScene* S, bool lm, void* stream)
 {
     if (K.est == VPT_HETERO_RATIO) return ratio_launch(device, K, S, lm, stream);
     return with_flags([&](auto lmc, auto f32) {
-        return persistent_launch(hetero_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value>,
+        return persistent_launch(hetero_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU>,
                                  device, K, S, stream);
     }, lm, K.fb == VPT_FB_F32);
 }
@@ -283,17 +301,17 @@ static void ratio_trace_launch(const vpt_ray* rays, const uint64_t* states, int 
                                const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states)
 {
     const dim3 g((unsigned)((n + 255) / 256)), b(256);
-    if (lm) trace_batch_hetero_ratio_kernel<true><<<g, b>>>(rays, states, n, m, S, grid, out, out_states);
-    else trace_batch_hetero_ratio_kernel<false><<<g, b>>>(rays, states, n, m, S, grid, out, out_states);
+    if (lm) trace_batch_hetero_ratio_kernel<true, TLU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states);
+    else trace_batch_hetero_ratio_kernel<false, TLU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states);
 }
 
-void vpt_int_grid_ratio_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
+void VPT_HX(vpt_int_grid_ratio_probe_launch)(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
                                      const double* tmax, const uint64_t* states, int n, double* that, uint64_t* states_out,
                                      uint32_t* steps)
 {
     const dim3 g((unsigned)((n + 255) / 256)), b(256);
-    if (lm) grid_ratio_probe_kernel<true><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, that, states_out, steps);
-    else grid_ratio_probe_kernel<false><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, that, states_out, steps);
+    if (lm) grid_ratio_probe_kernel<true, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, that, states_out, steps);
+    else grid_ratio_probe_kernel<false, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, that, states_out, steps);
 }
 
 static int ratio_simple_launch(const KParams& K, const DevScene* S, bool lm, void* stream)
@@ -304,7 +322,7 @@ static int ratio_simple_launch(const KParams& K, const DevScene* S, bool lm, voi
 static int ratio_launch(int device, const KParams& K, const DevScene* S, bool lm, void* stream)
 {
     return with_flags([&](auto lmc, auto f32) {
-        return persistent_launch(hetero_ratio_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value>,
+        return persistent_launch(hetero_ratio_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU>,
                                  device, K, S, stream);
     }, lm, K.fb == VPT_FB_F32);
 }

@@ -208,90 +208,114 @@ int vpt_accum_select_host(const int32_t* tile_levels, const double* tile_err, in
 }
 
 /* ---- the density grid's walkers on host arrays (csrc/vpt_grid.h) ---- */
+/* the host probes' grid: the view, with its majorant grid (in `maj`) where block >= 1 */
+static void probe_view(vpt_grid_view* G, std::vector<float>& maj, const vpt_grid_desc* desc, const float* density, int block,
+                       int interp)
+{
+    const int32_t dims[3] = {desc->nx, desc->ny, desc->nz};
+    vpt_grid_view_init(G, dims, desc->lo, desc->hi, density, density);
+    G->interp = interp;
+    if (block) {
+        int32_t nb[3];
+        vpt_grid_majorant_counts(dims, block, nb);
+        maj.resize((size_t)nb[0] * (size_t)nb[1] * (size_t)nb[2]);
+        if (interp) vpt_grid_majorant_build_tl(dims, block, density, maj.data());
+        else vpt_grid_majorant_build(dims, block, density, maj.data());
+        vpt_grid_view_set_majorant(G, block, maj.data());
+    }
+}
+
+static int grid_probe_host(const char* who, const vpt_grid_desc* desc, const float* density, int block, int interp,
+                           double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states, int n, double* tau,
+                           double* t_coll, uint64_t* states_out, uint32_t* steps)
+{
+    vpt_clear_error();
+    if (!rays || !tmax || !states || n < 0) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
+    if (block < 0) return vpt_fail(VPT_E_INVALID, "%s: block %d (0 = the global majorant, else >= 1)", who, block);
+    if (interp != VPT_GRID_NEAREST && interp != VPT_GRID_TRILINEAR)
+        return vpt_fail(VPT_E_INVALID, "%s: interp %d (0 = nearest, 1 = trilinear)", who, interp);
+    int rc = vpt_int_grid_check(desc, density, who);
+    if (rc) return rc;
+    vpt_grid_view G;
+    std::vector<float> maj;
+    probe_view(&G, maj, desc, density, block, interp);
+    for (int i = 0; i < n; ++i) {
+        uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
+        uint32_t ns = 0;
+        if (tau) tau[i] = interp ? vpt_grid_tau_tl(&G, rays[i].o, rays[i].d, tmax[i]) : vpt_grid_tau(&G, rays[i].o, rays[i].d, tmax[i]);
+        const double tc = block ? vpt_grid_track_lm_m(&G, interp, rays[i].o, rays[i].d, tmax[i], sigma_t, &X, &ns)
+                                : vpt_grid_track_m(&G, interp, rays[i].o, rays[i].d, tmax[i], sigma_t, &X, &ns);
+        if (t_coll) t_coll[i] = tc;
+        if (states_out) states_out[i] = X;
+        if (steps) steps[i] = ns;
+    }
+    return VPT_OK;
+}
+
+static int grid_ratio_probe_host(const char* who, const vpt_grid_desc* desc, const float* density, int block, int interp,
+                                 double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states, int n,
+                                 double* that, uint64_t* states_out, uint32_t* steps)
+{
+    vpt_clear_error();
+    if (!rays || !tmax || !states || n < 0) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
+    if (block < 0) return vpt_fail(VPT_E_INVALID, "%s: block %d (0 = the global majorant, else >= 1)", who, block);
+    if (interp != VPT_GRID_NEAREST && interp != VPT_GRID_TRILINEAR)
+        return vpt_fail(VPT_E_INVALID, "%s: interp %d (0 = nearest, 1 = trilinear)", who, interp);
+    int rc = vpt_int_grid_check(desc, density, who);
+    if (rc) return rc;
+    vpt_grid_view G;
+    std::vector<float> maj;
+    probe_view(&G, maj, desc, density, block, interp);
+    for (int i = 0; i < n; ++i) {
+        uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
+        uint32_t ns = 0;
+        const double T = block ? vpt_grid_ratio_lm_m(&G, interp, rays[i].o, rays[i].d, tmax[i], sigma_t, &X, &ns)
+                               : vpt_grid_ratio_m(&G, interp, rays[i].o, rays[i].d, tmax[i], sigma_t, &X, &ns);
+        if (that) that[i] = T;
+        if (states_out) states_out[i] = X;
+        if (steps) steps[i] = ns;
+    }
+    return VPT_OK;
+}
+
 int vpt_grid_probe_host(const vpt_grid_desc* desc, const float* density, double sigma_t, const vpt_ray* rays,
                         const double* tmax, const uint64_t* states, int n, double* tau, double* t_coll,
                         uint64_t* states_out)
 {
-    vpt_clear_error();
-    if (!rays || !tmax || !states || n < 0) return vpt_fail(VPT_E_INVALID, "vpt_grid_probe_host: bad arguments");
-    int rc = vpt_int_grid_check(desc, density, "vpt_grid_probe_host");
-    if (rc) return rc;
-    const int32_t dims[3] = {desc->nx, desc->ny, desc->nz};
-    vpt_grid_view G;
-    vpt_grid_view_init(&G, dims, desc->lo, desc->hi, density, density);
-    for (int i = 0; i < n; ++i) {
-        uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
-        if (tau) tau[i] = vpt_grid_tau(&G, rays[i].o, rays[i].d, tmax[i]);
-        const double tc = vpt_grid_track(&G, rays[i].o, rays[i].d, tmax[i], sigma_t, &X, nullptr);
-        if (t_coll) t_coll[i] = tc;
-        if (states_out) states_out[i] = X;
-    }
-    return VPT_OK;
+    return grid_probe_host("vpt_grid_probe_host", desc, density, 0, 0, sigma_t, rays, tmax, states, n, tau, t_coll, states_out,
+                           nullptr);
 }
 
 int vpt_grid_probe_host_lm(const vpt_grid_desc* desc, const float* density, int block, double sigma_t, const vpt_ray* rays,
                            const double* tmax, const uint64_t* states, int n, double* tau, double* t_coll,
                            uint64_t* states_out, uint32_t* steps)
 {
-    vpt_clear_error();
-    if (!rays || !tmax || !states || n < 0) return vpt_fail(VPT_E_INVALID, "vpt_grid_probe_host_lm: bad arguments");
-    if (block < 0) return vpt_fail(VPT_E_INVALID, "vpt_grid_probe_host_lm: block %d (0 = the global majorant, else >= 1)", block);
-    int rc = vpt_int_grid_check(desc, density, "vpt_grid_probe_host_lm");
-    if (rc) return rc;
-    const int32_t dims[3] = {desc->nx, desc->ny, desc->nz};
-    vpt_grid_view G;
-    vpt_grid_view_init(&G, dims, desc->lo, desc->hi, density, density);
-    std::vector<float> maj;
-    if (block) {
-        int32_t nb[3];
-        vpt_grid_majorant_counts(dims, block, nb);
-        maj.resize((size_t)nb[0] * (size_t)nb[1] * (size_t)nb[2]);
-        vpt_grid_majorant_build(dims, block, density, maj.data());
-        vpt_grid_view_set_majorant(&G, block, maj.data());
-    }
-    for (int i = 0; i < n; ++i) {
-        uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
-        uint32_t ns = 0;
-        if (tau) tau[i] = vpt_grid_tau(&G, rays[i].o, rays[i].d, tmax[i]);
-        const double tc = block ? vpt_grid_track_lm(&G, rays[i].o, rays[i].d, tmax[i], sigma_t, &X, &ns)
-                                : vpt_grid_track(&G, rays[i].o, rays[i].d, tmax[i], sigma_t, &X, &ns);
-        if (t_coll) t_coll[i] = tc;
-        if (states_out) states_out[i] = X;
-        if (steps) steps[i] = ns;
-    }
-    return VPT_OK;
+    return grid_probe_host("vpt_grid_probe_host_lm", desc, density, block, 0, sigma_t, rays, tmax, states, n, tau, t_coll,
+                           states_out, steps);
+}
+
+int vpt_grid_probe_host_ex(const vpt_grid_desc* desc, const float* density, int block, int interp, double sigma_t,
+                           const vpt_ray* rays, const double* tmax, const uint64_t* states, int n, double* tau,
+                           double* t_coll, uint64_t* states_out, uint32_t* steps)
+{
+    return grid_probe_host("vpt_grid_probe_host_ex", desc, density, block, interp, sigma_t, rays, tmax, states, n, tau, t_coll,
+                           states_out, steps);
 }
 
 int vpt_grid_ratio_probe_host(const vpt_grid_desc* desc, const float* density, int block, double sigma_t,
                               const vpt_ray* rays, const double* tmax, const uint64_t* states, int n, double* that,
                               uint64_t* states_out, uint32_t* steps)
 {
-    vpt_clear_error();
-    if (!rays || !tmax || !states || n < 0) return vpt_fail(VPT_E_INVALID, "vpt_grid_ratio_probe_host: bad arguments");
-    if (block < 0) return vpt_fail(VPT_E_INVALID, "vpt_grid_ratio_probe_host: block %d (0 = the global majorant, else >= 1)", block);
-    int rc = vpt_int_grid_check(desc, density, "vpt_grid_ratio_probe_host");
-    if (rc) return rc;
-    const int32_t dims[3] = {desc->nx, desc->ny, desc->nz};
-    vpt_grid_view G;
-    vpt_grid_view_init(&G, dims, desc->lo, desc->hi, density, density);
-    std::vector<float> maj;
-    if (block) {
-        int32_t nb[3];
-        vpt_grid_majorant_counts(dims, block, nb);
-        maj.resize((size_t)nb[0] * (size_t)nb[1] * (size_t)nb[2]);
-        vpt_grid_majorant_build(dims, block, density, maj.data());
-        vpt_grid_view_set_majorant(&G, block, maj.data());
-    }
-    for (int i = 0; i < n; ++i) {
-        uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
-        uint32_t ns = 0;
-        const double T = block ? vpt_grid_ratio_lm(&G, rays[i].o, rays[i].d, tmax[i], sigma_t, &X, &ns)
-                               : vpt_grid_ratio(&G, rays[i].o, rays[i].d, tmax[i], sigma_t, &X, &ns);
-        if (that) that[i] = T;
-        if (states_out) states_out[i] = X;
-        if (steps) steps[i] = ns;
-    }
-    return VPT_OK;
+    return grid_ratio_probe_host("vpt_grid_ratio_probe_host", desc, density, block, 0, sigma_t, rays, tmax, states, n, that,
+                                 states_out, steps);
+}
+
+int vpt_grid_ratio_probe_host_ex(const vpt_grid_desc* desc, const float* density, int block, int interp, double sigma_t,
+                                 const vpt_ray* rays, const double* tmax, const uint64_t* states, int n, double* that,
+                                 uint64_t* states_out, uint32_t* steps)
+{
+    return grid_ratio_probe_host("vpt_grid_ratio_probe_host_ex", desc, density, block, interp, sigma_t, rays, tmax, states, n,
+                                 that, states_out, steps);
 }
 
 /* ---- PPM ---- */

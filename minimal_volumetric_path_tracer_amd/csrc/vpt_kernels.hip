@@ -241,6 +241,8 @@ struct vpt_context {
     int maj_block = 0;
     float* d_maj = nullptr;
     vpt_grid_view h_grid = {};
+    /* trilinear interpolation (vpt_set_grid_interpolation): the context's mode, in h_grid.interp of every grid */
+    int grid_interp = 0;
 };
 
 /* The stream's slot, created on first use (or taken over from an idle stream once MAX_STREAM_SLOTS
@@ -462,15 +464,16 @@ static bool hetero_simple_kernel()
  * counting mode and VPT_SIMPLE_KERNEL=1: render_kernel_simple<10 or 11> */
 static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
 {
-    const bool lm = ctx->h_grid.block > 0;
-    if (K.counters || hetero_simple_kernel()) return vpt_int_hetero_simple_launch(K, ctx->d_scene, lm, stream);
+    const bool lm = ctx->h_grid.block > 0, tl = ctx->h_grid.interp != 0;
+    if (K.counters || hetero_simple_kernel())
+        return (tl ? vpt_int_hetero_simple_launch_tl : vpt_int_hetero_simple_launch)(K, ctx->d_scene, lm, stream);
     std::lock_guard<std::mutex> lock(ctx->mu);
     StreamSlot* sl = nullptr;
     int rc = stream_slot(ctx, stream, 0, &sl);
     if (rc) return rc;
     K.queue = sl->d_queue;
     HIP_OK(hipMemsetAsync(K.queue, 0, sizeof(unsigned), stream));
-    rc = vpt_int_hetero_launch(ctx->device, K, ctx->d_scene, lm, stream);
+    rc = (tl ? vpt_int_hetero_launch_tl : vpt_int_hetero_launch)(ctx->device, K, ctx->d_scene, lm, stream);
     if (rc) return rc;
     return slot_done(sl, stream);
 }
@@ -836,13 +839,14 @@ int vpt_set_scene(vpt_context* ctx, const vpt_sphere* s, int n)
 }
 
 /* the block maxima of `density` (host) for block size B >= 1 on the device (*d_maj, the caller frees) and in
- * the view */
+ * the view; the dilated maxima where the view's field is trilinear (vpt_grid.h) */
 static hipError_t majorant_upload(vpt_grid_view* G, int B, const float* density, float** d_maj)
 {
     int32_t nb[3];
     vpt_grid_majorant_counts(G->n, B, nb);
     std::vector<float> maj((size_t)nb[0] * (size_t)nb[1] * (size_t)nb[2]);
-    vpt_grid_majorant_build(G->n, B, density, maj.data());
+    if (G->interp) vpt_grid_majorant_build_tl(G->n, B, density, maj.data());
+    else vpt_grid_majorant_build(G->n, B, density, maj.data());
     hipError_t e = hipMalloc((void**)d_maj, maj.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(*d_maj, maj.data(), maj.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) vpt_grid_view_set_majorant(G, B, *d_maj);
@@ -860,7 +864,7 @@ int vpt_set_density_grid(vpt_context* ctx, const vpt_grid_desc* desc, const floa
         if (ctx->d_maj) (void)hipFree(ctx->d_maj);
         ctx->d_rho = nullptr;
         ctx->d_maj = nullptr;
-        ctx->has_grid = 0;  /* maj_block stays: the next grid gets its majorant grid */
+        ctx->has_grid = 0;  /* maj_block and grid_interp stay: the next grid gets its majorant grid and its mode */
         return VPT_OK;
     }
     int rc = vpt_int_grid_check(desc, density, "vpt_set_density_grid");
@@ -871,6 +875,7 @@ int vpt_set_density_grid(vpt_context* ctx, const vpt_grid_desc* desc, const floa
     HIP_OK(hipMalloc((void**)&d_rho, bytes));
     vpt_grid_view G;
     vpt_grid_view_init(&G, dims, desc->lo, desc->hi, density, d_rho);  /* the majorant: scanned on the host */
+    G.interp = ctx->grid_interp;
     hipError_t e = hipMemcpy(d_rho, density, bytes, hipMemcpyHostToDevice);
     float* d_maj = nullptr;
     if (e == hipSuccess && ctx->maj_block) e = majorant_upload(&G, ctx->maj_block, density, &d_maj);
@@ -925,6 +930,42 @@ int vpt_set_grid_majorant_block(vpt_context* ctx, int block)
     return VPT_OK;
 }
 
+int vpt_set_grid_interpolation(vpt_context* ctx, int mode)
+{
+    vpt_clear_error();
+    if (!ctx) return vpt_fail(VPT_E_INVALID, "vpt_set_grid_interpolation: NULL context");
+    if (mode != VPT_GRID_NEAREST && mode != VPT_GRID_TRILINEAR)
+        return vpt_fail(VPT_E_INVALID, "vpt_set_grid_interpolation: mode %d (0 = nearest, 1 = trilinear)", mode);
+    if (!ctx->has_grid || ctx->h_grid.interp == mode) {  /* applied when a grid is set */
+        ctx->grid_interp = mode;
+        return VPT_OK;
+    }
+    HIP_OK(hipSetDevice(ctx->device));
+    HIP_OK(hipDeviceSynchronize());  /* nothing in flight reads the view or the previous majorant grid */
+    vpt_grid_view G = ctx->h_grid;
+    G.interp = mode;
+    float* d_maj = nullptr;
+    hipError_t e = hipSuccess;
+    if (G.block) {  /* the majorant grid follows the mode: rebuilt from the device's copy of the voxels */
+        const size_t nv = (size_t)G.n[0] * (size_t)G.n[1] * (size_t)G.n[2];
+        std::vector<float> rho(nv);
+        e = hipMemcpy(rho.data(), ctx->d_rho, nv * sizeof(float), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = majorant_upload(&G, G.block, rho.data(), &d_maj);
+    }
+    if (e == hipSuccess) e = hipMemcpy(ctx->d_grid, &G, sizeof G, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (d_maj) (void)hipFree(d_maj);
+        return vpt_fail(VPT_E_HIP, "vpt_set_grid_interpolation: %s", hipGetErrorString(e));
+    }
+    if (G.block) {
+        if (ctx->d_maj) (void)hipFree(ctx->d_maj);
+        ctx->d_maj = d_maj;
+    }
+    ctx->h_grid = G;
+    ctx->grid_interp = mode;
+    return VPT_OK;
+}
+
 /* vpt_grid_probe (lm false: the global-majorant track whatever the context's setting) and vpt_grid_probe_lm */
 static int grid_probe(vpt_context* ctx, bool lm, double sigma_t, const vpt_ray* rays, const double* tmax,
                       const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out, uint32_t* steps)
@@ -962,7 +1003,8 @@ static int grid_probe(vpt_context* ctx, bool lm, double sigma_t, const vpt_ray* 
     if (e == hipSuccess) e = hipMemcpy(ds, states, sizeof(uint64_t) * nn, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dtm, tmax, sizeof(double) * nn, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        vpt_int_grid_probe_launch(dview, lm && ctx->h_grid.block > 0, sigma_t, dr, dtm, ds, n, dtau, dtc, dso, dst);
+        (ctx->h_grid.interp ? vpt_int_grid_probe_launch_tl : vpt_int_grid_probe_launch)(dview, lm && ctx->h_grid.block > 0, sigma_t, dr,
+                                                                                        dtm, ds, n, dtau, dtc, dso, dst);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(tau, dtau, sizeof(double) * nn, hipMemcpyDeviceToHost);
@@ -1017,7 +1059,8 @@ int vpt_grid_ratio_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, 
     if (e == hipSuccess) e = hipMemcpy(ds, states, sizeof(uint64_t) * nn, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dtm, tmax, sizeof(double) * nn, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        vpt_int_grid_ratio_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, sigma_t, dr, dtm, ds, n, dth, dso, dst);
+        (ctx->h_grid.interp ? vpt_int_grid_ratio_probe_launch_tl : vpt_int_grid_ratio_probe_launch)(
+            ctx->d_grid, ctx->h_grid.block > 0, sigma_t, dr, dtm, ds, n, dth, dso, dst);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(that, dth, sizeof(double) * nn, hipMemcpyDeviceToHost);
@@ -1145,7 +1188,7 @@ static int trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* ray
         case 7: trace_batch_kernel<7><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         case 8: trace_batch_kernel<8><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         case VPT_HETERO_FREE:
-        case VPT_HETERO_RATIO: vpt_int_hetero_trace_launch(m->estimator, dr, ds, n, mm, ctx->d_scene, ctx->d_grid, ctx->h_grid.block > 0, dout, dso, stats); break;
+        case VPT_HETERO_RATIO: (ctx->h_grid.interp ? vpt_int_hetero_trace_launch_tl : vpt_int_hetero_trace_launch)(m->estimator, dr, ds, n, mm, ctx->d_scene, ctx->d_grid, ctx->h_grid.block > 0, dout, dso, stats); break;
         default: trace_batch_kernel<9><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         }
         e = hipGetLastError();

@@ -241,6 +241,17 @@ int vpt_multi_set_grid_majorant_block(vpt_multi* m, int block)
     return VPT_OK;
 }
 
+int vpt_multi_set_grid_interpolation(vpt_multi* m, int mode)
+{
+    vpt_clear_error();
+    if (!m) return vpt_fail(VPT_E_INVALID, "vpt_multi_set_grid_interpolation: NULL handle");
+    for (int g = 0; g < m->n; ++g) {
+        int rc = vpt_set_grid_interpolation(m->ctx[g], mode);
+        if (rc) return rc;
+    }
+    return VPT_OK;
+}
+
 int vpt_multi_render(vpt_multi* m, const vpt_params* p, void* h_out)
 {
     vpt_clear_error();

@@ -1,9 +1,9 @@
 /*
  * vpt_render_simple.h -- a render's launch parameters (KParams), the per-pixel helpers every render kernel but
  * the pool kernel uses (row mapping, camera ray, pixel store), and the one-lane-per-pixel render kernel, shared by
- * the two translation units that instantiate it: vpt_kernels.hip (estimators 0-9) and vpt_hetero.hip (estimator 10,
- * so that the code object of vpt_kernels.hip -- the tuned pool kernels and their placement -- stays what it was
- * before estimator 10 existed).  render_kernel_simple replaces main()'s OpenMP pixel loop (src/rt.cpp:767-805):
+ * the translation units that instantiate it: vpt_kernels.hip (estimators 0-9) and vpt_hetero.hip (estimators 10 and
+ * 11; vpt_hetero_tl.hip compiles that file again for the trilinear field), so that the code object of
+ * vpt_kernels.hip -- the tuned pool kernels and their placement -- stays what it was before estimator 10 existed.  render_kernel_simple replaces main()'s OpenMP pixel loop (src/rt.cpp:767-805):
  * one lane owns one pixel and runs its spp camera samples (src/rt.cpp:786-798) through the estimator,
  * accumulating in FP64 in the reference's order, then writes the average (src/rt.cpp:800) once.
  */
@@ -89,8 +89,8 @@ namespace {
 
 using namespace vpt;
 
-/* LM: estimators 10 and 11 only -- the grid has a majorant grid (vpt_hetero.h) */
-template <int EST, bool COUNT, int FB, bool LM = false>
+/* LM, TL: estimators 10 and 11 only -- the grid has a majorant grid, the field is trilinear (vpt_hetero.h) */
+template <int EST, bool COUNT, int FB, bool LM = false, bool TL = false>
 __global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const DevScene* __restrict__ S)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -118,9 +118,9 @@ __global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const Dev
         smp.cnt.draw_mismatch = 0;
         const dv3 dir = camera_dir(P, smp, x, row.y);
         dv3 L;
-        if constexpr (EST == VPT_HETERO_FREE) L = trace_hetero<COUNT, LM>(S, GridTr::load<LM>(P.grid), smp, o, dir, m);
+        if constexpr (EST == VPT_HETERO_FREE) L = trace_hetero<COUNT, LM, TL>(S, GridTrT<TL>::template load<LM>(P.grid), smp, o, dir, m);
         else if constexpr (EST == VPT_HETERO_RATIO)
-            L = trace_hetero<COUNT, LM>(S, GridRatioTr<LM>::template load<LM>(P.grid), smp, o, dir, m);
+            L = trace_hetero<COUNT, LM, TL>(S, GridRatioTr<LM, TL>::template load<LM>(P.grid), smp, o, dir, m);
         else L = trace_sample<EST, COUNT>(S, smp, o, dir, m, EST == 6 ? march_oc : nullptr);
         acc = add(L, acc);
         if (COUNT) {

@@ -87,13 +87,32 @@ def _probe_args(rays, tmax, states):
     return r, t, s, np.zeros(len(r)), np.zeros(len(r)), np.zeros(len(r), dtype=np.uint64)
 
 
-def grid_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, states, majorant_block: int = 0, return_steps: bool = False):
+INTERPOLATIONS = {"nearest": _lib.GRID_NEAREST, "trilinear": _lib.GRID_TRILINEAR}
+
+
+def _interp_mode(name) -> int:
+    """the vpt_grid_interp of "nearest" / "trilinear"; any other name is VPT_E_INVALID"""
+    if name not in INTERPOLATIONS:
+        raise _lib.VPTError(_lib.VPT_E_INVALID, f"interpolation {name!r} (one of {', '.join(INTERPOLATIONS)})")
+    return INTERPOLATIONS[name]
+
+
+def grid_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, states, majorant_block: int = 0, return_steps: bool = False,
+                    interpolation: str = "nearest"):
     """csrc/vpt_grid.h on the host (vpt_grid_probe_host, no GPU): per ray (unit direction) the optical depth of
     the grid over t in [0, tmax], the delta-tracking result from `states` (-1: none, NaN: step cap) and the
     erand48 states after the track.  majorant_block > 0 tracks with local majorants on super-voxels of that
-    many voxels per axis (vpt_grid_probe_host_lm); return_steps appends the tentative steps of each track."""
+    many voxels per axis (vpt_grid_probe_host_lm); return_steps appends the tentative steps of each track;
+    interpolation "trilinear" reads the field trilinearly (vpt_grid_probe_host_ex)."""
+    mode = _interp_mode(interpolation)
     d, r = _grid_args(rho, lo, hi)
     ry, t, s, tau, tc, so = _probe_args(rays, tmax, states)
+    if mode:
+        steps = np.zeros(len(ry), dtype=np.uint32)
+        check(lib().vpt_grid_probe_host_ex(byref(d), r.ctypes.data, int(majorant_block), mode, float(sigma_t), ry.ctypes.data,
+                                           t.ctypes.data, s.ctypes.data, len(ry), tau.ctypes.data, tc.ctypes.data,
+                                           so.ctypes.data, steps.ctypes.data))
+        return (tau, tc, so, steps) if return_steps else (tau, tc, so)
     if not majorant_block and not return_steps:
         check(lib().vpt_grid_probe_host(byref(d), r.ctypes.data, float(sigma_t), ry.ctypes.data, t.ctypes.data,
                                         s.ctypes.data, len(ry), tau.ctypes.data, tc.ctypes.data, so.ctypes.data))
@@ -105,28 +124,40 @@ def grid_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, states, majorant_bl
     return (tau, tc, so, steps) if return_steps else (tau, tc, so)
 
 
-def grid_ratio_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, states, majorant_block: int = 0):
+def grid_ratio_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, states, majorant_block: int = 0,
+                          interpolation: str = "nearest"):
     """csrc/vpt_grid.h's ratio tracking on the host (vpt_grid_ratio_probe_host, no GPU): per ray (unit direction)
     the estimate That of exp(-sigma_t tau) over t in [0, tmax] from `states` (NaN: step cap), the erand48 states
     after it and its draws.  majorant_block > 0 walks with local majorants on super-voxels of that many voxels
-    per axis."""
+    per axis; interpolation "trilinear" reads the field trilinearly (vpt_grid_ratio_probe_host_ex)."""
+    mode = _interp_mode(interpolation)
     d, r = _grid_args(rho, lo, hi)
     ry, t, s, that, _, so = _probe_args(rays, tmax, states)
     steps = np.zeros(len(ry), dtype=np.uint32)
+    if mode:
+        check(lib().vpt_grid_ratio_probe_host_ex(byref(d), r.ctypes.data, int(majorant_block), mode, float(sigma_t),
+                                                 ry.ctypes.data, t.ctypes.data, s.ctypes.data, len(ry), that.ctypes.data,
+                                                 so.ctypes.data, steps.ctypes.data))
+        return that, so, steps
     check(lib().vpt_grid_ratio_probe_host(byref(d), r.ctypes.data, int(majorant_block), float(sigma_t), ry.ctypes.data,
                                           t.ctypes.data, s.ctypes.data, len(ry), that.ctypes.data, so.ctypes.data,
                                           steps.ctypes.data))
     return that, so, steps
 
 
-def _set_grid_with_block(owner, block, upload) -> None:
-    """set_density_grid(..., majorant_block=block) of Tracer and MultiTracer: the grid first -- a rejected grid
-    leaves the grid and the block size as they were -- then the block size, where it changes."""
+def _set_grid_with_block(owner, block, upload, interpolation=None) -> None:
+    """set_density_grid(..., majorant_block=block, interpolation=...) of Tracer and MultiTracer: the grid first -- a
+    rejected grid leaves the grid and the settings as they were -- then the block size and the interpolation, where
+    they change."""
     if block is not None and int(block) < 0:
         owner.set_majorant_block(block)  # raises VPT_E_INVALID before anything is uploaded
+    if interpolation is not None:
+        _interp_mode(interpolation)  # the same for an unknown name
     upload()
     if block is not None and int(block) != owner._majorant_block:
         owner.set_majorant_block(block)
+    if interpolation is not None and interpolation != owner._grid_interpolation:
+        owner.set_grid_interpolation(interpolation)
 
 
 @dataclass
@@ -180,6 +211,7 @@ class Tracer:
         self._ctx = h
         self.device = device
         self._majorant_block = 0  # the context's setting (vpt_set_grid_majorant_block)
+        self._grid_interpolation = "nearest"  # the context's setting (vpt_set_grid_interpolation)
         self.set_scene(default_scene() if spheres is None else spheres)
 
     def close(self) -> None:
@@ -199,13 +231,15 @@ class Tracer:
         self.spheres = s
 
     # ---- heterogeneous medium (estimator "hetero") ----
-    def set_density_grid(self, rho, lo, hi, majorant_block: Optional[int] = None) -> None:
+    def set_density_grid(self, rho, lo, hi, majorant_block: Optional[int] = None,
+                         interpolation: Optional[str] = None) -> None:
         """The density grid of estimator "hetero": rho of shape [nz, ny, nx] (float32, finite, >= 0) in the world
         box [lo, hi], zero outside; sigma_a / sigma_s are then per unit density.  Kept across set_scene.
         majorant_block: set_majorant_block for this and later grids (None leaves the tracer's setting alone); a
-        grid that is rejected leaves the setting as it was."""
+        grid that is rejected leaves the setting as it was.  interpolation: set_grid_interpolation in the same way."""
         d, r = _grid_args(rho, lo, hi)
-        _set_grid_with_block(self, majorant_block, lambda: check(lib().vpt_set_density_grid(self._ctx, byref(d), r.ctypes.data)))
+        _set_grid_with_block(self, majorant_block, lambda: check(lib().vpt_set_density_grid(self._ctx, byref(d), r.ctypes.data)),
+                             interpolation)
 
     def set_majorant_block(self, block: int) -> None:
         """Local majorants for delta tracking: super-voxels of `block` voxels per axis, each with its own
@@ -213,6 +247,13 @@ class Tracer:
         and to every later one.  Fewer null collisions on sparse fields; the same estimator, other draws."""
         check(lib().vpt_set_grid_majorant_block(self._ctx, int(block)))
         self._majorant_block = int(block)
+
+    def set_grid_interpolation(self, interpolation: str) -> None:
+        """How the density is read between the voxel centres: "nearest" (the default: constant per voxel) or
+        "trilinear" (a smooth field, clamped at the border of the box; include/vpt.h vpt_set_grid_interpolation).
+        Belongs to the tracer: applied to the current grid and to every later one."""
+        check(lib().vpt_set_grid_interpolation(self._ctx, _interp_mode(interpolation)))
+        self._grid_interpolation = interpolation
 
     def clear_density_grid(self) -> None:
         check(lib().vpt_set_density_grid(self._ctx, None, None))
@@ -467,19 +508,27 @@ class MultiTracer:
         self._m = h
         self.n_gpus = n_gpus
         self._majorant_block = 0
+        self._grid_interpolation = "nearest"
         s = np.ascontiguousarray(default_scene() if spheres is None else spheres, dtype=SPHERE_DTYPE)
         check(lib().vpt_multi_set_scene(self._m, s.ctypes.data, len(s)))
         self.spheres = s
 
-    def set_density_grid(self, rho, lo, hi, majorant_block: Optional[int] = None) -> None:
+    def set_density_grid(self, rho, lo, hi, majorant_block: Optional[int] = None,
+                         interpolation: Optional[str] = None) -> None:
         """Tracer.set_density_grid on every rank's context."""
         d, r = _grid_args(rho, lo, hi)
-        _set_grid_with_block(self, majorant_block, lambda: check(lib().vpt_multi_set_density_grid(self._m, byref(d), r.ctypes.data)))
+        _set_grid_with_block(self, majorant_block, lambda: check(lib().vpt_multi_set_density_grid(self._m, byref(d), r.ctypes.data)),
+                             interpolation)
 
     def set_majorant_block(self, block: int) -> None:
         """Tracer.set_majorant_block on every rank's context."""
         check(lib().vpt_multi_set_grid_majorant_block(self._m, int(block)))
         self._majorant_block = int(block)
+
+    def set_grid_interpolation(self, interpolation: str) -> None:
+        """Tracer.set_grid_interpolation on every rank's context."""
+        check(lib().vpt_multi_set_grid_interpolation(self._m, _interp_mode(interpolation)))
+        self._grid_interpolation = interpolation
 
     def clear_density_grid(self) -> None:
         check(lib().vpt_multi_set_density_grid(self._m, None, None))
