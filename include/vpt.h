@@ -190,6 +190,17 @@ int vpt_set_grid_majorant_block(vpt_context* ctx, int block);
  * every later vpt_set_density_grid, and survives a clear.  Any other mode -> VPT_E_INVALID, nothing changes. */
 typedef enum { VPT_GRID_NEAREST = 0, VPT_GRID_TRILINEAR = 1 } vpt_grid_interp;
 int vpt_set_grid_interpolation(vpt_context* ctx, int mode);
+/* Volumetric emission for estimators VPT_HETERO_FREE and VPT_HETERO_RATIO (csrc/vpt_grid.h, csrc/vpt_hetero.h): an
+ * emission grid eps of the density grid's nx x ny x nz float32 values (finite, >= 0; the same box, layout and lookup --
+ * nearest or trilinear -- as the density) and a colour rgb (finite, >= 0).  The medium's source term is
+ * sigma_a rho(x) eps(x) rgb, radiance per unit length: Kirchhoff's form, so where the medium does not absorb (sigma_a = 0
+ * or rho = 0) it does not glow.  Scored by the collision estimator on every tentative collision of the delta track, at
+ * every depth, without a random draw: paths, draw counts and end states are those of the same render without emission.
+ * Copied to the device (synchronous); eps NULL clears it (rgb is ignored).  Without a density grid, or with a NaN,
+ * negative or infinite eps or rgb value -> VPT_E_INVALID, nothing changes.  The emission grid belongs to the density
+ * grid: setting or clearing that one clears it; vpt_set_grid_majorant_block and vpt_set_grid_interpolation leave it in
+ * place.  vpt_trace_batch, vpt_render*, vpt_count_work honour it; the progressive accumulator supports neither estimator. */
+int vpt_set_emission_grid(vpt_context* ctx, const float* eps, const double rgb[3]);
 
 /* Renders into a DEVICE buffer on `stream` (a hipStream_t, NULL = default stream); returns
  * after enqueueing.  d_out: vpt_shard_rows(p) * width * 3 elements of fb_format, the
@@ -219,6 +230,8 @@ int vpt_multi_set_density_grid(vpt_multi* m, const vpt_grid_desc* desc, const fl
 int vpt_multi_set_grid_majorant_block(vpt_multi* m, int block);
 /* vpt_set_grid_interpolation on every context of the handle */
 int vpt_multi_set_grid_interpolation(vpt_multi* m, int mode);
+/* vpt_set_emission_grid on every context of the handle */
+int vpt_multi_set_emission_grid(vpt_multi* m, const float* eps, const double rgb[3]);
 int vpt_multi_render(vpt_multi* m, const vpt_params* p, void* h_out);
 void vpt_multi_destroy(vpt_multi* m);
 /* one-shot: create, set the scene, render, destroy */
@@ -369,6 +382,18 @@ int vpt_grid_probe_host_ex(const vpt_grid_desc* desc, const float* density, int 
 int vpt_grid_ratio_probe_host_ex(const vpt_grid_desc* desc, const float* density, int block, int interp, double sigma_t,
                                  const vpt_ray* rays, const double* tmax, const uint64_t* states, int n, double* that,
                                  uint64_t* states_out, uint32_t* steps);
+
+/* Emission probe (csrc/vpt_grid.h: vpt_grid_track_em_m, vpt_grid_track_lm_em_m): the delta track of vpt_grid_probe_lm from
+ * states[i] over t in [0, tmax[i]] with the collision estimator of the emission grid: t_coll[i], states_out[i] and steps[i]
+ * (may be NULL) are that probe's bit for bit, esum[i] = the sum of rho eps / mu over the track's tentative collisions, whose
+ * expectation is sigma_t times the integral of T rho eps along the tracked segment.  The GPU probe reads the context's
+ * emission grid (VPT_E_INVALID without one) and honours its majorant block and interpolation; the host probe takes the
+ * density, eps (both nx x ny x nz), the block size and the mode.  Host arrays, synchronous. */
+int vpt_grid_emission_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
+                            int n, double* t_coll, double* esum, uint64_t* states_out, uint32_t* steps);
+int vpt_grid_emission_probe_host(const vpt_grid_desc* desc, const float* density, const float* eps, int block, int interp,
+                                 double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states, int n,
+                                 double* t_coll, double* esum, uint64_t* states_out, uint32_t* steps);
 
 /* PPM writer of main() (src/rt.cpp:812-820): clamp to [0,1] (src/rt.cpp:803), gamma 1/2.2,
  * int(v*255 + .5) (include/mathUtilities.h:43-45), "P3\n%d %d\n255\n" then "%d %d %d " per

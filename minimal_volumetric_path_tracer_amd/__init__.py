@@ -13,6 +13,7 @@ from .tracer import (
     Tracer,
     default_scene,
     encode_ppm,
+    grid_emission_probe_host,
     grid_probe_host,
     grid_ratio_probe_host,
     render_multi,
@@ -23,6 +24,6 @@ from .tracer import (
 
 __all__ = [
     "FB_F32", "FB_F64", "FREE_FLIGHT", "MIS_EQUIANGULAR", "EXPLICIT_FREE", "IMPLICIT_FREE", "EXPLICIT_EQUIANGULAR", "SURFACE_PT", "RAY_MARCHING",
-    "RAY_MARCHING_SA", "RAY_MARCHING_GLOBAL", "RAY_MARCHING_EXPLICIT", "HETERO_FREE", "HETERO_RATIO", "grid_probe_host", "grid_ratio_probe_host", "RAY_DTYPE", "SPHERE_DTYPE", "VPTError", "build_id", "lib",
+    "RAY_MARCHING_SA", "RAY_MARCHING_GLOBAL", "RAY_MARCHING_EXPLICIT", "HETERO_FREE", "HETERO_RATIO", "grid_probe_host", "grid_ratio_probe_host", "grid_emission_probe_host", "RAY_DTYPE", "SPHERE_DTYPE", "VPTError", "build_id", "lib",
     "Accumulator", "MultiTracer", "render_multi", "Ray", "RenderConfig", "Sphere", "Tracer", "default_scene", "encode_ppm", "scene", "stream_state", "write_ppm",
 ]

@@ -107,6 +107,7 @@ PROTOTYPES = [
     ("vpt_set_density_grid", c_int, [c_void_p, POINTER(vpt_grid_desc), c_void_p]),
     ("vpt_set_grid_majorant_block", c_int, [c_void_p, c_int]),
     ("vpt_set_grid_interpolation", c_int, [c_void_p, c_int]),
+    ("vpt_set_emission_grid", c_int, [c_void_p, c_void_p, c_void_p]),
     ("vpt_render_device", c_int, [c_void_p, POINTER(vpt_params), c_void_p, c_void_p]),
     ("vpt_render", c_int, [c_void_p, POINTER(vpt_params), c_void_p]),
     ("vpt_multi_create", c_int, [c_int, POINTER(c_void_p)]),
@@ -114,6 +115,7 @@ PROTOTYPES = [
     ("vpt_multi_set_density_grid", c_int, [c_void_p, POINTER(vpt_grid_desc), c_void_p]),
     ("vpt_multi_set_grid_majorant_block", c_int, [c_void_p, c_int]),
     ("vpt_multi_set_grid_interpolation", c_int, [c_void_p, c_int]),
+    ("vpt_multi_set_emission_grid", c_int, [c_void_p, c_void_p, c_void_p]),
     ("vpt_multi_render", c_int, [c_void_p, POINTER(vpt_params), c_void_p]),
     ("vpt_multi_destroy", None, [c_void_p]),
     ("vpt_render_multi", c_int, [c_void_p, c_int, POINTER(vpt_params), c_int, c_void_p]),
@@ -146,6 +148,10 @@ PROTOTYPES = [
     ("vpt_grid_ratio_probe", c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     ("vpt_grid_ratio_probe_host", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p,
                                           c_int, c_void_p, c_void_p, c_void_p]),
+    ("vpt_grid_emission_probe", c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
+    ("vpt_grid_emission_probe_host", c_int, [POINTER(vpt_grid_desc), c_void_p, c_void_p, c_int, c_int, c_double, c_void_p,
+                                             c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vpt_grid_probe_host_ex", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p,
                                        c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vpt_grid_ratio_probe_host_ex", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_int, c_double, c_void_p, c_void_p,

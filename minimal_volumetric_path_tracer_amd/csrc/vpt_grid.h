@@ -94,6 +94,21 @@
  * floor((p - lo) * inv_cell - 0.5) + 1 held to [0, n]; a cell the rounding left without length is passed over, and
  * since the integrand is looked up by position, never by cell index, a cut misplaced by an ulp costs an ulp.  Capped
  * at n[0] + n[1] + n[2] + 7 pieces.  No draw; T = exp(sigma_t * tau * -1.0) as before.
+ *
+ * Emission (opt-in: vpt_grid_view.emit != NULL; vpt_grid_track_em_m, vpt_grid_track_lm_em_m).  An emission grid eps, float32
+ * >= 0, on the density grid's box and resolution; the medium's source term is sigma_a rho(x) eps(x) rgb, radiance per unit
+ * length -- Kirchhoff's form: where nothing absorbs, nothing emits.  eps(x) is looked up as rho(x) is: the voxel's value
+ * (nearest), or the same eight voxels and weights as the density lookup, lerp for lerp (trilinear); zero outside the box.
+ * The emitting walkers are the two tracks above statement for statement -- the same draws, t_coll, end state and step
+ * count, bit for bit -- and score the collision estimator on every tentative collision: wherever the track has fetched rho at
+ * a tentative point that passed the boundary test (step 2 of the global track, step 3 of the local one),
+ *   esum = esum + ((rho * eps) / mu)        mu = rho_max, or the super-voxel's majorant
+ * before rho is tested against mu, so null and real collisions and the no-draw case rho >= mu all score; a tentative point
+ * the boundary test rejects scores nothing, and an empty super-voxel is skipped as before (rho = 0 there).  esum starts at
+ * +0 and the terms are added in the order they occur.  Under the nearest lookup both factors are widened float32 values, so
+ * the product is exact, and with mu == rho the score is eps bit for bit.  E[esum] = sigma_t * integral of
+ * T(t) rho(t) eps(t) dt over the tracked segment, T = exp(-sigma_t tau): a tentative point falls into dt with probability
+ * density T_mu(t) mu sigma_t summed over the null-collision histories, which is sigma_t mu T(t) once the nulls are weighed.
  */
 #ifndef VPT_GRID_H
 #define VPT_GRID_H
@@ -120,8 +135,11 @@
 #define VPT_GRID_MAX_TRACK_STEPS (1 << 22)
 #define VPT_GRID_BIG 1.7976931348623157e+308
 
-/* the grid as the walkers read it (host or device pointer in rho); filled by vpt_grid_view_init */
-typedef struct vpt_grid_view {
+/* the grid as the walkers read it (host or device pointer in rho): vpt_grid_fields, filled by vpt_grid_view_init.  The
+ * view extends it by one pointer, `emit`, after every other field, and only the emitting walkers take the view: every
+ * other walker takes the fields (a view converts to them), so a kernel without emission keeps a vpt_grid_fields -- the
+ * object it kept before emission existed, under another name -- and its code is what it was */
+typedef struct vpt_grid_fields {
     int32_t n[3];          /* nx, ny, nz */
     int32_t interp;        /* 0 nearest, 1 trilinear (header comment); the word that was padding */
     double lo[3], hi[3];
@@ -133,6 +151,10 @@ typedef struct vpt_grid_view {
     const float* maj;      /* nb[2] x nb[1] x nb[0] block maxima, x fastest */
     int32_t nb[3];
     int32_t block;
+} vpt_grid_fields;
+typedef struct vpt_grid_view : vpt_grid_fields {
+    /* emission (header comment); NULL: none.  After every other field */
+    const float* emit;     /* nz x ny x nx, the density's layout */
 } vpt_grid_view;
 
 /* 0 when valid, else 1 dimension < 1 or too many voxels, 2 box not finite or hi <= lo, 3 a density that is
@@ -173,6 +195,7 @@ static inline void vpt_grid_view_init(vpt_grid_view* G, const int32_t n[3], cons
     G->maj = 0;
     G->nb[0] = G->nb[1] = G->nb[2] = 0;
     G->block = 0;
+    G->emit = 0;
 }
 
 /* host: the super-voxel counts of block size B >= 1 and the block maxima of `density` into out (nb[2] x nb[1] x
@@ -233,7 +256,7 @@ static inline void vpt_grid_view_set_majorant(vpt_grid_view* G, int32_t B, const
     else G->nb[0] = G->nb[1] = G->nb[2] = 0;
 }
 
-VPT_GR int vpt_grid_axis_index(const vpt_grid_view* G, int a, double p)
+VPT_GR int vpt_grid_axis_index(const vpt_grid_fields* G, int a, double p)
 {
     const double f = floor((p - G->lo[a]) * G->inv_cell[a]);
     if (!(f >= 0.0)) return 0;  /* a hair below lo (or NaN) */
@@ -241,14 +264,14 @@ VPT_GR int vpt_grid_axis_index(const vpt_grid_view* G, int a, double p)
 }
 
 /* density at a point of the box (the caller has clipped to it) */
-VPT_GR double vpt_grid_density(const vpt_grid_view* G, double px, double py, double pz)
+VPT_GR double vpt_grid_density(const vpt_grid_fields* G, double px, double py, double pz)
 {
     const int ix = vpt_grid_axis_index(G, 0, px), iy = vpt_grid_axis_index(G, 1, py), iz = vpt_grid_axis_index(G, 2, pz);
     return (double)G->rho[((int64_t)iz * G->n[1] + iy) * G->n[0] + ix];
 }
 
 /* one axis of the trilinear lookup (header comment): the two voxel indices and the weight of the upper one */
-VPT_GR void vpt_grid_tl_axis(const vpt_grid_view* G, int a, double p, int* i0, int* i1, double* f)
+VPT_GR void vpt_grid_tl_axis(const vpt_grid_fields* G, int a, double p, int* i0, int* i1, double* f)
 {
     const int n = G->n[a];
     double u = (p - G->lo[a]) * G->inv_cell[a] - 0.5;
@@ -269,7 +292,7 @@ VPT_GR double vpt_grid_lerp(double a, double b, double f)
 }
 
 /* trilinear density at a point of the box (header comment) */
-VPT_GR double vpt_grid_density_tl(const vpt_grid_view* G, double px, double py, double pz)
+VPT_GR double vpt_grid_density_tl(const vpt_grid_fields* G, double px, double py, double pz)
 {
     int x0, x1, y0, y1, z0, z1;
     double fx, fy, fz;
@@ -289,14 +312,14 @@ VPT_GR double vpt_grid_density_tl(const vpt_grid_view* G, double px, double py, 
 }
 
 /* the density as the walkers read it at a tentative point; tl is a constant at every call, so one lookup remains */
-VPT_GR double vpt_grid_lookup(const vpt_grid_view* G, const int tl, double px, double py, double pz)
+VPT_GR double vpt_grid_lookup(const vpt_grid_fields* G, const int tl, double px, double py, double pz)
 {
     return tl ? vpt_grid_density_tl(G, px, py, pz) : vpt_grid_density(G, px, py, pz);
 }
 
 /* slab test of o + d t against the box: the interval [*t0, *t1] with *t0 >= 0; returns 0 when there is none.
  * An axis with d == 0 takes part through o alone (lo <= o < hi). */
-VPT_GR int vpt_grid_slab(const vpt_grid_view* G, const double o[3], const double d[3], double* t0, double* t1)
+VPT_GR int vpt_grid_slab(const vpt_grid_fields* G, const double o[3], const double d[3], double* t0, double* t1)
 {
     double a0 = 0.0, a1 = VPT_GRID_BIG;
     for (int a = 0; a < 3; ++a) {
@@ -321,7 +344,7 @@ VPT_GR int vpt_grid_slab(const vpt_grid_view* G, const double o[3], const double
 }
 
 /* optical depth over t in [0, tmax] (header comment) */
-VPT_GR double vpt_grid_tau(const vpt_grid_view* G, const double o[3], const double d[3], double tmax)
+VPT_GR double vpt_grid_tau(const vpt_grid_fields* G, const double o[3], const double d[3], double tmax)
 {
     double t0, t1;
     if (!(tmax > 0.0) || !(G->rho_max > 0.0)) return 0.0;
@@ -356,7 +379,7 @@ VPT_GR double vpt_grid_tau(const vpt_grid_view* G, const double o[3], const doub
 }
 
 /* plane j of the interpolation cells of axis a, j = 0 .. n + 1: cell c lies between planes c and c + 1 */
-VPT_GR double vpt_grid_tl_plane(const vpt_grid_view* G, int a, int j)
+VPT_GR double vpt_grid_tl_plane(const vpt_grid_fields* G, int a, int j)
 {
     if (j <= 0) return G->lo[a];
     if (j > G->n[a]) return G->hi[a];
@@ -364,7 +387,7 @@ VPT_GR double vpt_grid_tl_plane(const vpt_grid_view* G, int a, int j)
 }
 
 /* optical depth of the trilinear field over t in [0, tmax] (header comment) */
-VPT_GR double vpt_grid_tau_tl(const vpt_grid_view* G, const double o[3], const double d[3], double tmax)
+VPT_GR double vpt_grid_tau_tl(const vpt_grid_fields* G, const double o[3], const double d[3], double tmax)
 {
     double t0, t1;
     if (!(tmax > 0.0) || !(G->rho_max > 0.0)) return 0.0;
@@ -402,13 +425,13 @@ VPT_GR double vpt_grid_tau_tl(const vpt_grid_view* G, const double o[3], const d
     return tau;
 }
 
-VPT_GR double vpt_grid_transmittance(const vpt_grid_view* G, const double o[3], const double d[3], double tmax,
+VPT_GR double vpt_grid_transmittance(const vpt_grid_fields* G, const double o[3], const double d[3], double tmax,
                                      double sigma_t)
 {
     return VPT_GRID_EXP(sigma_t * vpt_grid_tau(G, o, d, tmax) * -1.0);
 }
 
-VPT_GR double vpt_grid_transmittance_tl(const vpt_grid_view* G, const double o[3], const double d[3], double tmax,
+VPT_GR double vpt_grid_transmittance_tl(const vpt_grid_fields* G, const double o[3], const double d[3], double tmax,
                                         double sigma_t)
 {
     return VPT_GRID_EXP(sigma_t * vpt_grid_tau_tl(G, o, d, tmax) * -1.0);
@@ -416,7 +439,7 @@ VPT_GR double vpt_grid_transmittance_tl(const vpt_grid_view* G, const double o[3
 
 /* delta tracking (header comment): the collision distance, -1 for "none", NaN for a capped track; *X is the
  * erand48 state, advanced by the draws taken; *steps (optional) counts the tentative steps */
-VPT_GR double vpt_grid_track_m(const vpt_grid_view* G, const int tl, const double o[3], const double d[3], double tmax, double sigma_t,
+VPT_GR double vpt_grid_track_m(const vpt_grid_fields* G, const int tl, const double o[3], const double d[3], double tmax, double sigma_t,
                              uint64_t* X, uint32_t* steps)
 {
     double t0, t1;
@@ -436,7 +459,7 @@ VPT_GR double vpt_grid_track_m(const vpt_grid_view* G, const int tl, const doubl
 }
 
 /* the plane below super-voxel kb of axis a (kb == nb[a]: the plane above the last one); header comment */
-VPT_GR double vpt_grid_block_plane(const vpt_grid_view* G, int a, int kb)
+VPT_GR double vpt_grid_block_plane(const vpt_grid_fields* G, int a, int kb)
 {
     if (kb <= 0) return G->lo[a];
     if (kb >= G->nb[a]) return G->hi[a];
@@ -445,7 +468,7 @@ VPT_GR double vpt_grid_block_plane(const vpt_grid_view* G, int a, int kb)
 
 /* delta tracking with local majorants (header comment; G->block >= 1): vpt_grid_track's arguments and
  * results */
-VPT_GR double vpt_grid_track_lm_m(const vpt_grid_view* G, const int tl, const double o[3], const double d[3], double tmax,
+VPT_GR double vpt_grid_track_lm_m(const vpt_grid_fields* G, const int tl, const double o[3], const double d[3], double tmax,
                                 double sigma_t, uint64_t* X, uint32_t* steps)
 {
     double t0, t1;
@@ -502,7 +525,7 @@ VPT_GR double vpt_grid_track_lm_m(const vpt_grid_view* G, const int tl, const do
 
 /* ratio tracking (header comment): the estimate That of exp(-sigma_t tau(o, d, tmax)), NaN for a capped walk;
  * *X is the erand48 state, advanced by the draws taken; *steps (optional) counts them */
-VPT_GR double vpt_grid_ratio_m(const vpt_grid_view* G, const int tl, const double o[3], const double d[3], double tmax, double sigma_t,
+VPT_GR double vpt_grid_ratio_m(const vpt_grid_fields* G, const int tl, const double o[3], const double d[3], double tmax, double sigma_t,
                              uint64_t* X, uint32_t* steps)
 {
     double t0, t1;
@@ -523,7 +546,7 @@ VPT_GR double vpt_grid_ratio_m(const vpt_grid_view* G, const int tl, const doubl
 
 /* ratio tracking with local majorants (header comment; G->block >= 1): vpt_grid_ratio's arguments and results.
  * The walk is vpt_grid_track_lm's, restated: sharing it would put the weight into the track's loop */
-VPT_GR double vpt_grid_ratio_lm_m(const vpt_grid_view* G, const int tl, const double o[3], const double d[3], double tmax,
+VPT_GR double vpt_grid_ratio_lm_m(const vpt_grid_fields* G, const int tl, const double o[3], const double d[3], double tmax,
                                 double sigma_t, uint64_t* X, uint32_t* steps)
 {
     double t0, t1;
@@ -576,23 +599,143 @@ VPT_GR double vpt_grid_ratio_lm_m(const vpt_grid_view* G, const int tl, const do
     return (double)NAN;
 }
 
+/* density and emission at a point of the box (header comment): vpt_grid_lookup's value in *rho, bit for bit, and eps from
+ * the same voxels and weights */
+VPT_GR void vpt_grid_lookup_em(const vpt_grid_view* G, const int tl, double px, double py, double pz, double* rho, double* eps)
+{
+    if (!tl) {
+        const int ix = vpt_grid_axis_index(G, 0, px), iy = vpt_grid_axis_index(G, 1, py), iz = vpt_grid_axis_index(G, 2, pz);
+        const int64_t r = ((int64_t)iz * G->n[1] + iy) * G->n[0] + ix;
+        *rho = (double)G->rho[r];
+        *eps = (double)G->emit[r];
+        return;
+    }
+    int x0, x1, y0, y1, z0, z1;
+    double fx, fy, fz;
+    vpt_grid_tl_axis(G, 0, px, &x0, &x1, &fx);
+    vpt_grid_tl_axis(G, 1, py, &y0, &y1, &fy);
+    vpt_grid_tl_axis(G, 2, pz, &z0, &z1, &fz);
+    const int64_t r00 = ((int64_t)z0 * G->n[1] + y0) * G->n[0] + x0, r01 = ((int64_t)z0 * G->n[1] + y1) * G->n[0] + x0;
+    const int64_t r10 = ((int64_t)z1 * G->n[1] + y0) * G->n[0] + x0, r11 = ((int64_t)z1 * G->n[1] + y1) * G->n[0] + x0;
+    const int dx = x1 - x0;
+    const double c00 = vpt_grid_lerp((double)G->rho[r00], (double)G->rho[r00 + dx], fx);
+    const double c01 = vpt_grid_lerp((double)G->rho[r01], (double)G->rho[r01 + dx], fx);
+    const double c10 = vpt_grid_lerp((double)G->rho[r10], (double)G->rho[r10 + dx], fx);
+    const double c11 = vpt_grid_lerp((double)G->rho[r11], (double)G->rho[r11 + dx], fx);
+    *rho = vpt_grid_lerp(vpt_grid_lerp(c00, c01, fy), vpt_grid_lerp(c10, c11, fy), fz);
+    const double e00 = vpt_grid_lerp((double)G->emit[r00], (double)G->emit[r00 + dx], fx);
+    const double e01 = vpt_grid_lerp((double)G->emit[r01], (double)G->emit[r01 + dx], fx);
+    const double e10 = vpt_grid_lerp((double)G->emit[r10], (double)G->emit[r10 + dx], fx);
+    const double e11 = vpt_grid_lerp((double)G->emit[r11], (double)G->emit[r11 + dx], fx);
+    *eps = vpt_grid_lerp(vpt_grid_lerp(e00, e01, fy), vpt_grid_lerp(e10, e11, fy), fz);
+}
+
+/* the emission alone (the models and the probes' callers; the walkers use the pair above) */
+VPT_GR double vpt_grid_emission(const vpt_grid_view* G, const int tl, double px, double py, double pz)
+{
+    double rho, eps;
+    vpt_grid_lookup_em(G, tl, px, py, pz, &rho, &eps);
+    return eps;
+}
+
+/* the emitting track (header comment; G->emit != NULL): vpt_grid_track_m with the collision estimator's sum in *esum */
+VPT_GR double vpt_grid_track_em_m(const vpt_grid_view* G, const int tl, const double o[3], const double d[3], double tmax,
+                                  double sigma_t, uint64_t* X, uint32_t* steps, double* esum)
+{
+    double t0, t1;
+    if (steps) *steps = 0;
+    *esum = 0.0;
+    if (!(G->rho_max > 0.0)) return -1.0;
+    if (!vpt_grid_slab(G, o, d, &t0, &t1)) return -1.0;
+    double t = t0;
+    for (int k = 0; k < VPT_GRID_MAX_TRACK_STEPS; ++k) {
+        t = t + (-VPT_GRID_LOG(1 - vpt_erand48(X)) / (G->rho_max * sigma_t));
+        if (steps) *steps = (uint32_t)(k + 1);
+        if (t > tmax || t >= t1 || t != t) return -1.0;
+        double rho, eps;
+        vpt_grid_lookup_em(G, tl, o[0] + d[0] * t, o[1] + d[1] * t, o[2] + d[2] * t, &rho, &eps);
+        *esum = *esum + ((rho * eps) / G->rho_max);
+        if (rho >= G->rho_max) return t;
+        if (vpt_erand48(X) * G->rho_max < rho) return t;
+    }
+    return (double)NAN;
+}
+
+/* the emitting track with local majorants (header comment; G->block >= 1, G->emit != NULL): vpt_grid_track_lm_m with
+ * the collision estimator's sum in *esum */
+VPT_GR double vpt_grid_track_lm_em_m(const vpt_grid_view* G, const int tl, const double o[3], const double d[3], double tmax,
+                                     double sigma_t, uint64_t* X, uint32_t* steps, double* esum)
+{
+    double t0, t1;
+    if (steps) *steps = 0;
+    *esum = 0.0;
+    if (!(G->rho_max > 0.0)) return -1.0;
+    if (!vpt_grid_slab(G, o, d, &t0, &t1)) return -1.0;
+    int i[3], step[3];
+    double tn[3], inv[3];
+    for (int a = 0; a < 3; ++a) {
+        i[a] = vpt_grid_axis_index(G, a, o[a] + d[a] * t0) / G->block;
+        step[a] = d[a] > 0.0 ? 1 : (d[a] < 0.0 ? -1 : 0);
+        inv[a] = step[a] ? 1.0 / d[a] : 0.0;
+        tn[a] = step[a] ? (vpt_grid_block_plane(G, a, i[a] + (step[a] > 0)) - o[a]) * inv[a] : VPT_GRID_BIG;
+    }
+    const int max_cross = G->nb[0] + G->nb[1] + G->nb[2] + 4;
+    double t = t0;
+    int a = tn[0] <= tn[1] ? (tn[0] <= tn[2] ? 0 : 2) : (tn[1] <= tn[2] ? 1 : 2);
+    double te = tn[a];
+    double mu = te > t ? (double)G->maj[((int64_t)i[2] * G->nb[1] + i[1]) * G->nb[0] + i[0]] : 0.0;
+    for (int k = 0; k < VPT_GRID_MAX_TRACK_STEPS; ++k) {
+        double rem = -VPT_GRID_LOG(1 - vpt_erand48(X));
+        if (steps) *steps = (uint32_t)(k + 1);
+        double tc = 0.0;
+        int c = 0;
+        for (; c < max_cross; ++c) {
+            if (te > t) {
+                if (mu > 0.0) {
+                    const double s = mu * sigma_t;
+                    tc = t + (rem / s);
+                    if (tc < te) break;  /* a tentative collision */
+                    rem = rem - s * (te - t);
+                }
+                t = te;
+            }
+            if (!(te < t1) || te > tmax) return -1.0;
+            i[a] += step[a];
+            if (i[a] < 0 || i[a] >= G->nb[a]) return -1.0;
+            tn[a] = (vpt_grid_block_plane(G, a, i[a] + (step[a] > 0)) - o[a]) * inv[a];
+            a = tn[0] <= tn[1] ? (tn[0] <= tn[2] ? 0 : 2) : (tn[1] <= tn[2] ? 1 : 2);
+            te = tn[a];
+            mu = te > t ? (double)G->maj[((int64_t)i[2] * G->nb[1] + i[1]) * G->nb[0] + i[0]] : 0.0;
+        }
+        if (c == max_cross) return -1.0;
+        if (tc > tmax || tc >= t1) return -1.0;
+        double rho, eps;
+        vpt_grid_lookup_em(G, tl, o[0] + d[0] * tc, o[1] + d[1] * tc, o[2] + d[2] * tc, &rho, &eps);
+        *esum = *esum + ((rho * eps) / mu);
+        if (rho >= mu) return tc;
+        if (vpt_erand48(X) * mu < rho) return tc;
+        t = tc;
+    }
+    return (double)NAN;
+}
+
 /* the nearest-lookup walkers under the names they have always had */
-VPT_GR double vpt_grid_track(const vpt_grid_view* G, const double o[3], const double d[3], double tmax, double sigma_t,
+VPT_GR double vpt_grid_track(const vpt_grid_fields* G, const double o[3], const double d[3], double tmax, double sigma_t,
         uint64_t* X, uint32_t* steps)
 {
     return vpt_grid_track_m(G, 0, o, d, tmax, sigma_t, X, steps);
 }
-VPT_GR double vpt_grid_track_lm(const vpt_grid_view* G, const double o[3], const double d[3], double tmax, double sigma_t,
+VPT_GR double vpt_grid_track_lm(const vpt_grid_fields* G, const double o[3], const double d[3], double tmax, double sigma_t,
         uint64_t* X, uint32_t* steps)
 {
     return vpt_grid_track_lm_m(G, 0, o, d, tmax, sigma_t, X, steps);
 }
-VPT_GR double vpt_grid_ratio(const vpt_grid_view* G, const double o[3], const double d[3], double tmax, double sigma_t,
+VPT_GR double vpt_grid_ratio(const vpt_grid_fields* G, const double o[3], const double d[3], double tmax, double sigma_t,
         uint64_t* X, uint32_t* steps)
 {
     return vpt_grid_ratio_m(G, 0, o, d, tmax, sigma_t, X, steps);
 }
-VPT_GR double vpt_grid_ratio_lm(const vpt_grid_view* G, const double o[3], const double d[3], double tmax, double sigma_t,
+VPT_GR double vpt_grid_ratio_lm(const vpt_grid_fields* G, const double o[3], const double d[3], double tmax, double sigma_t,
         uint64_t* X, uint32_t* steps)
 {
     return vpt_grid_ratio_lm_m(G, 0, o, d, tmax, sigma_t, X, steps);

@@ -20,11 +20,24 @@
  * host in the same way from the view's interp word; the walkers and the optical depth take it as a constant, so
  * there is no test of the mode in a loop.  The TL = true kernels are instantiated in vpt_hetero_tl.hip, a code object
  * of their own, and the TL = false ones stay in vpt_hetero.hip as they were.
+ * Emission (vpt_grid.h, vpt_set_emission_grid): the template parameter EM, chosen on the host where the context holds an
+ * emission grid.  hetero_decide's track becomes the emitting one, and after the track, before its result is classified,
+ *   p.L = p.L + (rgb * p.beta) * (((sigma_a / sigma_t) * esum) * (1 / continueprob))
+ * in exactly this order, at every depth (the medium has no next-event estimation, so a collision at any depth sees it;
+ * continueprob = 0.6 is the roulette's factor, which precedes decide at every depth).  sigma_a / sigma_t turns
+ * E[esum] = sigma_t int T rho eps into the source term's integral sigma_a int T rho eps.  Emission takes no draw and
+ * changes no branch: paths, draw counts and end states are those of EM = false.  A camera ray that ends on a light adds
+ * the light's radiance to p.L, so the emission scored on that segment survives.  The colour travels with the emission
+ * grid: the four doubles in front of the voxels (rgb and a pad word; VPT_EMIT_HEAD below).  The EM = true kernels are
+ * instantiated in vpt_hetero_em.hip and vpt_hetero_em_tl.hip; the EM = false kernels copy and keep the fields in front of
+ * `emit` (vpt_grid_fields, which every walker but the emitting ones takes), so they load and hold what they did before.
  */
 #ifndef VPT_HETERO_H
 #define VPT_HETERO_H
 
 #include <stddef.h>
+
+#include <type_traits>
 
 #include "vpt_device.h"
 
@@ -34,13 +47,24 @@
 
 namespace vpt {
 
+/* the emission grid on the device: VPT_EMIT_HEAD doubles -- rgb, then a pad word -- and behind them the voxels that
+ * vpt_grid_view.emit points to */
+#define VPT_EMIT_HEAD 4
+
+/* what a policy with an emission grid holds beside the view: the colour, read once from in front of the voxels */
+struct GridColour {
+    dv3 rgb;
+};
+struct GridNoColour {};
+
 /* the grid's transmittance as the TP policy of mis_v2 / single_scattering (vpt_device.h TrHom); TL: the trilinear
- * field (GridTr is the nearest one) */
-template <bool TL>
-struct GridTrT {
+ * field (GridTr is the nearest one).  EM: with the emission grid -- the policy then holds the whole view and the colour;
+ * without it the fields alone (vpt_grid.h vpt_grid_fields), the object these kernels held before the view had `emit` */
+template <bool TL, bool EM = false>
+struct GridTrT : std::conditional_t<EM, GridColour, GridNoColour> {
     static constexpr bool hom = false;
     static constexpr bool draws = false;
-    vpt_grid_view G;
+    std::conditional_t<EM, vpt_grid_view, vpt_grid_fields> G;
     /* the context's view from device memory.  Without local majorants only the fields the global-majorant
      * walkers read are copied (everything before `maj`): block, nb and maj stay unset and nothing reads them, so
      * the LM = false kernels load what they loaded before local majorants existed */
@@ -48,8 +72,12 @@ struct GridTrT {
     __device__ __forceinline__ static GridTrT load(const vpt_grid_view* __restrict__ g)
     {
         GridTrT tp;
-        if (LM) tp.G = *g;
-        else __builtin_memcpy(&tp.G, g, offsetof(vpt_grid_view, maj));
+        if (LM || EM) tp.G = *g;
+        else __builtin_memcpy(&tp.G, g, offsetof(vpt_grid_fields, maj));
+        if constexpr (EM) {
+            const double* c = (const double*)tp.G.emit - VPT_EMIT_HEAD;
+            tp.rgb = mk(c[0], c[1], c[2]);
+        }
         return tp;
     }
     __device__ __forceinline__ double along(dv3 o, dv3 d, double dist, double sigma_t) const
@@ -71,19 +99,23 @@ using GridTr = GridTrT<false>;
 /* estimator 11's policy: every factor is a ratio-tracking estimate (vpt_grid.h) over the same segment, drawn from
  * the sample's own stream where GridTr evaluates the factor -- a policy with draws == true takes the sampler first.
  * A zero-length segment is 1.0 without a draw, as vpt_grid_tau's is exp(-0).  LM: the grid has a majorant grid; TL: the
- * trilinear field. */
-template <bool LM, bool TL = false>
-struct GridRatioTr {
+ * trilinear field; EM: with the emission grid, as in GridTrT (the shadow rays stay transmittance only). */
+template <bool LM, bool TL = false, bool EM = false>
+struct GridRatioTr : std::conditional_t<EM, GridColour, GridNoColour> {
     static constexpr bool hom = false;
     static constexpr bool draws = true;
-    vpt_grid_view G;
+    std::conditional_t<EM, vpt_grid_view, vpt_grid_fields> G;
     template <bool LM_>
     __device__ __forceinline__ static GridRatioTr load(const vpt_grid_view* __restrict__ g)
     {
         static_assert(LM_ == LM, "the policy's LM is the kernel's");
         GridRatioTr tp;
-        if (LM) tp.G = *g;
-        else __builtin_memcpy(&tp.G, g, offsetof(vpt_grid_view, maj));
+        if (LM || EM) tp.G = *g;
+        else __builtin_memcpy(&tp.G, g, offsetof(vpt_grid_fields, maj));
+        if constexpr (EM) {
+            const double* c = (const double*)tp.G.emit - VPT_EMIT_HEAD;
+            tp.rgb = mk(c[0], c[1], c[2]);
+        }
         return tp;
     }
     template <bool COUNT>
@@ -109,8 +141,8 @@ struct HeteroStats {
     unsigned long long tracks, steps;
 };
 
-/* decide<0> with delta tracking in freeFlightSample's place */
-template <bool COUNT, bool LM = false, bool TL = false, class TP = GridTrT<TL>>
+/* decide<0> with delta tracking in freeFlightSample's place; EM: the emitting track and its contribution (header comment) */
+template <bool COUNT, bool LM = false, bool TL = false, class TP = GridTrT<TL>, bool EM = false>
 VPT_DEV int hetero_decide(const DevScene* __restrict__ S, const TP& tp, Sampler<COUNT>& smp, Path& p, Event& e,
                           const Medium& m, HeteroStats* hs = nullptr)
 {
@@ -126,8 +158,17 @@ VPT_DEV int hetero_decide(const DevScene* __restrict__ S, const TP& tp, Sampler<
     e.src = emit_pick(S, (int)(smp.next() * count), count);
     const double oo[3] = {p.o.x, p.o.y, p.o.z}, dd[3] = {p.d.x, p.d.y, p.d.z};
     uint32_t nsteps = 0;
-    const double tc = LM ? vpt_grid_track_lm_m(&tp.G, TL, oo, dd, t, sigma_t, &smp.X, hs ? &nsteps : (uint32_t*)nullptr)
-                        : vpt_grid_track_m(&tp.G, TL, oo, dd, t, sigma_t, &smp.X, hs ? &nsteps : (uint32_t*)nullptr);
+    double tc;
+    if constexpr (EM) {
+        const double continueprob = 0.6;
+        double esum;
+        tc = LM ? vpt_grid_track_lm_em_m(&tp.G, TL, oo, dd, t, sigma_t, &smp.X, hs ? &nsteps : (uint32_t*)nullptr, &esum)
+                : vpt_grid_track_em_m(&tp.G, TL, oo, dd, t, sigma_t, &smp.X, hs ? &nsteps : (uint32_t*)nullptr, &esum);
+        p.L = add(p.L, scl(mul(tp.rgb, p.beta), (((m.sigma_a / sigma_t) * esum) * (1 / continueprob))));
+    } else {
+        tc = LM ? vpt_grid_track_lm_m(&tp.G, TL, oo, dd, t, sigma_t, &smp.X, hs ? &nsteps : (uint32_t*)nullptr)
+                : vpt_grid_track_m(&tp.G, TL, oo, dd, t, sigma_t, &smp.X, hs ? &nsteps : (uint32_t*)nullptr);
+    }
     if (hs) {
         hs->tracks += 1;
         hs->steps += nsteps;
@@ -142,7 +183,10 @@ VPT_DEV int hetero_decide(const DevScene* __restrict__ S, const TP& tp, Sampler<
     }
     if (!hit) return EV_END;  /* left the medium into vacuum */
     if (sph_flag(S->m_emitter, id)) {  /* the path ends on a light; only a camera ray sees it */
-        if (p.depth == 0) p.L = mul(sph_rad(S, id), p.beta);
+        if (p.depth == 0) {
+            if constexpr (EM) p.L = add(p.L, mul(sph_rad(S, id), p.beta));  /* the segment's emission stays */
+            else p.L = mul(sph_rad(S, id), p.beta);
+        }
         return EV_END;
     }
     return EV_SURF;
@@ -193,8 +237,8 @@ VPT_DEV void hetero_medium(const DevScene* __restrict__ S, const TP& tp, Sampler
 }
 
 /* one camera sample, sequentially (vpt_trace_batch, render_kernel_simple<10>) */
-template <bool COUNT, bool LM = false, bool TL = false>
-__device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridTrT<TL>& tp, Sampler<COUNT>& smp, dv3 o, dv3 d,
+template <bool COUNT, bool LM = false, bool TL = false, bool EM = false>
+__device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridTrT<TL, EM>& tp, Sampler<COUNT>& smp, dv3 o, dv3 d,
                                    const Medium& m, HeteroStats* hs = nullptr)
 {
     Path p;
@@ -206,7 +250,7 @@ __device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridTrT
     Event e;
     e.pdf = 0;
     while (continue_path(smp, p, m)) {
-        const int ev = hetero_decide<COUNT, LM, TL>(S, tp, smp, p, e, m, hs);
+        const int ev = hetero_decide<COUNT, LM, TL, GridTrT<TL, EM>, EM>(S, tp, smp, p, e, m, hs);
         if (ev == EV_END) break;
         if (ev == EV_SURF) hetero_surface(S, tp, smp, p, e, m);
         else hetero_medium(S, tp, smp, p, e, m);
@@ -216,8 +260,8 @@ __device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridTrT
 
 /* the same for estimator 11 (render_kernel_simple<11>).  Restated, not a shared template: estimator 10's function
  * above is an out-of-line function of its kernels, and its name and code are to stay what they were */
-template <bool COUNT, bool LM = false, bool TL = false>
-__device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridRatioTr<LM, TL>& tp, Sampler<COUNT>& smp, dv3 o,
+template <bool COUNT, bool LM = false, bool TL = false, bool EM = false>
+__device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridRatioTr<LM, TL, EM>& tp, Sampler<COUNT>& smp, dv3 o,
                                    dv3 d, const Medium& m, HeteroStats* hs = nullptr)
 {
     Path p;
@@ -229,7 +273,7 @@ __device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridRat
     Event e;
     e.pdf = 0;
     while (continue_path(smp, p, m)) {
-        const int ev = hetero_decide<COUNT, LM, TL, GridRatioTr<LM, TL>>(S, tp, smp, p, e, m, hs);
+        const int ev = hetero_decide<COUNT, LM, TL, GridRatioTr<LM, TL, EM>, EM>(S, tp, smp, p, e, m, hs);
         if (ev == EV_END) break;
         if (ev == EV_SURF) hetero_surface(S, tp, smp, p, e, m);
         else hetero_medium(S, tp, smp, p, e, m);
@@ -238,14 +282,14 @@ __device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridRat
 }
 
 /* the three steps as the persistent-wave loop (vpt_wave.h) calls them, on the kernel's view of the grid */
-template <bool LM, bool TL = false, class TP = GridTrT<TL>>
+template <bool LM, bool TL = false, class TP = GridTrT<TL>, bool EM = false>
 struct HeteroSteps {
     TP tp;
     template <bool COUNT>
     __device__ __forceinline__ int decide(const DevScene* __restrict__ S, Sampler<COUNT>& smp, Path& p, Event& e,
                                           const Medium& m) const
     {
-        return hetero_decide<COUNT, LM, TL, TP>(S, tp, smp, p, e, m);
+        return hetero_decide<COUNT, LM, TL, TP, EM>(S, tp, smp, p, e, m);
     }
     template <bool COUNT>
     __device__ __forceinline__ void surface(const DevScene* __restrict__ S, Sampler<COUNT>& smp, Path& p, const Event& e,
@@ -296,5 +340,23 @@ void vpt_int_grid_probe_launch_tl(const vpt_grid_view* grid, bool lm, double sig
 void vpt_int_grid_ratio_probe_launch_tl(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
                                         const double* tmax, const uint64_t* states, int n, double* that, uint64_t* states_out,
                                         uint32_t* steps);
+/* and, but for the two probes, with the suffixes _em and _em_tl: the EM = true kernels (vpt_hetero_em.hip,
+ * vpt_hetero_em_tl.hip), which the caller takes where the view has an emission grid.  Their probe is the emitting track's */
+int vpt_int_hetero_launch_em(int device, const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
+int vpt_int_hetero_simple_launch_em(const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
+void vpt_int_hetero_trace_launch_em(int est, const vpt_ray* rays, const uint64_t* states, int n, const vpt::Medium& m,
+                                    const DevScene* S, const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states,
+                                    unsigned long long* stats);
+void vpt_int_grid_emission_probe_launch_em(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
+                                           const double* tmax, const uint64_t* states, int n, double* t_coll, double* esum,
+                                           uint64_t* states_out, uint32_t* steps);
+int vpt_int_hetero_launch_em_tl(int device, const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
+int vpt_int_hetero_simple_launch_em_tl(const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
+void vpt_int_hetero_trace_launch_em_tl(int est, const vpt_ray* rays, const uint64_t* states, int n, const vpt::Medium& m,
+                                       const DevScene* S, const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states,
+                                       unsigned long long* stats);
+void vpt_int_grid_emission_probe_launch_em_tl(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
+                                              const double* tmax, const uint64_t* states, int n, double* t_coll, double* esum,
+                                              uint64_t* states_out, uint32_t* steps);
 
 #endif

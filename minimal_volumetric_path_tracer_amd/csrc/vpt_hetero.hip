@@ -21,6 +21,12 @@
  * vpt_int_* launches; vpt_hetero_tl.hip includes this file with VPT_HETERO_TL = 1 and exports the same launches with
  * the suffix _tl, so the trilinear kernels are a code object of their own and this unit's stays what it was.  The LDS
  * prologue serves both lookups as it is.
+ *
+ * Emission: the template parameter EM (vpt_hetero.h) in the same way, VPT_HETERO_EM.  vpt_hetero_em.hip and
+ * vpt_hetero_em_tl.hip include this file with VPT_HETERO_EM = 1 and export the launches with the suffixes _em and _em_tl
+ * (the emitting track's probe in place of the two grid probes), two more code objects; this unit's kernels and the
+ * trilinear unit's stay what they were.  The emission grid is read from global memory: the LDS prologue stages the
+ * density and the majorants as before.
  */
 #include <hip/hip_runtime.h>
 
@@ -36,7 +42,14 @@
 #ifndef VPT_HETERO_TL
 #define VPT_HETERO_TL 0
 #endif
-#if VPT_HETERO_TL
+#ifndef VPT_HETERO_EM
+#define VPT_HETERO_EM 0
+#endif
+#if VPT_HETERO_EM && VPT_HETERO_TL
+#define VPT_HX(name) name##_em_tl
+#elif VPT_HETERO_EM
+#define VPT_HX(name) name##_em
+#elif VPT_HETERO_TL
 #define VPT_HX(name) name##_tl
 #else
 #define VPT_HX(name) name
@@ -49,71 +62,73 @@
 
 namespace vpt {
 
-template <bool COUNT, int FB, bool LM, bool TL>
+template <bool COUNT, int FB, bool LM, bool TL, bool EM = false>
 __global__ __launch_bounds__(256, 2) void hetero_kernel(KParams P, const DevScene* __restrict__ S)
 {
+    using TP = GridTrT<TL, EM>;
     /* the view lives in the steps object from the start: the walkers take its address, so a copy made after the
      * prologue is a second stack object (416 against 288 bytes of scratch, 9 against 4 spilled VGPRs) */
-    HeteroSteps<LM, TL> st{GridTrT<TL>::template load<LM>(P.grid)};
-    [[maybe_unused]] GridTrT<TL>& tp = st.tp;
+    HeteroSteps<LM, TL, TP, EM> st{TP::template load<LM>(P.grid)};
+    [[maybe_unused]] auto& G = st.tp.G;
 #if VPT_HETERO_LDS
     __shared__ float lds_rho[VPT_HETERO_LDS_BYTES / sizeof(float)];
     {
-        const int64_t nv = (int64_t)tp.G.n[0] * tp.G.n[1] * tp.G.n[2];
+        const int64_t nv = (int64_t)G.n[0] * G.n[1] * G.n[2];
         if (nv <= (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float))) {  /* workgroup-uniform */
-            for (int k = threadIdx.x; k < (int)nv; k += blockDim.x) lds_rho[k] = tp.G.rho[k];
+            for (int k = threadIdx.x; k < (int)nv; k += blockDim.x) lds_rho[k] = G.rho[k];
             __syncthreads();
-            tp.G.rho = lds_rho;
+            G.rho = lds_rho;
         }
 #if VPT_HETERO_LDS_MAJ
         if (LM) {  /* the majorant grid goes into what the density left of the budget */
             const int64_t cap = (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float));
             const int64_t used = nv <= cap ? nv : 0;
-            const int64_t nbv = (int64_t)tp.G.nb[0] * tp.G.nb[1] * tp.G.nb[2];
+            const int64_t nbv = (int64_t)G.nb[0] * G.nb[1] * G.nb[2];
             if (nbv <= cap - used) {  /* workgroup-uniform */
-                for (int k = threadIdx.x; k < (int)nbv; k += blockDim.x) lds_rho[used + k] = tp.G.maj[k];
+                for (int k = threadIdx.x; k < (int)nbv; k += blockDim.x) lds_rho[used + k] = G.maj[k];
                 __syncthreads();
-                tp.G.maj = lds_rho + used;
+                G.maj = lds_rho + used;
             }
         }
 #endif
     }
 #endif
-    wave_render<HeteroSteps<LM, TL>, COUNT, FB>(P, S, st);
+    wave_render<HeteroSteps<LM, TL, TP, EM>, COUNT, FB>(P, S, st);
 }
 
 /* estimator 11 (VPT_HETERO_RATIO): hetero_kernel on the ratio-tracking policy.  The prologue is restated, not shared:
  * with estimator 10's kernel calling a common body template its code moves (commuted v_mul_f64 operands, swapped
  * v_add_f64 pairs, up to three instructions more or fewer), and that kernel is to stay what it was */
-template <bool COUNT, int FB, bool LM, bool TL>
+template <bool COUNT, int FB, bool LM, bool TL, bool EM = false>
 __global__ __launch_bounds__(256, 2) void hetero_ratio_kernel(KParams P, const DevScene* __restrict__ S)
 {
-    HeteroSteps<LM, TL, GridRatioTr<LM, TL>> st{GridRatioTr<LM, TL>::template load<LM>(P.grid)};
-    [[maybe_unused]] GridRatioTr<LM, TL>& tp = st.tp;
+    using TP = GridRatioTr<LM, TL, EM>;
+    HeteroSteps<LM, TL, TP, EM> st{TP::template load<LM>(P.grid)};
+    [[maybe_unused]] auto& G = st.tp.G;
 #if VPT_HETERO_LDS
     __shared__ float lds_rho[VPT_HETERO_LDS_BYTES / sizeof(float)];
     {
-        const int64_t nv = (int64_t)tp.G.n[0] * tp.G.n[1] * tp.G.n[2];
+        const int64_t nv = (int64_t)G.n[0] * G.n[1] * G.n[2];
         if (nv <= (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float))) {  /* workgroup-uniform */
-            for (int k = threadIdx.x; k < (int)nv; k += blockDim.x) lds_rho[k] = tp.G.rho[k];
+            for (int k = threadIdx.x; k < (int)nv; k += blockDim.x) lds_rho[k] = G.rho[k];
             __syncthreads();
-            tp.G.rho = lds_rho;
+            G.rho = lds_rho;
         }
 #if VPT_HETERO_LDS_MAJ
         if (LM) {  /* the majorant grid goes into what the density left of the budget */
             const int64_t cap = (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float));
             const int64_t used = nv <= cap ? nv : 0;
-            const int64_t nbv = (int64_t)tp.G.nb[0] * tp.G.nb[1] * tp.G.nb[2];
+            const int64_t nbv = (int64_t)G.nb[0] * G.nb[1] * G.nb[2];
             if (nbv <= cap - used) {  /* workgroup-uniform */
-                for (int k = threadIdx.x; k < (int)nbv; k += blockDim.x) lds_rho[used + k] = tp.G.maj[k];
+                for (int k = threadIdx.x; k < (int)nbv; k += blockDim.x) lds_rho[used + k] = G.maj[k];
                 __syncthreads();
-                tp.G.maj = lds_rho + used;
+                G.maj = lds_rho + used;
             }
         }
 #endif
     }
 #endif
-    wave_render<HeteroSteps<LM, TL, GridRatioTr<LM, TL>>, COUNT, FB>(P, S, st);
+    wave_render<HeteroSteps<LM, TL, TP, EM>, COUNT, FB>(P, S, st);
 }
 
 }  // namespace vpt
@@ -123,9 +138,10 @@ using namespace vpt;
 namespace {
 
 constexpr bool TLU = VPT_HETERO_TL != 0;  /* the unit's value of TL */
+constexpr bool EMU = VPT_HETERO_EM != 0;  /* and of EM */
 
 /* estimator 10's per-sample call (vpt_hetero.h) */
-template <bool LM, bool TL>
+template <bool LM, bool TL, bool EM = false>
 __global__ __launch_bounds__(256) void trace_batch_hetero_kernel(const vpt_ray* __restrict__ rays,
                                                                  const uint64_t* __restrict__ states, int n, Medium m,
                                                                  const DevScene* __restrict__ S,
@@ -138,7 +154,7 @@ __global__ __launch_bounds__(256) void trace_batch_hetero_kernel(const vpt_ray* 
     smp.X = states[i] & 0xFFFFFFFFFFFFull;
     smp.g = m.g;
     HeteroStats hs{0, 0};
-    dv3 L = trace_hetero<false, LM, TL>(S, GridTrT<TL>::template load<LM>(grid), smp, ld3(rays[i].o), ld3(rays[i].d), m, stats ? &hs : nullptr);
+    dv3 L = trace_hetero<false, LM, TL>(S, GridTrT<TL, EM>::template load<LM>(grid), smp, ld3(rays[i].o), ld3(rays[i].d), m, stats ? &hs : nullptr);
     if (stats) {  /* vpt_debug_hetero_steps */
         atomicAdd(&stats[0], hs.tracks);
         atomicAdd(&stats[1], hs.steps);
@@ -150,7 +166,7 @@ __global__ __launch_bounds__(256) void trace_batch_hetero_kernel(const vpt_ray* 
 }
 
 /* estimator 11's per-sample call: the same on the ratio-tracking policy (no step statistics) */
-template <bool LM, bool TL>
+template <bool LM, bool TL, bool EM = false>
 __global__ __launch_bounds__(256) void trace_batch_hetero_ratio_kernel(const vpt_ray* __restrict__ rays,
                                                                        const uint64_t* __restrict__ states, int n, Medium m,
                                                                        const DevScene* __restrict__ S,
@@ -162,7 +178,7 @@ __global__ __launch_bounds__(256) void trace_batch_hetero_ratio_kernel(const vpt
     Sampler<false> smp;
     smp.X = states[i] & 0xFFFFFFFFFFFFull;
     smp.g = m.g;
-    dv3 L = trace_hetero<false, LM, TL>(S, GridRatioTr<LM, TL>::template load<LM>(grid), smp, ld3(rays[i].o), ld3(rays[i].d), m);
+    dv3 L = trace_hetero<false, LM, TL>(S, GridRatioTr<LM, TL, EM>::template load<LM>(grid), smp, ld3(rays[i].o), ld3(rays[i].d), m);
     out[3 * i] = L.x;
     out[3 * i + 1] = L.y;
     out[3 * i + 2] = L.z;
@@ -178,7 +194,7 @@ __global__ __launch_bounds__(256) void grid_probe_kernel(const vpt_grid_view* __
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const vpt_grid_view G = *grid;
+    const vpt_grid_fields G = *grid;
     const double o[3] = {rays[i].o[0], rays[i].o[1], rays[i].o[2]}, d[3] = {rays[i].d[0], rays[i].d[1], rays[i].d[2]};
     uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
     tau[i] = TL ? vpt_grid_tau_tl(&G, o, d, tmax[i]) : vpt_grid_tau(&G, o, d, tmax[i]);
@@ -198,7 +214,7 @@ __global__ __launch_bounds__(256) void grid_ratio_probe_kernel(const vpt_grid_vi
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const vpt_grid_view G = *grid;
+    const vpt_grid_fields G = *grid;
     const double o[3] = {rays[i].o[0], rays[i].o[1], rays[i].o[2]}, d[3] = {rays[i].d[0], rays[i].d[1], rays[i].d[2]};
     uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
     uint32_t ns = 0;
@@ -207,6 +223,29 @@ __global__ __launch_bounds__(256) void grid_ratio_probe_kernel(const vpt_grid_vi
     states_out[i] = X;
     if (steps) steps[i] = ns;
 }
+
+#if VPT_HETERO_EM
+/* the emitting tracks (vpt_grid.h), one ray per lane (vpt_grid_emission_probe) */
+template <bool LM, bool TL>
+__global__ __launch_bounds__(256) void grid_emission_probe_kernel(const vpt_grid_view* __restrict__ grid, double sigma_t,
+                                                                  const vpt_ray* __restrict__ rays, const double* __restrict__ tmax,
+                                                                  const uint64_t* __restrict__ states, int n, double* t_coll,
+                                                                  double* esum, uint64_t* states_out, uint32_t* steps)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const vpt_grid_view G = *grid;
+    const double o[3] = {rays[i].o[0], rays[i].o[1], rays[i].o[2]}, d[3] = {rays[i].d[0], rays[i].d[1], rays[i].d[2]};
+    uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
+    uint32_t ns = 0;
+    double es = 0.0;
+    t_coll[i] = LM ? vpt_grid_track_lm_em_m(&G, TL, o, d, tmax[i], sigma_t, &X, &ns, &es)
+                   : vpt_grid_track_em_m(&G, TL, o, d, tmax[i], sigma_t, &X, &ns, &es);
+    esum[i] = es;
+    states_out[i] = X;
+    if (steps) steps[i] = ns;
+}
+#endif
 
 }  // namespace
 
@@ -223,10 +262,20 @@ void VPT_HX(vpt_int_hetero_trace_launch)(int est, const vpt_ray* rays, const uin
 {
     if (est == VPT_HETERO_RATIO) return ratio_trace_launch(rays, states, n, m, S, grid, lm, out, out_states);
     const dim3 g((unsigned)((n + 255) / 256)), b(256);
-    if (lm) trace_batch_hetero_kernel<true, TLU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states, stats);
-    else trace_batch_hetero_kernel<false, TLU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states, stats);
+    if (lm) trace_batch_hetero_kernel<true, TLU, EMU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states, stats);
+    else trace_batch_hetero_kernel<false, TLU, EMU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states, stats);
 }
 
+#if VPT_HETERO_EM
+void VPT_HX(vpt_int_grid_emission_probe_launch)(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
+                                                const double* tmax, const uint64_t* states, int n, double* t_coll, double* esum,
+                                                uint64_t* states_out, uint32_t* steps)
+{
+    const dim3 g((unsigned)((n + 255) / 256)), b(256);
+    if (lm) grid_emission_probe_kernel<true, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, t_coll, esum, states_out, steps);
+    else grid_emission_probe_kernel<false, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, t_coll, esum, states_out, steps);
+}
+#else
 void VPT_HX(vpt_int_grid_probe_launch)(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays, const double* tmax,
                                const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out,
                                uint32_t* steps)
@@ -235,6 +284,7 @@ void VPT_HX(vpt_int_grid_probe_launch)(const vpt_grid_view* grid, bool lm, doubl
     if (lm) grid_probe_kernel<true, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, steps);
     else grid_probe_kernel<false, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, steps);
 }
+#endif
 /* run-time flags as compile-time constants: f(std::bool_constant<flag>{}...) */
 template <class F>
 static int with_flags(F f)
@@ -255,7 +305,7 @@ static int simple_launch(const KParams& K, const DevScene* S, bool lm, void* str
     return with_flags([&](auto lmc, auto count, auto f32) {
         constexpr int FB = decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64;
         dim3 grid((unsigned)((K.w + 15) / 16), (unsigned)((K.shard_rows + 15) / 16));
-        render_kernel_simple<EST, decltype(count)::value, FB, decltype(lmc)::value, TLU><<<grid, dim3(256), 0, (hipStream_t)stream>>>(K, S);
+        render_kernel_simple<EST, decltype(count)::value, FB, decltype(lmc)::value, TLU, EMU><<<grid, dim3(256), 0, (hipStream_t)stream>>>(K, S);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "render_kernel_simple<%d> launch: %s", EST, hipGetErrorString(e));
         return (int)VPT_OK;
@@ -291,7 +341,7 @@ int VPT_HX(vpt_int_hetero_launch)(int device, const KParams& K, const DevScene* 
 {
     if (K.est == VPT_HETERO_RATIO) return ratio_launch(device, K, S, lm, stream);
     return with_flags([&](auto lmc, auto f32) {
-        return persistent_launch(hetero_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU>,
+        return persistent_launch(hetero_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU, EMU>,
                                  device, K, S, stream);
     }, lm, K.fb == VPT_FB_F32);
 }
@@ -301,10 +351,11 @@ static void ratio_trace_launch(const vpt_ray* rays, const uint64_t* states, int 
                                const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states)
 {
     const dim3 g((unsigned)((n + 255) / 256)), b(256);
-    if (lm) trace_batch_hetero_ratio_kernel<true, TLU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states);
-    else trace_batch_hetero_ratio_kernel<false, TLU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states);
+    if (lm) trace_batch_hetero_ratio_kernel<true, TLU, EMU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states);
+    else trace_batch_hetero_ratio_kernel<false, TLU, EMU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states);
 }
 
+#if !VPT_HETERO_EM
 void VPT_HX(vpt_int_grid_ratio_probe_launch)(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
                                      const double* tmax, const uint64_t* states, int n, double* that, uint64_t* states_out,
                                      uint32_t* steps)
@@ -313,6 +364,7 @@ void VPT_HX(vpt_int_grid_ratio_probe_launch)(const vpt_grid_view* grid, bool lm,
     if (lm) grid_ratio_probe_kernel<true, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, that, states_out, steps);
     else grid_ratio_probe_kernel<false, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, that, states_out, steps);
 }
+#endif
 
 static int ratio_simple_launch(const KParams& K, const DevScene* S, bool lm, void* stream)
 {
@@ -322,7 +374,7 @@ static int ratio_simple_launch(const KParams& K, const DevScene* S, bool lm, voi
 static int ratio_launch(int device, const KParams& K, const DevScene* S, bool lm, void* stream)
 {
     return with_flags([&](auto lmc, auto f32) {
-        return persistent_launch(hetero_ratio_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU>,
+        return persistent_launch(hetero_ratio_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU, EMU>,
                                  device, K, S, stream);
     }, lm, K.fb == VPT_FB_F32);
 }

@@ -39,6 +39,19 @@ int vpt_fail(int code, const char* fmt, ...)
 
 void vpt_clear_error(void) { g_err.clear(); }
 
+/* an emission grid and its colour (rgb may be NULL: the voxels only) */
+int vpt_int_emission_check(const float* eps, size_t nv, const double rgb[3], const char* who)
+{
+    if (rgb)
+        for (int c = 0; c < 3; ++c)
+            if (!(rgb[c] >= 0.0 && rgb[c] - rgb[c] == 0.0))
+                return vpt_fail(VPT_E_INVALID, "%s: rgb[%d] = %g (finite and >= 0)", who, c, rgb[c]);
+    for (size_t i = 0; i < nv; ++i)
+        if (!(eps[i] >= 0.0f && eps[i] - eps[i] == 0.0f))
+            return vpt_fail(VPT_E_INVALID, "%s: emission value %g at voxel %zu (finite and >= 0)", who, (double)eps[i], i);
+    return VPT_OK;
+}
+
 /* vpt_grid_bad (csrc/vpt_grid.h) as a status with its message */
 int vpt_int_grid_check(const vpt_grid_desc* desc, const float* density, const char* who)
 {
@@ -246,6 +259,38 @@ static int grid_probe_host(const char* who, const vpt_grid_desc* desc, const flo
         const double tc = block ? vpt_grid_track_lm_m(&G, interp, rays[i].o, rays[i].d, tmax[i], sigma_t, &X, &ns)
                                 : vpt_grid_track_m(&G, interp, rays[i].o, rays[i].d, tmax[i], sigma_t, &X, &ns);
         if (t_coll) t_coll[i] = tc;
+        if (states_out) states_out[i] = X;
+        if (steps) steps[i] = ns;
+    }
+    return VPT_OK;
+}
+
+int vpt_grid_emission_probe_host(const vpt_grid_desc* desc, const float* density, const float* eps, int block, int interp,
+                                 double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states, int n,
+                                 double* t_coll, double* esum, uint64_t* states_out, uint32_t* steps)
+{
+    const char* who = "vpt_grid_emission_probe_host";
+    vpt_clear_error();
+    if (!rays || !tmax || !states || !eps || n < 0) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
+    if (block < 0) return vpt_fail(VPT_E_INVALID, "%s: block %d (0 = the global majorant, else >= 1)", who, block);
+    if (interp != VPT_GRID_NEAREST && interp != VPT_GRID_TRILINEAR)
+        return vpt_fail(VPT_E_INVALID, "%s: interp %d (0 = nearest, 1 = trilinear)", who, interp);
+    int rc = vpt_int_grid_check(desc, density, who);
+    if (rc) return rc;
+    rc = vpt_int_emission_check(eps, (size_t)desc->nx * (size_t)desc->ny * (size_t)desc->nz, nullptr, who);
+    if (rc) return rc;
+    vpt_grid_view G;
+    std::vector<float> maj;
+    probe_view(&G, maj, desc, density, block, interp);
+    G.emit = eps;
+    for (int i = 0; i < n; ++i) {
+        uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
+        uint32_t ns = 0;
+        double es = 0.0;
+        const double tc = block ? vpt_grid_track_lm_em_m(&G, interp, rays[i].o, rays[i].d, tmax[i], sigma_t, &X, &ns, &es)
+                                : vpt_grid_track_em_m(&G, interp, rays[i].o, rays[i].d, tmax[i], sigma_t, &X, &ns, &es);
+        if (t_coll) t_coll[i] = tc;
+        if (esum) esum[i] = es;
         if (states_out) states_out[i] = X;
         if (steps) steps[i] = ns;
     }

@@ -24,5 +24,7 @@ void vpt_int_cam_table(const double* o, const double* centre, size_t stride, int
 
 /* vpt_grid_bad's verdict on a grid as a vpt_status with its message (vpt_host.cpp) */
 int vpt_int_grid_check(const vpt_grid_desc* desc, const float* density, const char* who);
+/* an emission grid of nv voxels and its colour: finite and >= 0, else VPT_E_INVALID with its message (vpt_host.cpp) */
+int vpt_int_emission_check(const float* eps, size_t nv, const double rgb[3], const char* who);
 
 #endif

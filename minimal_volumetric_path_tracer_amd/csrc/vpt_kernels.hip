@@ -243,6 +243,9 @@ struct vpt_context {
     vpt_grid_view h_grid = {};
     /* trilinear interpolation (vpt_set_grid_interpolation): the context's mode, in h_grid.interp of every grid */
     int grid_interp = 0;
+    /* emission (vpt_set_emission_grid): the current grid's emission on the device -- the colour's VPT_EMIT_HEAD doubles,
+     * then the voxels that h_grid.emit points to (vpt_hetero.h); NULL: none */
+    double* d_emit = nullptr;
 };
 
 /* The stream's slot, created on first use (or taken over from an idle stream once MAX_STREAM_SLOTS
@@ -464,16 +467,18 @@ static bool hetero_simple_kernel()
  * counting mode and VPT_SIMPLE_KERNEL=1: render_kernel_simple<10 or 11> */
 static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
 {
-    const bool lm = ctx->h_grid.block > 0, tl = ctx->h_grid.interp != 0;
+    const bool lm = ctx->h_grid.block > 0, tl = ctx->h_grid.interp != 0, em = ctx->h_grid.emit != nullptr;
     if (K.counters || hetero_simple_kernel())
-        return (tl ? vpt_int_hetero_simple_launch_tl : vpt_int_hetero_simple_launch)(K, ctx->d_scene, lm, stream);
+        return (em ? (tl ? vpt_int_hetero_simple_launch_em_tl : vpt_int_hetero_simple_launch_em)
+                   : (tl ? vpt_int_hetero_simple_launch_tl : vpt_int_hetero_simple_launch))(K, ctx->d_scene, lm, stream);
     std::lock_guard<std::mutex> lock(ctx->mu);
     StreamSlot* sl = nullptr;
     int rc = stream_slot(ctx, stream, 0, &sl);
     if (rc) return rc;
     K.queue = sl->d_queue;
     HIP_OK(hipMemsetAsync(K.queue, 0, sizeof(unsigned), stream));
-    rc = (tl ? vpt_int_hetero_launch_tl : vpt_int_hetero_launch)(ctx->device, K, ctx->d_scene, lm, stream);
+    rc = (em ? (tl ? vpt_int_hetero_launch_em_tl : vpt_int_hetero_launch_em)
+             : (tl ? vpt_int_hetero_launch_tl : vpt_int_hetero_launch))(ctx->device, K, ctx->d_scene, lm, stream);
     if (rc) return rc;
     return slot_done(sl, stream);
 }
@@ -778,6 +783,7 @@ void vpt_context_destroy(vpt_context* ctx)
     if (ctx->d_grid) (void)hipFree(ctx->d_grid);
     if (ctx->d_rho) (void)hipFree(ctx->d_rho);
     if (ctx->d_maj) (void)hipFree(ctx->d_maj);
+    if (ctx->d_emit) (void)hipFree(ctx->d_emit);
     for (auto& sl : ctx->slots) {
         if (sl->done) (void)hipEventSynchronize(sl->done);
         if (sl->d_partials) (void)hipFree(sl->d_partials);
@@ -862,8 +868,11 @@ int vpt_set_density_grid(vpt_context* ctx, const vpt_grid_desc* desc, const floa
         HIP_OK(hipDeviceSynchronize());
         if (ctx->d_rho) (void)hipFree(ctx->d_rho);
         if (ctx->d_maj) (void)hipFree(ctx->d_maj);
+        if (ctx->d_emit) (void)hipFree(ctx->d_emit);
         ctx->d_rho = nullptr;
         ctx->d_maj = nullptr;
+        ctx->d_emit = nullptr;  /* the emission grid goes with the grid whose dimensions it has */
+        ctx->h_grid.emit = nullptr;
         ctx->has_grid = 0;  /* maj_block and grid_interp stay: the next grid gets its majorant grid and its mode */
         return VPT_OK;
     }
@@ -889,10 +898,49 @@ int vpt_set_density_grid(vpt_context* ctx, const vpt_grid_desc* desc, const floa
     }
     if (ctx->d_rho) (void)hipFree(ctx->d_rho);
     if (ctx->d_maj) (void)hipFree(ctx->d_maj);
+    if (ctx->d_emit) (void)hipFree(ctx->d_emit);  /* the previous grid's emission: G.emit is NULL */
     ctx->d_rho = d_rho;
     ctx->d_maj = d_maj;
+    ctx->d_emit = nullptr;
     ctx->h_grid = G;
     ctx->has_grid = 1;
+    return VPT_OK;
+}
+
+int vpt_set_emission_grid(vpt_context* ctx, const float* eps, const double rgb[3])
+{
+    vpt_clear_error();
+    if (!ctx) return vpt_fail(VPT_E_INVALID, "vpt_set_emission_grid: NULL context");
+    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "vpt_set_emission_grid: no density grid set (vpt_set_density_grid)");
+    vpt_grid_view G = ctx->h_grid;
+    double* d_emit = nullptr;
+    HIP_OK(hipSetDevice(ctx->device));
+    if (eps) {
+        if (!rgb) return vpt_fail(VPT_E_INVALID, "vpt_set_emission_grid: rgb is NULL");
+        const size_t nv = (size_t)G.n[0] * (size_t)G.n[1] * (size_t)G.n[2];
+        int rc = vpt_int_emission_check(eps, nv, rgb, "vpt_set_emission_grid");
+        if (rc) return rc;
+        const double head[VPT_EMIT_HEAD] = {rgb[0], rgb[1], rgb[2], 0.0};
+        HIP_OK(hipMalloc((void**)&d_emit, sizeof head + nv * sizeof(float)));
+        hipError_t e = hipMemcpy(d_emit, head, sizeof head, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_emit + VPT_EMIT_HEAD, eps, nv * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d_emit);
+            return vpt_fail(VPT_E_HIP, "vpt_set_emission_grid: %s", hipGetErrorString(e));
+        }
+        G.emit = (const float*)(d_emit + VPT_EMIT_HEAD);
+    } else {
+        G.emit = nullptr;
+    }
+    hipError_t e = hipDeviceSynchronize();  /* nothing in flight reads the view or the previous emission grid */
+    if (e == hipSuccess) e = hipMemcpy(ctx->d_grid, &G, sizeof G, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (d_emit) (void)hipFree(d_emit);
+        return vpt_fail(VPT_E_HIP, "vpt_set_emission_grid: %s", hipGetErrorString(e));
+    }
+    if (ctx->d_emit) (void)hipFree(ctx->d_emit);
+    ctx->d_emit = d_emit;
+    ctx->h_grid = G;
     return VPT_OK;
 }
 
@@ -1076,6 +1124,51 @@ int vpt_grid_ratio_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, 
     return VPT_OK;
 }
 
+int vpt_grid_emission_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
+                            int n, double* t_coll, double* esum, uint64_t* states_out, uint32_t* steps)
+{
+    vpt_clear_error();
+    if (!ctx || !rays || !tmax || !states || !t_coll || !esum || !states_out || n < 0)
+        return vpt_fail(VPT_E_INVALID, "vpt_grid_emission_probe: bad arguments");
+    if (!ctx->has_grid || !ctx->h_grid.emit)
+        return vpt_fail(VPT_E_INVALID, "vpt_grid_emission_probe: no emission grid set (vpt_set_emission_grid)");
+    if (n == 0) return VPT_OK;
+    HIP_OK(hipSetDevice(ctx->device));
+    uint32_t* dst = nullptr;
+    vpt_ray* dr = nullptr;
+    uint64_t *ds = nullptr, *dso = nullptr;
+    double *dtm = nullptr, *dtc = nullptr, *des = nullptr;
+    const size_t nn = (size_t)n;
+    hipError_t e = hipMalloc((void**)&dr, sizeof(vpt_ray) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&ds, sizeof(uint64_t) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&dso, sizeof(uint64_t) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&dtm, sizeof(double) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&dtc, sizeof(double) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&des, sizeof(double) * nn);
+    if (e == hipSuccess && steps) e = hipMalloc((void**)&dst, sizeof(uint32_t) * nn);
+    if (e == hipSuccess) e = hipMemcpy(dr, rays, sizeof(vpt_ray) * nn, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ds, states, sizeof(uint64_t) * nn, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dtm, tmax, sizeof(double) * nn, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        (ctx->h_grid.interp ? vpt_int_grid_emission_probe_launch_em_tl : vpt_int_grid_emission_probe_launch_em)(
+            ctx->d_grid, ctx->h_grid.block > 0, sigma_t, dr, dtm, ds, n, dtc, des, dso, dst);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(t_coll, dtc, sizeof(double) * nn, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(esum, des, sizeof(double) * nn, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(states_out, dso, sizeof(uint64_t) * nn, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && steps) e = hipMemcpy(steps, dst, sizeof(uint32_t) * nn, hipMemcpyDeviceToHost);
+    if (dst) (void)hipFree(dst);
+    if (dr) (void)hipFree(dr);
+    if (ds) (void)hipFree(ds);
+    if (dso) (void)hipFree(dso);
+    if (dtm) (void)hipFree(dtm);
+    if (dtc) (void)hipFree(dtc);
+    if (des) (void)hipFree(des);
+    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "vpt_grid_emission_probe: %s", hipGetErrorString(e));
+    return VPT_OK;
+}
+
 int vpt_render_device(vpt_context* ctx, const vpt_params* p, void* d_out, void* stream)
 {
     vpt_clear_error();
@@ -1188,7 +1281,8 @@ static int trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* ray
         case 7: trace_batch_kernel<7><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         case 8: trace_batch_kernel<8><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         case VPT_HETERO_FREE:
-        case VPT_HETERO_RATIO: (ctx->h_grid.interp ? vpt_int_hetero_trace_launch_tl : vpt_int_hetero_trace_launch)(m->estimator, dr, ds, n, mm, ctx->d_scene, ctx->d_grid, ctx->h_grid.block > 0, dout, dso, stats); break;
+        case VPT_HETERO_RATIO: (ctx->h_grid.emit ? (ctx->h_grid.interp ? vpt_int_hetero_trace_launch_em_tl : vpt_int_hetero_trace_launch_em)
+                                                 : (ctx->h_grid.interp ? vpt_int_hetero_trace_launch_tl : vpt_int_hetero_trace_launch))(m->estimator, dr, ds, n, mm, ctx->d_scene, ctx->d_grid, ctx->h_grid.block > 0, dout, dso, stats); break;
         default: trace_batch_kernel<9><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         }
         e = hipGetLastError();

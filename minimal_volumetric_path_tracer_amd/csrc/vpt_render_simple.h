@@ -89,8 +89,9 @@ namespace {
 
 using namespace vpt;
 
-/* LM, TL: estimators 10 and 11 only -- the grid has a majorant grid, the field is trilinear (vpt_hetero.h) */
-template <int EST, bool COUNT, int FB, bool LM = false, bool TL = false>
+/* LM, TL, EM: estimators 10 and 11 only -- the grid has a majorant grid, the field is trilinear, the context holds an
+ * emission grid (vpt_hetero.h) */
+template <int EST, bool COUNT, int FB, bool LM = false, bool TL = false, bool EM = false>
 __global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const DevScene* __restrict__ S)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -118,9 +119,9 @@ __global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const Dev
         smp.cnt.draw_mismatch = 0;
         const dv3 dir = camera_dir(P, smp, x, row.y);
         dv3 L;
-        if constexpr (EST == VPT_HETERO_FREE) L = trace_hetero<COUNT, LM, TL>(S, GridTrT<TL>::template load<LM>(P.grid), smp, o, dir, m);
+        if constexpr (EST == VPT_HETERO_FREE) L = trace_hetero<COUNT, LM, TL>(S, GridTrT<TL, EM>::template load<LM>(P.grid), smp, o, dir, m);
         else if constexpr (EST == VPT_HETERO_RATIO)
-            L = trace_hetero<COUNT, LM, TL>(S, GridRatioTr<LM, TL>::template load<LM>(P.grid), smp, o, dir, m);
+            L = trace_hetero<COUNT, LM, TL>(S, GridRatioTr<LM, TL, EM>::template load<LM>(P.grid), smp, o, dir, m);
         else L = trace_sample<EST, COUNT>(S, smp, o, dir, m, EST == 6 ? march_oc : nullptr);
         acc = add(L, acc);
         if (COUNT) {

@@ -145,6 +145,35 @@ def grid_ratio_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, states, major
     return that, so, steps
 
 
+def _emission_args(eps, rgb, shape) -> tuple[np.ndarray, np.ndarray]:
+    """(float32 voxels, float64 colour) of an emission grid for a density grid of `shape` (None: not known here, the
+    library says what is missing); another shape or a colour that is not three numbers is VPT_E_INVALID"""
+    e = np.ascontiguousarray(eps, dtype=np.float32)
+    if shape is not None and e.shape != tuple(shape):
+        raise _lib.VPTError(_lib.VPT_E_INVALID, f"emission grid of shape {e.shape}: the density grid's is {tuple(shape)}")
+    c = np.ascontiguousarray(rgb, dtype=np.float64)
+    if c.shape != (3,):
+        raise _lib.VPTError(_lib.VPT_E_INVALID, f"emission colour of shape {c.shape}: three numbers (r, g, b)")
+    return e, c
+
+
+def grid_emission_probe_host(rho, eps, lo, hi, sigma_t: float, rays, tmax, states, majorant_block: int = 0,
+                             interpolation: str = "nearest"):
+    """csrc/vpt_grid.h's emitting delta track on the host (vpt_grid_emission_probe_host, no GPU): per ray (unit
+    direction) grid_probe_host's collision distance, end state and tentative steps -- bit for bit -- and esum, the sum
+    of rho eps / majorant over the track's tentative collisions (expectation: sigma_t times the integral of
+    T rho eps along the tracked segment).  eps: the emission grid, rho's shape.  Returns (t_coll, esum, states, steps)."""
+    mode = _interp_mode(interpolation)
+    d, r = _grid_args(rho, lo, hi)
+    e, _ = _emission_args(eps, (1, 1, 1), r.shape)
+    ry, t, s, tc, es, so = _probe_args(rays, tmax, states)
+    steps = np.zeros(len(ry), dtype=np.uint32)
+    check(lib().vpt_grid_emission_probe_host(byref(d), r.ctypes.data, e.ctypes.data, int(majorant_block), mode, float(sigma_t),
+                                             ry.ctypes.data, t.ctypes.data, s.ctypes.data, len(ry), tc.ctypes.data,
+                                             es.ctypes.data, so.ctypes.data, steps.ctypes.data))
+    return tc, es, so, steps
+
+
 def _set_grid_with_block(owner, block, upload, interpolation=None) -> None:
     """set_density_grid(..., majorant_block=block, interpolation=...) of Tracer and MultiTracer: the grid first -- a
     rejected grid leaves the grid and the settings as they were -- then the block size and the interpolation, where
@@ -212,6 +241,7 @@ class Tracer:
         self.device = device
         self._majorant_block = 0  # the context's setting (vpt_set_grid_majorant_block)
         self._grid_interpolation = "nearest"  # the context's setting (vpt_set_grid_interpolation)
+        self._grid_shape = None  # [nz, ny, nx] of the current density grid: what an emission grid has to have
         self.set_scene(default_scene() if spheres is None else spheres)
 
     def close(self) -> None:
@@ -232,14 +262,35 @@ class Tracer:
 
     # ---- heterogeneous medium (estimator "hetero") ----
     def set_density_grid(self, rho, lo, hi, majorant_block: Optional[int] = None,
-                         interpolation: Optional[str] = None) -> None:
+                         interpolation: Optional[str] = None, emission=None, emission_rgb=(1, 1, 1)) -> None:
         """The density grid of estimator "hetero": rho of shape [nz, ny, nx] (float32, finite, >= 0) in the world
         box [lo, hi], zero outside; sigma_a / sigma_s are then per unit density.  Kept across set_scene.
         majorant_block: set_majorant_block for this and later grids (None leaves the tracer's setting alone); a
-        grid that is rejected leaves the setting as it was.  interpolation: set_grid_interpolation in the same way."""
+        grid that is rejected leaves the setting as it was.  interpolation: set_grid_interpolation in the same way.
+        emission: set_emission_grid(emission, emission_rgb) for this grid; a new density grid always drops the
+        previous grid's emission."""
         d, r = _grid_args(rho, lo, hi)
-        _set_grid_with_block(self, majorant_block, lambda: check(lib().vpt_set_density_grid(self._ctx, byref(d), r.ctypes.data)),
-                             interpolation)
+        if emission is not None:
+            _emission_args(emission, emission_rgb, r.shape)  # rejected before anything is uploaded
+        def upload():  # the shape goes with the grid the context holds, whatever the settings after it do
+            check(lib().vpt_set_density_grid(self._ctx, byref(d), r.ctypes.data))
+            self._grid_shape = r.shape
+
+        _set_grid_with_block(self, majorant_block, upload, interpolation)
+        if emission is not None:
+            self.set_emission_grid(emission, emission_rgb)
+
+    def set_emission_grid(self, eps, rgb=(1, 1, 1)) -> None:
+        """Volumetric emission for the "hetero" estimators: eps of the density grid's shape (float32, finite, >= 0),
+        looked up as the density is, and a colour rgb (finite, >= 0).  The medium emits sigma_a rho(x) eps(x) rgb per
+        unit length (Kirchhoff's form: no absorption or no density, no emission), scored on every tentative collision
+        of the delta track without a random draw, so paths and draw counts stay what they are.  Needs a density grid
+        and goes with it: a new or cleared density grid drops it; the majorant block and the interpolation do not."""
+        e, c = _emission_args(eps, rgb, self._grid_shape)
+        check(lib().vpt_set_emission_grid(self._ctx, e.ctypes.data, c.ctypes.data))
+
+    def clear_emission_grid(self) -> None:
+        check(lib().vpt_set_emission_grid(self._ctx, None, None))
 
     def set_majorant_block(self, block: int) -> None:
         """Local majorants for delta tracking: super-voxels of `block` voxels per axis, each with its own
@@ -257,6 +308,16 @@ class Tracer:
 
     def clear_density_grid(self) -> None:
         check(lib().vpt_set_density_grid(self._ctx, None, None))
+        self._grid_shape = None
+
+    def grid_emission_probe(self, sigma_t: float, rays, tmax, states):
+        """grid_emission_probe_host's quantities for the tracer's density and emission grids, majorant block and
+        interpolation, computed on the GPU (vpt_grid_emission_probe): (t_coll, esum, states, steps)."""
+        ry, t, s, tc, es, so = _probe_args(rays, tmax, states)
+        steps = np.zeros(len(ry), dtype=np.uint32)
+        check(lib().vpt_grid_emission_probe(self._ctx, float(sigma_t), ry.ctypes.data, t.ctypes.data, s.ctypes.data, len(ry),
+                                            tc.ctypes.data, es.ctypes.data, so.ctypes.data, steps.ctypes.data))
+        return tc, es, so, steps
 
     def grid_probe(self, sigma_t: float, rays, tmax, states, return_steps: bool = False):
         """grid_probe_host's quantities for the tracer's grid and its majorant block, computed on the GPU
@@ -509,16 +570,33 @@ class MultiTracer:
         self.n_gpus = n_gpus
         self._majorant_block = 0
         self._grid_interpolation = "nearest"
+        self._grid_shape = None
         s = np.ascontiguousarray(default_scene() if spheres is None else spheres, dtype=SPHERE_DTYPE)
         check(lib().vpt_multi_set_scene(self._m, s.ctypes.data, len(s)))
         self.spheres = s
 
     def set_density_grid(self, rho, lo, hi, majorant_block: Optional[int] = None,
-                         interpolation: Optional[str] = None) -> None:
+                         interpolation: Optional[str] = None, emission=None, emission_rgb=(1, 1, 1)) -> None:
         """Tracer.set_density_grid on every rank's context."""
         d, r = _grid_args(rho, lo, hi)
-        _set_grid_with_block(self, majorant_block, lambda: check(lib().vpt_multi_set_density_grid(self._m, byref(d), r.ctypes.data)),
-                             interpolation)
+        if emission is not None:
+            _emission_args(emission, emission_rgb, r.shape)
+        def upload():
+            self._grid_shape = None  # a failure part of the way leaves contexts with and without the new grid
+            check(lib().vpt_multi_set_density_grid(self._m, byref(d), r.ctypes.data))
+            self._grid_shape = r.shape
+
+        _set_grid_with_block(self, majorant_block, upload, interpolation)
+        if emission is not None:
+            self.set_emission_grid(emission, emission_rgb)
+
+    def set_emission_grid(self, eps, rgb=(1, 1, 1)) -> None:
+        """Tracer.set_emission_grid on every rank's context."""
+        e, c = _emission_args(eps, rgb, self._grid_shape)
+        check(lib().vpt_multi_set_emission_grid(self._m, e.ctypes.data, c.ctypes.data))
+
+    def clear_emission_grid(self) -> None:
+        check(lib().vpt_multi_set_emission_grid(self._m, None, None))
 
     def set_majorant_block(self, block: int) -> None:
         """Tracer.set_majorant_block on every rank's context."""
@@ -532,6 +610,7 @@ class MultiTracer:
 
     def clear_density_grid(self) -> None:
         check(lib().vpt_multi_set_density_grid(self._m, None, None))
+        self._grid_shape = None
 
     def render(self, cfg: Optional[RenderConfig] = None, **kw) -> np.ndarray:
         """(height, width, 3), file order; cfg.band_rows (when it cuts the image) is the band size."""
