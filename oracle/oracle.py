@@ -97,6 +97,15 @@ class Oracle:
         L.orc_math_n.restype, L.orc_math_n.argtypes = None, [_I, _P, _P, _P, _I]
         L.orc_hg_phase_sample.restype, L.orc_hg_phase_sample.argtypes = _U, [_D, _P, _U, _P]
         L.orc_hg_phase_value.restype, L.orc_hg_phase_value.argtypes = _D, [_D, _P, _P]
+        # the heterogeneous medium (oracle/vpt_oracle_grid.h): estimators 10 and 11
+        L.orc_set_density_grid.restype, L.orc_set_density_grid.argtypes = _I, [_P, _I, _I, _I, _P, _P, _I, _I]
+        L.orc_clear_density_grid.restype, L.orc_clear_density_grid.argtypes = None, []
+        L.orc_set_emission_grid.restype, L.orc_set_emission_grid.argtypes = _I, [_P, _P]
+        L.orc_clear_emission_grid.restype, L.orc_clear_emission_grid.argtypes = None, []
+        L.orc_hetero_set_fault.restype, L.orc_hetero_set_fault.argtypes = None, [_I]
+        L.orc_grid_probe.restype, L.orc_grid_probe.argtypes = _I, [_D, _P, _P, _P, _I, _P, _P, _P, _P]
+        L.orc_grid_ratio_probe.restype, L.orc_grid_ratio_probe.argtypes = _I, [_D, _P, _P, _P, _I, _P, _P, _P]
+        L.orc_grid_emission_probe.restype, L.orc_grid_emission_probe.argtypes = _I, [_D, _P, _P, _P, _I, _P, _P, _P, _P]
         self.L = L
         self.portable = bool(L.orc_is_portable_math())
         self.prefix = "orc"
@@ -122,9 +131,105 @@ class Oracle:
             pv[i] = self.L.orc_hg_phase_value(g, d.ctypes.data, w[i].ctypes.data)
         return out, st, pv
 
+    # ---- the heterogeneous medium.  The grid, the emission grid and the fault are state of the library, which the
+    # session's fixtures share: whoever sets one resets it in a `finally` (clear_density_grid, set_hetero_fault(0)).
+    INTERPOLATIONS = {"nearest": 0, "trilinear": 1}
+
+    def set_density_grid(self, rho, lo, hi, majorant_block: int = 0, interpolation: str = "nearest", emission=None,
+                         emission_rgb=(1, 1, 1)) -> None:
+        """rho: [nz, ny, nx] (x fastest) in the box [lo, hi]; the arguments of Tracer.set_density_grid, but the block
+        and the mode do not persist: every call states them.  A new grid drops the emission grid."""
+        r = np.ascontiguousarray(rho, dtype=np.float32)
+        if r.ndim != 3:
+            raise ValueError("rho must have shape [nz, ny, nx]")
+        a, b = np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
+        nz, ny, nx = r.shape
+        if self.L.orc_set_density_grid(r.ctypes.data, nx, ny, nz, a.ctypes.data, b.ctypes.data, int(majorant_block),
+                                       self.INTERPOLATIONS[interpolation]) != 0:
+            raise ValueError("oracle: bad density grid")
+        self._grid_shape = r.shape
+        if emission is not None:
+            self.set_emission_grid(emission, emission_rgb)
+
+    def set_emission_grid(self, eps, rgb=(1, 1, 1)) -> None:
+        e = np.ascontiguousarray(eps, dtype=np.float32)
+        c = np.ascontiguousarray(rgb, dtype=np.float64)
+        if e.shape != getattr(self, "_grid_shape", None) or c.shape != (3,):
+            raise ValueError("oracle: the emission grid has the density grid's shape and three colour values")
+        if self.L.orc_set_emission_grid(e.ctypes.data, c.ctypes.data) != 0:
+            raise ValueError("oracle: bad emission grid, or no density grid")
+
+    def clear_emission_grid(self) -> None:
+        self.L.orc_clear_emission_grid()
+
+    def clear_density_grid(self) -> None:
+        self.L.orc_clear_density_grid()
+        self._grid_shape = None
+
+    def set_hetero_fault(self, kind: int) -> None:
+        """test only: the mistake trace_hetero commits on purpose (0: none; oracle/vpt_oracle.c)"""
+        self.L.orc_hetero_set_fault(int(kind))
+
+    @staticmethod
+    def _probe_args(rays, tmax, states):
+        r = np.ascontiguousarray(rays)
+        if r.dtype.itemsize != 48 and r.dtype != np.float64:
+            raise ValueError("rays: records of (o, d), 6 doubles each")
+        n = r.size if r.dtype.itemsize == 48 else r.size // 6
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, dtype=np.float64), (n,)))
+        s = np.ascontiguousarray(states, dtype=np.uint64)
+        if len(s) != n:
+            raise ValueError("rays and states must have the same length")
+        return r, t, s, n
+
+    def grid_probe(self, rho, lo, hi, sigma_t, rays, tmax, states, majorant_block=0, return_steps=False,
+                   interpolation="nearest"):
+        """grid_probe_host's arguments and results: (tau, t_coll, states[, steps]).  Sets the grid and clears it."""
+        r, t, s, n = self._probe_args(rays, tmax, states)
+        tau, tc, so, steps = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32)
+        self.set_density_grid(rho, lo, hi, majorant_block, interpolation)
+        try:
+            rc = self.L.orc_grid_probe(float(sigma_t), r.ctypes.data, t.ctypes.data, s.ctypes.data, n, tau.ctypes.data,
+                                       tc.ctypes.data, so.ctypes.data, steps.ctypes.data)
+        finally:
+            self.clear_density_grid()
+        assert rc == 0
+        return (tau, tc, so, steps) if return_steps else (tau, tc, so)
+
+    def grid_ratio_probe(self, rho, lo, hi, sigma_t, rays, tmax, states, majorant_block=0, interpolation="nearest"):
+        """grid_ratio_probe_host's arguments and results: (That, states, steps)"""
+        r, t, s, n = self._probe_args(rays, tmax, states)
+        that, so, steps = np.zeros(n), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32)
+        self.set_density_grid(rho, lo, hi, majorant_block, interpolation)
+        try:
+            rc = self.L.orc_grid_ratio_probe(float(sigma_t), r.ctypes.data, t.ctypes.data, s.ctypes.data, n,
+                                             that.ctypes.data, so.ctypes.data, steps.ctypes.data)
+        finally:
+            self.clear_density_grid()
+        assert rc == 0
+        return that, so, steps
+
+    def grid_emission_probe(self, rho, eps, lo, hi, sigma_t, rays, tmax, states, majorant_block=0,
+                            interpolation="nearest"):
+        """grid_emission_probe_host's arguments and results: (t_coll, esum, states, steps)"""
+        r, t, s, n = self._probe_args(rays, tmax, states)
+        tc, es, so, steps = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32)
+        self.set_density_grid(rho, lo, hi, majorant_block, interpolation, emission=eps)
+        try:
+            rc = self.L.orc_grid_emission_probe(float(sigma_t), r.ctypes.data, t.ctypes.data, s.ctypes.data, n,
+                                                tc.ctypes.data, es.ctypes.data, so.ctypes.data, steps.ctypes.data)
+        finally:
+            self.clear_density_grid()
+        assert rc == 0
+        return tc, es, so, steps
+
     def trace(self, estimator: int, rays: np.ndarray, states: np.ndarray, sigma_a=0.001, sigma_s=0.009, hg_g=0.0,
               max_depth=0, counters: bool = False, march_step=0.1, march_light=7):
+        """per-sample radiance and end state of include/vpt.h's estimator number (0-11; 10 and 11 need a density
+        grid: without one the radiance is NaN and the state is the start state)"""
         m = Medium(sigma_a, sigma_s, hg_g, max_depth, estimator, march_step, march_light)
+        if getattr(rays, "dtype", None) is not None and rays.dtype.names:  # records of (o, d), as Tracer.trace takes them
+            rays = np.ascontiguousarray(rays).view(np.float64)
         r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
         out = np.zeros((len(r), 3))
         st = np.zeros(len(r), dtype=np.uint64)
@@ -141,13 +246,16 @@ class Oracle:
                y0=0, y1=None, threads=0, counters=False, chunk=None, march_step=0.1, march_light=7):
         """main()'s pixel loop over camera rows [y0, y1); returns (h, w, 3) float64 in file order.
         chunk: samples per partial sum in uniform chunks (spp = the reference's order); None = the
-        GPU's default (vpt_params.chunk_spp == 0): chunks of min(spp, 32), the last 32 tapered
-        (csrc/vpt_chunks.h)."""
+        GPU's default (vpt_params.chunk_spp == 0): for estimators 0-5 chunks of min(spp, 32), the last 64
+        samples tapered (csrc/vpt_chunks.h); for estimators 6-11, whose kernels ignore chunk_spp (include/vpt.h),
+        the reference's order."""
         m = Medium(sigma_a, sigma_s, hg_g, max_depth, estimator, march_step, march_light)
         out = np.zeros((h, w, 3))
         c = Counters()
         taper = 0
-        if chunk is None or chunk == 0:
+        if (chunk is None or chunk == 0) and estimator >= 6:
+            chunk = spp
+        elif chunk is None or chunk == 0:
             chunk, taper = default_chunk(spp), 1
         self.L.orc_render_layout(w, h, spp, chunk, taper, byref(m), seed, y0, h if y1 is None else y1,
                                  out.ctypes.data, threads, byref(c))

@@ -1,0 +1,403 @@
+/*
+ * vpt_oracle_grid.h -- TEST INFRASTRUCTURE ONLY: the oracle's statement of the heterogeneous medium, written
+ * from the specification (the header comments of csrc/vpt_grid.h and csrc/vpt_hetero.h),
+ * not from the walkers: it includes none of the product's grid code and is organised differently.  The product
+ * states every walker once per kind (track, ratio, emitting track; global and local majorant); here ONE generator
+ * yields a ray's tentative points -- the draws, the step count, the boundary test -- for the global or the local
+ * majorant, and ONE consumer applies the rule of the track, of ratio tracking or of the emitting track at each
+ * point.  Everything that draws keeps the specification's operation order, FP64 without contraction.
+ *
+ * Included by vpt_oracle.c after xi(c), M_EXP, M_LOG and v3 exist; plain C11.
+ */
+#ifndef VPT_ORACLE_GRID_H
+#define VPT_ORACLE_GRID_H
+
+#define OG_BIG 1.7976931348623157e+308
+#define OG_MAX_STEPS (1 << 22)
+
+/* ------------------------------------------------------------------ the grid (global state, next to g_s) */
+typedef struct {
+    int set;               /* a density grid is present */
+    int n[3];              /* nx, ny, nz */
+    int interp;            /* 0 nearest, 1 trilinear */
+    int B;                 /* super-voxel size in voxels, 0: global majorant only */
+    int nb[3];             /* super-voxels per axis: ceil(n / B) */
+    double lo[3], hi[3];
+    double inv_cell[3];    /* n / (hi - lo) */
+    double cell[3];        /* (hi - lo) / n */
+    double rho_max;
+    float* rho;            /* [nz][ny][nx] */
+    float* maj;            /* [nbz][nby][nbx], B >= 1 */
+    float* eps;            /* emission grid, rho's layout; NULL: none */
+    double rgb[3];
+} og_grid;
+
+static og_grid g_grid;
+static int g_hetero_fault = 0;  /* orc_hetero_set_fault: the mistake trace_hetero commits on purpose (tests) */
+
+static void og_free(float** p)
+{
+    free(*p);
+    *p = NULL;
+}
+
+static void og_clear(void)
+{
+    og_free(&g_grid.rho);
+    og_free(&g_grid.maj);
+    og_free(&g_grid.eps);
+    memset(&g_grid, 0, sizeof g_grid);
+}
+
+static inline size_t og_at(int ix, int iy, int iz) { return ((size_t)iz * (size_t)g_grid.n[1] + (size_t)iy) * (size_t)g_grid.n[0] + (size_t)ix; }
+
+/* super-voxel majorants: the float32 maximum over the block's voxels; under trilinear the block is dilated by one
+ * voxel on every side (held to the grid), since a point of the block reads the voxels next to it too */
+static void og_build_majorants(void)
+{
+    og_grid* G = &g_grid;
+    const int B = G->B, dil = G->interp ? 1 : 0;
+    for (int a = 0; a < 3; ++a) G->nb[a] = (G->n[a] + B - 1) / B;
+    G->maj = (float*)malloc(sizeof(float) * (size_t)G->nb[0] * (size_t)G->nb[1] * (size_t)G->nb[2]);
+    for (int bz = 0; bz < G->nb[2]; ++bz)
+        for (int by = 0; by < G->nb[1]; ++by)
+            for (int bx = 0; bx < G->nb[0]; ++bx) {
+                const int b[3] = {bx, by, bz};
+                int first[3], last[3];
+                for (int a = 0; a < 3; ++a) {
+                    first[a] = b[a] * B - dil;
+                    last[a] = (b[a] + 1) * B - 1 + dil;
+                    if (first[a] < 0) first[a] = 0;
+                    if (last[a] > G->n[a] - 1) last[a] = G->n[a] - 1;
+                }
+                float mx = 0.0f;
+                for (int z = first[2]; z <= last[2]; ++z)
+                    for (int y = first[1]; y <= last[1]; ++y)
+                        for (int x = first[0]; x <= last[0]; ++x)
+                            if (G->rho[og_at(x, y, z)] > mx) mx = G->rho[og_at(x, y, z)];
+                G->maj[((size_t)bz * (size_t)G->nb[1] + (size_t)by) * (size_t)G->nb[0] + (size_t)bx] = mx;
+            }
+}
+
+/* 0, or -1 for a grid the specification does not define (dimensions, box, a density that is not finite and >= 0) */
+static int og_set(const float* rho, int nx, int ny, int nz, const double lo[3], const double hi[3], int block, int interp)
+{
+    if (nx < 1 || ny < 1 || nz < 1 || block < 0 || (interp != 0 && interp != 1)) return -1;
+    const size_t nv = (size_t)nx * (size_t)ny * (size_t)nz;
+    for (int a = 0; a < 3; ++a)
+        if (!(hi[a] > lo[a]) || !isfinite(lo[a]) || !isfinite(hi[a]) || !isfinite(hi[a] - lo[a])) return -1;
+    for (size_t i = 0; i < nv; ++i)
+        if (!(rho[i] >= 0.0f) || !isfinite(rho[i])) return -1;
+    og_clear();
+    og_grid* G = &g_grid;
+    G->n[0] = nx;
+    G->n[1] = ny;
+    G->n[2] = nz;
+    G->interp = interp;
+    G->B = block;
+    G->rho = (float*)malloc(sizeof(float) * nv);
+    memcpy(G->rho, rho, sizeof(float) * nv);
+    float mx = 0.0f;
+    for (size_t i = 0; i < nv; ++i)
+        if (rho[i] > mx) mx = rho[i];
+    G->rho_max = (double)mx;
+    for (int a = 0; a < 3; ++a) {
+        G->lo[a] = lo[a];
+        G->hi[a] = hi[a];
+        G->inv_cell[a] = (double)G->n[a] / (hi[a] - lo[a]);
+        G->cell[a] = (hi[a] - lo[a]) / (double)G->n[a];
+    }
+    if (block >= 1) og_build_majorants();
+    G->set = 1;
+    return 0;
+}
+
+/* ------------------------------------------------------------------ lookups */
+/* voxel index of one axis: min(n - 1, floor((p - lo) * inv_cell)); a point a hair below lo is held at voxel 0 */
+static int og_voxel(int a, double p)
+{
+    const double f = floor((p - g_grid.lo[a]) * g_grid.inv_cell[a]);
+    if (!(f >= 0.0)) return 0;
+    if (f >= (double)g_grid.n[a]) return g_grid.n[a] - 1;
+    return (int)f;
+}
+
+/* one axis of the trilinear lookup: u = (p - lo) * inv_cell - 0.5 held to [0, n - 1]; i0 = floor(u) held to
+ * [0, max(n - 2, 0)]; i1 = min(i0 + 1, n - 1); f = u - i0 */
+static void og_tl_weights(int a, double p, int* i0, int* i1, double* f)
+{
+    const int n = g_grid.n[a];
+    double u = (p - g_grid.lo[a]) * g_grid.inv_cell[a] - 0.5;
+    if (!(u > 0.0)) u = 0.0;
+    if (u > (double)(n - 1)) u = (double)(n - 1);
+    int i = (int)floor(u);
+    const int top = n - 2 > 0 ? n - 2 : 0;
+    if (i > top) i = top;
+    if (i < 0) i = 0;
+    *i0 = i;
+    *i1 = i + 1 < n - 1 ? i + 1 : n - 1;
+    *f = u - (double)i;
+}
+
+static inline double og_lerp(double a, double b, double f) { return a + f * (b - a); }
+
+/* a field (rho or eps) at a point of the box: the voxel's value, or four lerps along x, two along y, one along z */
+static double og_field(const float* F, const double p[3])
+{
+    if (!g_grid.interp) return (double)F[og_at(og_voxel(0, p[0]), og_voxel(1, p[1]), og_voxel(2, p[2]))];
+    int x0, x1, y0, y1, z0, z1;
+    double fx, fy, fz;
+    og_tl_weights(0, p[0], &x0, &x1, &fx);
+    og_tl_weights(1, p[1], &y0, &y1, &fy);
+    og_tl_weights(2, p[2], &z0, &z1, &fz);
+    const double c00 = og_lerp((double)F[og_at(x0, y0, z0)], (double)F[og_at(x1, y0, z0)], fx);
+    const double c01 = og_lerp((double)F[og_at(x0, y1, z0)], (double)F[og_at(x1, y1, z0)], fx);
+    const double c10 = og_lerp((double)F[og_at(x0, y0, z1)], (double)F[og_at(x1, y0, z1)], fx);
+    const double c11 = og_lerp((double)F[og_at(x0, y1, z1)], (double)F[og_at(x1, y1, z1)], fx);
+    return og_lerp(og_lerp(c00, c01, fy), og_lerp(c10, c11, fy), fz);
+}
+
+static double og_field_on_ray(const float* F, const double o[3], const double d[3], double t)
+{
+    const double p[3] = {o[0] + d[0] * t, o[1] + d[1] * t, o[2] + d[2] * t};
+    return og_field(F, p);
+}
+
+/* the slab test: the interval [*t0, *t1] of o + d t in the box with *t0 >= 0, 0 when there is none; an axis with
+ * d == 0 takes part through o alone (lo <= o < hi) */
+static int og_slab(const double o[3], const double d[3], double* t0, double* t1)
+{
+    double near = 0.0, far = OG_BIG;
+    for (int a = 0; a < 3; ++a) {
+        if (d[a] == 0.0) {
+            if (!(o[a] >= g_grid.lo[a] && o[a] < g_grid.hi[a])) return 0;
+            continue;
+        }
+        const double inv = 1.0 / d[a];
+        const double ta = (g_grid.lo[a] - o[a]) * inv, tb = (g_grid.hi[a] - o[a]) * inv;
+        if (ta != ta || tb != tb) return 0;
+        const double in = ta > tb ? tb : ta, out = ta > tb ? ta : tb;
+        if (in > near) near = in;
+        if (out < far) far = out;
+    }
+    *t0 = near;
+    *t1 = far;
+    return near < far;
+}
+
+static inline int og_argmin3(const double v[3])
+{
+    int a = 0;
+    if (v[1] < v[a]) a = 1;
+    if (v[2] < v[a]) a = 2;
+    return a;
+}
+
+/* ------------------------------------------------------------------ optical depth (no draw) */
+/* planes of the DDA that the optical depth walks: voxel planes lo + k cell (nearest, k = 0 .. n), or the planes of
+ * the n + 1 interpolation cells: lo, lo + (k + 0.5) cell for k = 0 .. n - 1, hi (trilinear, j = 0 .. n + 1) */
+static double og_tau_plane(int a, int j)
+{
+    if (!g_grid.interp) return g_grid.lo[a] + (double)j * g_grid.cell[a];
+    if (j <= 0) return g_grid.lo[a];
+    if (j > g_grid.n[a]) return g_grid.hi[a];
+    return g_grid.lo[a] + ((double)(j - 1) + 0.5) * g_grid.cell[a];
+}
+
+static double og_tau(const double o[3], const double d[3], double tmax)
+{
+    const og_grid* G = &g_grid;
+    double t0, t1;
+    if (!(tmax > 0.0) || !(G->rho_max > 0.0)) return 0.0;
+    if (!og_slab(o, d, &t0, &t1)) return 0.0;
+    const double tend = t1 < tmax ? t1 : tmax;
+    if (!(t0 < tend)) return 0.0;
+    const int tl = G->interp;
+    int cell[3], dir[3], last[3];
+    double next[3], inv[3];
+    for (int a = 0; a < 3; ++a) {
+        const double p = o[a] + d[a] * t0;
+        if (tl) {  /* the interpolation cell: floor((p - lo) * inv_cell - 0.5) + 1 held to [0, n] */
+            const double f = floor((p - G->lo[a]) * G->inv_cell[a] - 0.5) + 1.0;
+            cell[a] = !(f >= 0.0) ? 0 : (f >= (double)G->n[a] ? G->n[a] : (int)f);
+            last[a] = G->n[a];
+        } else {
+            cell[a] = og_voxel(a, p);
+            last[a] = G->n[a] - 1;
+        }
+        dir[a] = d[a] > 0.0 ? 1 : (d[a] < 0.0 ? -1 : 0);
+        inv[a] = dir[a] ? 1.0 / d[a] : 0.0;
+        next[a] = dir[a] ? (og_tau_plane(a, cell[a] + (dir[a] > 0)) - o[a]) * inv[a] : OG_BIG;
+    }
+    double tau = 0.0, t = t0;
+    double r0 = tl ? og_field_on_ray(G->rho, o, d, t) : 0.0;
+    const int cap = G->n[0] + G->n[1] + G->n[2] + (tl ? 7 : 4);
+    for (int k = 0; k < cap; ++k) {
+        const int a = og_argmin3(next);
+        const double te = next[a] < tend ? next[a] : tend;
+        if (te > t) {  /* a piece the rounding left without length is passed over */
+            if (tl) {  /* Simpson: exact for the cubic the field is along the ray inside a cell */
+                const double tm = 0.5 * (t + te);
+                const double rm = og_field_on_ray(G->rho, o, d, tm);
+                const double r1 = og_field_on_ray(G->rho, o, d, te);
+                tau = tau + (((r0 + 4.0 * rm) + r1) * (te - t)) * (1.0 / 6.0);
+                r0 = r1;
+            } else {
+                const double rho = (double)G->rho[og_at(cell[0], cell[1], cell[2])];
+                tau = tau + rho * (te - t);
+            }
+            t = te;
+        }
+        if (!(next[a] < tend)) break;
+        cell[a] += dir[a];
+        if (cell[a] < 0 || cell[a] > last[a]) break;
+        next[a] = (og_tau_plane(a, cell[a] + (dir[a] > 0)) - o[a]) * inv[a];
+    }
+    return tau;
+}
+
+/* ------------------------------------------------------------------ tentative points */
+/* the plane below super-voxel kb of an axis (kb == nb: the plane above the last one): a voxel plane, the two
+ * outermost ones lo and hi themselves */
+static double og_block_plane(int a, int kb)
+{
+    if (kb <= 0) return g_grid.lo[a];
+    if (kb >= g_grid.nb[a]) return g_grid.hi[a];
+    return g_grid.lo[a] + (double)(kb * g_grid.B) * g_grid.cell[a];
+}
+
+typedef struct {
+    const double* o;
+    const double* d;
+    double tmax, sigma_t;
+    double t1, t;          /* the slab's exit, the walk's position */
+    uint32_t steps;        /* xi draws */
+    /* local majorants: the current super-voxel, its exit axis and plane, its majorant */
+    int ib[3], dir[3];
+    double next[3], inv[3];
+    int ax;
+    double te, mu;
+} og_walk;
+
+static double og_block_mu(const og_walk* w)
+{
+    if (!(w->te > w->t)) return 0.0;  /* no length: passed over */
+    return (double)g_grid.maj[((size_t)w->ib[2] * (size_t)g_grid.nb[1] + (size_t)w->ib[1]) * (size_t)g_grid.nb[0] + (size_t)w->ib[0]];
+}
+
+/* 0: the walk draws nothing and ends as "none" (rho_max == 0, or no slab interval) */
+static int og_walk_begin(og_walk* w, const double o[3], const double d[3], double tmax, double sigma_t)
+{
+    double t0;
+    w->o = o;
+    w->d = d;
+    w->tmax = tmax;
+    w->sigma_t = sigma_t;
+    w->steps = 0;
+    if (!(g_grid.rho_max > 0.0)) return 0;
+    if (!og_slab(o, d, &t0, &w->t1)) return 0;
+    w->t = t0;
+    if (g_grid.B >= 1) {
+        for (int a = 0; a < 3; ++a) {
+            w->ib[a] = og_voxel(a, o[a] + d[a] * t0) / g_grid.B;
+            w->dir[a] = d[a] > 0.0 ? 1 : (d[a] < 0.0 ? -1 : 0);
+            w->inv[a] = w->dir[a] ? 1.0 / d[a] : 0.0;
+            w->next[a] = w->dir[a] ? (og_block_plane(a, w->ib[a] + (w->dir[a] > 0)) - o[a]) * w->inv[a] : OG_BIG;
+        }
+        w->ax = og_argmin3(w->next);
+        w->te = w->next[w->ax];
+        w->mu = og_block_mu(w);
+    }
+    return 1;
+}
+
+/* the next tentative point: one draw, one step counted.  1 with the point's distance and majorant, 0 for "none" */
+static int og_walk_next(og_walk* w, orc_ctx* c, double* tc_out, double* mu_out)
+{
+    const og_grid* G = &g_grid;
+    if (G->B < 1) {  /* the global majorant */
+        w->t = w->t + (-M_LOG(1 - xi(c)) / (G->rho_max * w->sigma_t));
+        w->steps++;
+        if (w->t > w->tmax || w->t >= w->t1 || w->t != w->t) return 0;
+        *tc_out = w->t;
+        *mu_out = G->rho_max;
+        return 1;
+    }
+    double rem = -M_LOG(1 - xi(c));  /* the optical depth still to cover */
+    w->steps++;
+    const int max_cross = G->nb[0] + G->nb[1] + G->nb[2] + 4;
+    for (int k = 0; k < max_cross; ++k) {
+        if (w->te > w->t) {
+            if (w->mu > 0.0) {  /* an empty super-voxel is skipped: rem untouched */
+                const double s = w->mu * w->sigma_t;
+                const double tc = w->t + (rem / s);
+                if (tc < w->te) {
+                    if (tc > w->tmax || tc >= w->t1) return 0;
+                    *tc_out = tc;
+                    *mu_out = w->mu;
+                    return 1;
+                }
+                rem = rem - s * (w->te - w->t);
+            }
+            w->t = w->te;
+        }
+        if (!(w->te < w->t1) || w->te > w->tmax) return 0;
+        w->ib[w->ax] += w->dir[w->ax];
+        if (w->ib[w->ax] < 0 || w->ib[w->ax] >= G->nb[w->ax]) return 0;
+        w->next[w->ax] = (og_block_plane(w->ax, w->ib[w->ax] + (w->dir[w->ax] > 0)) - w->o[w->ax]) * w->inv[w->ax];
+        w->ax = og_argmin3(w->next);
+        w->te = w->next[w->ax];
+        w->mu = og_block_mu(w);
+    }
+    return 0;  /* the crossing cap */
+}
+
+/* ------------------------------------------------------------------ the three rules at a tentative point */
+enum { OG_TRACK = 0, OG_RATIO = 1 };
+
+/* OG_TRACK: the collision distance, -1 for "none", NaN for a capped track; with esum != NULL the emitting track
+ * (the grid has eps): every tentative point that passed the boundary test scores (rho * eps) / mu before rho is
+ * tested.  OG_RATIO: the estimate That, NaN when capped.  *steps (optional): the xi draws. */
+static double og_run(int kind, const double o[3], const double d[3], double tmax, double sigma_t, orc_ctx* c,
+                     uint32_t* steps, double* esum)
+{
+    og_walk w;
+    double That = 1.0;
+    if (esum) *esum = 0.0;
+    if (steps) *steps = 0;
+    if (!og_walk_begin(&w, o, d, tmax, sigma_t)) return kind == OG_RATIO ? 1.0 : -1.0;
+    double result = (double)NAN;
+    for (int k = 0; k < OG_MAX_STEPS; ++k) {
+        double tc, mu;
+        if (!og_walk_next(&w, c, &tc, &mu)) {
+            result = kind == OG_RATIO ? That : -1.0;
+            break;
+        }
+        const double rho = og_field_on_ray(g_grid.rho, o, d, tc);
+        if (esum) {
+            const double eps = og_field_on_ray(g_grid.eps, o, d, tc);
+            *esum = *esum + ((rho * eps) / mu);
+        }
+        if (kind == OG_RATIO) {
+            if (rho >= mu) {
+                result = 0.0;
+                break;
+            }
+            That = That * (1.0 - rho / mu);
+        } else {
+            if (rho >= mu) {  /* a certain collision: NO draw */
+                result = tc;
+                break;
+            }
+            if (xi(c) * mu < rho) {
+                result = tc;
+                break;
+            }
+        }
+        w.t = tc;
+    }
+    if (steps) *steps = w.steps;
+    return result;
+}
+
+#endif
