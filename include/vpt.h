@@ -90,15 +90,24 @@ typedef enum {
                                     * transmittance factor; sigma_a, sigma_s are per unit density; a ray that
                                     * leaves the grid without a hit ends its path; rendered by a kernel of its own
                                     * (chunk_spp is ignored, as for 6-9); csrc/vpt_grid.h, csrc/vpt_hetero.h */
-    VPT_HETERO_RATIO = 11          /* extension: VPT_HETERO_FREE statement for statement, with every transmittance
+    VPT_HETERO_RATIO = 11,         /* extension: VPT_HETERO_FREE statement for statement, with every transmittance
                                     * factor a ratio-tracking estimate over the same segment, drawn from the
                                     * sample's own stream where estimator 10 evaluates the factor (a factor it skips
                                     * as an exact zero and a zero-length segment draw nothing): the same
                                     * expectation, other draws, a cost that follows the majorant optical depth and
                                     * not the grid's resolution; honours vpt_set_grid_majorant_block; not in the
                                     * accumulator (VPT_E_UNSUPPORTED) */
+    VPT_HETERO_EQUIANGULAR = 12    /* extension: MISVPTTracerRecursive's control flow in the density grid
+                                    * (VPT_E_INVALID without one): the scattering distance is sampled equi-angularly
+                                    * toward the picked light inside the part of [0, t] the box holds, the surface
+                                    * probability and every transmittance factor are the grid's exact ones, and the
+                                    * local sigma_s rho scales the scattering vertex -- no tracking, no majorant (the
+                                    * majorant block is accepted and ignored), no null collisions; the same
+                                    * expectation as estimator 10 without the 1 / d^2 noise of a vertex near a point
+                                    * light; nearest and trilinear fields; with an emission grid and in the
+                                    * accumulator VPT_E_UNSUPPORTED; csrc/vpt_grid_eqa.h, csrc/vpt_hetero_eqa.h */
 } vpt_estimator;
-#define VPT_NUM_ESTIMATORS 12
+#define VPT_NUM_ESTIMATORS 13
 
 typedef enum {
     VPT_FB_F32 = 0,            /* framebuffer: 3 x float per pixel */
@@ -394,6 +403,22 @@ int vpt_grid_emission_probe(vpt_context* ctx, double sigma_t, const vpt_ray* ray
 int vpt_grid_emission_probe_host(const vpt_grid_desc* desc, const float* density, const float* eps, int block, int interp,
                                  double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states, int n,
                                  double* t_coll, double* esum, uint64_t* states_out, uint32_t* steps);
+
+/* Equi-angular probe (csrc/vpt_grid_eqa.h: vpt_grid_eqa_one; one distance decision of estimator
+ * VPT_HETERO_EQUIANGULAR).  For each of the n rays (unit directions) with surface distance tmax[i], light position
+ * light[3 i .. 3 i + 2] and erand48 state states[i]: psurf[i] = the grid's transmittance over [0, tmax[i]] for sigma_t;
+ * two draws, always -- the equi-angular draw, then the coin; coin < psurf is the surface branch: dist[i] = -1 and
+ * pdf[i] = T[i] = rho_t[i] = +0.  Else dist[i] = the equi-angular distance toward the light inside the part of
+ * [0, tmax[i]] the box holds, pdf[i] = its density times 1 - psurf[i], rho_t[i] = the density at o + d dist[i] and T[i] =
+ * the transmittance over [0, dist[i]] (+0 where rho_t[i] == 0: the path ends there).  states_out[i] = the state after
+ * the two draws.  The GPU probe reads the context's grid and interpolation (VPT_E_INVALID without a grid); the host
+ * probe takes the density and the mode (a vpt_grid_interp).  Host arrays, synchronous. */
+int vpt_grid_eqa_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const double* light,
+                       const uint64_t* states, int n, double* psurf, double* dist, double* pdf, double* T, double* rho_t,
+                       uint64_t* states_out);
+int vpt_grid_eqa_probe_host(const vpt_grid_desc* desc, const float* density, int interp, double sigma_t, const vpt_ray* rays,
+                            const double* tmax, const double* light, const uint64_t* states, int n, double* psurf, double* dist,
+                            double* pdf, double* T, double* rho_t, uint64_t* states_out);
 
 /* PPM writer of main() (src/rt.cpp:812-820): clamp to [0,1] (src/rt.cpp:803), gamma 1/2.2,
  * int(v*255 + .5) (include/mathUtilities.h:43-45), "P3\n%d %d\n255\n" then "%d %d %d " per

@@ -25,6 +25,7 @@ FREE_FLIGHT, MIS_EQUIANGULAR, EXPLICIT_FREE, IMPLICIT_FREE, EXPLICIT_EQUIANGULAR
 RAY_MARCHING_SA, RAY_MARCHING_GLOBAL, RAY_MARCHING_EXPLICIT = 7, 8, 9
 HETERO_FREE = 10
 HETERO_RATIO = 11
+HETERO_EQUIANGULAR = 12
 FB_F32, FB_F64 = 0, 1
 GRID_NEAREST, GRID_TRILINEAR = 0, 1  # vpt_grid_interp
 
@@ -156,6 +157,10 @@ PROTOTYPES = [
                                        c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vpt_grid_ratio_probe_host_ex", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_int, c_double, c_void_p, c_void_p,
                                              c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    ("vpt_grid_eqa_probe", c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vpt_grid_eqa_probe_host", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vpt_write_ppm", c_int, [c_char_p, c_void_p, c_int, c_int, c_int]),
     ("vpt_encode_ppm", c_int64, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64]),
     ("vpt_last_error", c_char_p, []),

@@ -1,0 +1,174 @@
+/*
+ * vpt_hetero_eqa.hip -- the kernels of estimator 12 (VPT_HETERO_EQUIANGULAR, vpt_hetero_eqa.h) in a translation unit of
+ * their own, as vpt_hetero.hip is for estimators 10 and 11: the code objects of those stay what they were.
+ *
+ * hetero_eqa_kernel: the persistent-wave loop of vpt_wave.h on estimator 12's steps (HeteroEqaSteps).  A lane owns one
+ * pixel and runs that pixel's samples strictly in order, so the image is render_kernel_simple<12>'s bit for bit.  The
+ * prologue that stages a grid of at most 64 KiB in LDS is vpt_hetero.hip's, restated as estimator 11 restated it;
+ * there is no majorant grid to stage, because nothing tracks.
+ *
+ * Trilinear interpolation: the unit instantiates one value of TL, VPT_HETERO_TL.  Compiled as it stands (0) it holds the
+ * nearest-lookup kernels and exports the vpt_int_* launches; vpt_hetero_eqa_tl.hip includes this file with
+ * VPT_HETERO_TL = 1 and exports the same launches with the suffix _tl.
+ */
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "vpt_wave.h"
+#include "vpt_internal.h"
+
+#ifndef VPT_HETERO_LDS
+#define VPT_HETERO_LDS 1
+#endif
+#define VPT_HETERO_LDS_BYTES 65536
+#ifndef VPT_HETERO_TL
+#define VPT_HETERO_TL 0
+#endif
+#if VPT_HETERO_TL
+#define VPT_HX(name) name##_tl
+#else
+#define VPT_HX(name) name
+#endif
+
+namespace vpt {
+
+template <bool COUNT, int FB, bool TL>
+__global__ __launch_bounds__(256, 2) void hetero_eqa_kernel(KParams P, const DevScene* __restrict__ S)
+{
+    using TP = GridTrT<TL>;
+    /* the view lives in the steps object from the start, as in hetero_kernel: the walkers take its address */
+    HeteroEqaSteps<TL> st{TP::template load<false>(P.grid)};
+    [[maybe_unused]] auto& G = st.tp.G;
+#if VPT_HETERO_LDS
+    __shared__ float lds_rho[VPT_HETERO_LDS_BYTES / sizeof(float)];
+    {
+        const int64_t nv = (int64_t)G.n[0] * G.n[1] * G.n[2];
+        if (nv <= (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float))) {  /* workgroup-uniform */
+            for (int k = threadIdx.x; k < (int)nv; k += blockDim.x) lds_rho[k] = G.rho[k];
+            __syncthreads();
+            G.rho = lds_rho;
+        }
+    }
+#endif
+    wave_render<HeteroEqaSteps<TL>, COUNT, FB>(P, S, st);
+}
+
+}  // namespace vpt
+
+using namespace vpt;
+
+namespace {
+
+constexpr bool TLU = VPT_HETERO_TL != 0;  /* the unit's value of TL */
+
+/* estimator 12's per-sample call (vpt_hetero_eqa.h) */
+template <bool TL>
+__global__ __launch_bounds__(256) void trace_batch_hetero_eqa_kernel(const vpt_ray* __restrict__ rays,
+                                                                     const uint64_t* __restrict__ states, int n, Medium m,
+                                                                     const DevScene* __restrict__ S,
+                                                                     const vpt_grid_view* __restrict__ grid, double* out,
+                                                                     uint64_t* out_states)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Sampler<false> smp;
+    smp.X = states[i] & 0xFFFFFFFFFFFFull;
+    smp.g = m.g;
+    dv3 L = trace_hetero_eqa<false, TL>(S, GridTrT<TL>::template load<false>(grid), smp, ld3(rays[i].o), ld3(rays[i].d), m);
+    out[3 * i] = L.x;
+    out[3 * i + 1] = L.y;
+    out[3 * i + 2] = L.z;
+    out_states[i] = smp.X;
+}
+
+/* one equi-angular decision per lane (vpt_grid_eqa.h: vpt_grid_eqa_one; vpt_grid_eqa_probe) */
+template <bool TL>
+__global__ __launch_bounds__(256) void grid_eqa_probe_kernel(const vpt_grid_view* __restrict__ grid, double sigma_t,
+                                                             const vpt_ray* __restrict__ rays, const double* __restrict__ tmax,
+                                                             const double* __restrict__ light,
+                                                             const uint64_t* __restrict__ states, int n, double* psurf,
+                                                             double* dist, double* pdf, double* T, double* rho_t,
+                                                             uint64_t* states_out)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const vpt_grid_fields G = *grid;
+    const double o[3] = {rays[i].o[0], rays[i].o[1], rays[i].o[2]}, d[3] = {rays[i].d[0], rays[i].d[1], rays[i].d[2]};
+    const double lp[3] = {light[3 * i], light[3 * i + 1], light[3 * i + 2]};
+    uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
+    double ps, ds, pf, tr, rt;
+    vpt_grid_eqa_one(&G, TL, sigma_t, o, d, tmax[i], lp, &X, &ps, &ds, &pf, &tr, &rt);
+    psurf[i] = ps;
+    dist[i] = ds;
+    pdf[i] = pf;
+    T[i] = tr;
+    rho_t[i] = rt;
+    states_out[i] = X;
+}
+
+/* run-time flags as compile-time constants (vpt_hetero.hip's) */
+template <class F>
+static int with_flags(F f)
+{
+    return f();
+}
+template <class F, class... Bools>
+static int with_flags(F f, bool flag, Bools... rest)
+{
+    if (flag) return with_flags([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
+    return with_flags([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+
+}  // namespace
+
+void VPT_HX(vpt_int_hetero_eqa_trace_launch)(const vpt_ray* rays, const uint64_t* states, int n, const Medium& m,
+                                             const DevScene* S, const vpt_grid_view* grid, double* out, uint64_t* out_states)
+{
+    trace_batch_hetero_eqa_kernel<TLU><<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(rays, states, n, m, S, grid, out,
+                                                                                          out_states);
+}
+
+void VPT_HX(vpt_int_grid_eqa_probe_launch)(const vpt_grid_view* grid, double sigma_t, const vpt_ray* rays, const double* tmax,
+                                           const double* light, const uint64_t* states, int n, double* psurf, double* dist,
+                                           double* pdf, double* T, double* rho_t, uint64_t* states_out)
+{
+    grid_eqa_probe_kernel<TLU><<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(grid, sigma_t, rays, tmax, light, states, n,
+                                                                                  psurf, dist, pdf, T, rho_t, states_out);
+}
+
+/* render_kernel_simple<12> (vpt_render_simple.h): counting mode (K.counters != NULL) and VPT_SIMPLE_KERNEL=1 */
+int VPT_HX(vpt_int_hetero_eqa_simple_launch)(const KParams& K, const DevScene* S, void* stream)
+{
+    return with_flags([&](auto count, auto f32) {
+        constexpr int FB = decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64;
+        dim3 grid((unsigned)((K.w + 15) / 16), (unsigned)((K.shard_rows + 15) / 16));
+        render_kernel_simple<VPT_HETERO_EQUIANGULAR, decltype(count)::value, FB, false, TLU><<<grid, dim3(256), 0, (hipStream_t)stream>>>(K, S);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return vpt_fail(VPT_E_HIP, "render_kernel_simple<%d> launch: %s", (int)VPT_HETERO_EQUIANGULAR, hipGetErrorString(e));
+        return (int)VPT_OK;
+    }, K.counters != nullptr, K.fb == VPT_FB_F32);
+}
+
+/* the persistent-wave kernel on as many workgroups as the device holds, at most one per four tiles (vpt_hetero.hip's
+ * persistent_launch) */
+int VPT_HX(vpt_int_hetero_eqa_launch)(int device, const KParams& K, const DevScene* S, void* stream)
+{
+    return with_flags([&](auto f32) {
+        void (*kern)(KParams, const DevScene*) = hetero_eqa_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, TLU>;
+        int per_cu = 0, cus = 0;
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0);
+        if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+        if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_eqa_kernel: %s", hipGetErrorString(e));
+        int blocks = (per_cu < 1 ? 1 : per_cu) * cus;
+        const int tiles = K.tiles_x * K.tiles_y;
+        const int need = (tiles + 3) / 4;  /* 4 waves per block, one tile per wave to start */
+        if (blocks > need) blocks = need;
+        if (blocks < 1) blocks = 1;
+        kern<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(K, S);
+        e = hipGetLastError();
+        if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_eqa_kernel launch: %s", hipGetErrorString(e));
+        return (int)VPT_OK;
+    }, K.fb == VPT_FB_F32);
+}

@@ -21,6 +21,7 @@
 
 #include "vpt_accum.h"
 #include "vpt_grid.h"
+#include "vpt_grid_eqa.h"
 #include "vpt_internal.h"
 #include "vpt_rng.h"
 
@@ -361,6 +362,34 @@ int vpt_grid_ratio_probe_host_ex(const vpt_grid_desc* desc, const float* density
 {
     return grid_ratio_probe_host("vpt_grid_ratio_probe_host_ex", desc, density, block, interp, sigma_t, rays, tmax, states, n,
                                  that, states_out, steps);
+}
+
+int vpt_grid_eqa_probe_host(const vpt_grid_desc* desc, const float* density, int interp, double sigma_t, const vpt_ray* rays,
+                            const double* tmax, const double* light, const uint64_t* states, int n, double* psurf, double* dist,
+                            double* pdf, double* T, double* rho_t, uint64_t* states_out)
+{
+    const char* who = "vpt_grid_eqa_probe_host";
+    vpt_clear_error();
+    if (!rays || !tmax || !light || !states || n < 0) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
+    if (interp != VPT_GRID_NEAREST && interp != VPT_GRID_TRILINEAR)
+        return vpt_fail(VPT_E_INVALID, "%s: interp %d (0 = nearest, 1 = trilinear)", who, interp);
+    int rc = vpt_int_grid_check(desc, density, who);
+    if (rc) return rc;
+    vpt_grid_view G;
+    std::vector<float> maj;
+    probe_view(&G, maj, desc, density, 0, interp);
+    for (int i = 0; i < n; ++i) {
+        uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
+        double ps, ds, pf, tr, rt;
+        vpt_grid_eqa_one(&G, interp, sigma_t, rays[i].o, rays[i].d, tmax[i], light + 3 * (size_t)i, &X, &ps, &ds, &pf, &tr, &rt);
+        if (psurf) psurf[i] = ps;
+        if (dist) dist[i] = ds;
+        if (pdf) pdf[i] = pf;
+        if (T) T[i] = tr;
+        if (rho_t) rho_t[i] = rt;
+        if (states_out) states_out[i] = X;
+    }
+    return VPT_OK;
 }
 
 /* ---- PPM ---- */

@@ -317,8 +317,11 @@ static int check_medium(const vpt_medium* m)
  * (include/rayMarchingMethods.h:64,153), so the scene needs at least 6 spheres */
 static int check_march(const vpt_context* ctx, const vpt_medium* m)
 {
-    if (m->estimator == VPT_HETERO_FREE || m->estimator == VPT_HETERO_RATIO) {
+    if (m->estimator == VPT_HETERO_FREE || m->estimator == VPT_HETERO_RATIO || m->estimator == VPT_HETERO_EQUIANGULAR) {
         if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "estimator %d needs a density grid (vpt_set_density_grid)", m->estimator);
+        if (m->estimator == VPT_HETERO_EQUIANGULAR && ctx->h_grid.emit)  /* emission is scored on a delta track */
+            return vpt_fail(VPT_E_UNSUPPORTED, "estimator %d does not score an emission grid (estimators 10 and 11 do)",
+                            m->estimator);
         return VPT_OK;
     }
     if (m->estimator < VPT_RAY_MARCHING) return VPT_OK;
@@ -483,11 +486,30 @@ static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
     return slot_done(sl, stream);
 }
 
+/* estimator 12 (vpt_hetero_eqa.hip): hetero_eqa_kernel in the same way; the majorant block plays no part */
+static int launch_hetero_eqa(vpt_context* ctx, KParams K, hipStream_t stream)
+{
+    const bool tl = ctx->h_grid.interp != 0;
+    if (K.counters || hetero_simple_kernel())
+        return (tl ? vpt_int_hetero_eqa_simple_launch_tl : vpt_int_hetero_eqa_simple_launch)(K, ctx->d_scene, stream);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    StreamSlot* sl = nullptr;
+    int rc = stream_slot(ctx, stream, 0, &sl);
+    if (rc) return rc;
+    K.queue = sl->d_queue;
+    HIP_OK(hipMemsetAsync(K.queue, 0, sizeof(unsigned), stream));
+    rc = (tl ? vpt_int_hetero_eqa_launch_tl : vpt_int_hetero_eqa_launch)(ctx->device, K, ctx->d_scene, stream);
+    if (rc) return rc;
+    return slot_done(sl, stream);
+}
+
 template <int EST, bool COUNT, int FB>
 static int launch_one(vpt_context* ctx, KParams K, hipStream_t stream)
 {
     if constexpr (EST == VPT_HETERO_FREE || EST == VPT_HETERO_RATIO) {  /* their kernels live in vpt_hetero.hip */
         return launch_hetero(ctx, K, stream);
+    } else if constexpr (EST == VPT_HETERO_EQUIANGULAR) {  /* and estimator 12's in vpt_hetero_eqa.hip */
+        return launch_hetero_eqa(ctx, K, stream);
     } else {
         const DevScene* S = ctx->d_scene;
         /* counting (vpt_count_work) needs only the totals: the one-lane-per-pixel kernel, which is
@@ -692,6 +714,7 @@ static int launch_render(vpt_context* ctx, KParams K, hipStream_t stream)
         VPT_LAUNCH_EST(9)
         VPT_LAUNCH_EST(10)
         VPT_LAUNCH_EST(11)
+        VPT_LAUNCH_EST(12)
     }
 #undef VPT_LAUNCH_EST
     return vpt_fail(VPT_E_INVALID, "unknown estimator %d", K.est);
@@ -1124,6 +1147,49 @@ int vpt_grid_ratio_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, 
     return VPT_OK;
 }
 
+int vpt_grid_eqa_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const double* light,
+                       const uint64_t* states, int n, double* psurf, double* dist, double* pdf, double* T, double* rho_t,
+                       uint64_t* states_out)
+{
+    vpt_clear_error();
+    if (!ctx || !rays || !tmax || !light || !states || !psurf || !dist || !pdf || !T || !rho_t || !states_out || n < 0)
+        return vpt_fail(VPT_E_INVALID, "vpt_grid_eqa_probe: bad arguments");
+    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "vpt_grid_eqa_probe: no density grid set (vpt_set_density_grid)");
+    if (n == 0) return VPT_OK;
+    HIP_OK(hipSetDevice(ctx->device));
+    vpt_ray* dr = nullptr;
+    uint64_t *ds = nullptr, *dso = nullptr;
+    double *dtm = nullptr, *dl = nullptr, *dres = nullptr;  /* dres: the five result arrays, one behind the other */
+    const size_t nn = (size_t)n;
+    hipError_t e = hipMalloc((void**)&dr, sizeof(vpt_ray) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&ds, sizeof(uint64_t) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&dso, sizeof(uint64_t) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&dtm, sizeof(double) * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&dl, sizeof(double) * 3 * nn);
+    if (e == hipSuccess) e = hipMalloc((void**)&dres, sizeof(double) * 5 * nn);
+    if (e == hipSuccess) e = hipMemcpy(dr, rays, sizeof(vpt_ray) * nn, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ds, states, sizeof(uint64_t) * nn, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dtm, tmax, sizeof(double) * nn, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dl, light, sizeof(double) * 3 * nn, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        (ctx->h_grid.interp ? vpt_int_grid_eqa_probe_launch_tl : vpt_int_grid_eqa_probe_launch)(
+            ctx->d_grid, sigma_t, dr, dtm, dl, ds, n, dres, dres + nn, dres + 2 * nn, dres + 3 * nn, dres + 4 * nn, dso);
+        e = hipGetLastError();
+    }
+    double* const res[5] = {psurf, dist, pdf, T, rho_t};
+    for (int k = 0; k < 5; ++k)
+        if (e == hipSuccess) e = hipMemcpy(res[k], dres + (size_t)k * nn, sizeof(double) * nn, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(states_out, dso, sizeof(uint64_t) * nn, hipMemcpyDeviceToHost);
+    if (dr) (void)hipFree(dr);
+    if (ds) (void)hipFree(ds);
+    if (dso) (void)hipFree(dso);
+    if (dtm) (void)hipFree(dtm);
+    if (dl) (void)hipFree(dl);
+    if (dres) (void)hipFree(dres);
+    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "vpt_grid_eqa_probe: %s", hipGetErrorString(e));
+    return VPT_OK;
+}
+
 int vpt_grid_emission_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
                             int n, double* t_coll, double* esum, uint64_t* states_out, uint32_t* steps)
 {
@@ -1283,6 +1349,7 @@ static int trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* ray
         case VPT_HETERO_FREE:
         case VPT_HETERO_RATIO: (ctx->h_grid.emit ? (ctx->h_grid.interp ? vpt_int_hetero_trace_launch_em_tl : vpt_int_hetero_trace_launch_em)
                                                  : (ctx->h_grid.interp ? vpt_int_hetero_trace_launch_tl : vpt_int_hetero_trace_launch))(m->estimator, dr, ds, n, mm, ctx->d_scene, ctx->d_grid, ctx->h_grid.block > 0, dout, dso, stats); break;
+        case VPT_HETERO_EQUIANGULAR: (ctx->h_grid.interp ? vpt_int_hetero_eqa_trace_launch_tl : vpt_int_hetero_eqa_trace_launch)(dr, ds, n, mm, ctx->d_scene, ctx->d_grid, dout, dso); break;
         default: trace_batch_kernel<9><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         }
         e = hipGetLastError();

@@ -23,7 +23,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (EXPLICIT_EQUIANGULAR, EXPLICIT_FREE, FB_F32, FB_F64, FREE_FLIGHT, HETERO_FREE, HETERO_RATIO, IMPLICIT_FREE, MIS_EQUIANGULAR,
+from ._lib import (EXPLICIT_EQUIANGULAR, EXPLICIT_FREE, FB_F32, FB_F64, FREE_FLIGHT, HETERO_EQUIANGULAR, HETERO_FREE, HETERO_RATIO, IMPLICIT_FREE, MIS_EQUIANGULAR,
                    RAY_DTYPE, RAY_MARCHING, RAY_MARCHING_EXPLICIT, RAY_MARCHING_GLOBAL, RAY_MARCHING_SA, SPHERE_DTYPE,
                    SURFACE_PT, check, lib)
 
@@ -32,7 +32,7 @@ ESTIMATORS = {"ff": FREE_FLIGHT, "free_flight": FREE_FLIGHT, "mis": MIS_EQUIANGU
               "explicit_equiangular": EXPLICIT_EQUIANGULAR, "surface_pt": SURFACE_PT, "path_tracer": SURFACE_PT,
               "ray_marching": RAY_MARCHING, "ray_marching_sa": RAY_MARCHING_SA, "ray_marching_global": RAY_MARCHING_GLOBAL,
               "ray_marching_explicit": RAY_MARCHING_EXPLICIT, "hetero": HETERO_FREE, "hetero_free": HETERO_FREE,
-              "hetero_ratio": HETERO_RATIO}
+              "hetero_ratio": HETERO_RATIO, "hetero_equiangular": HETERO_EQUIANGULAR, "hetero_eqa": HETERO_EQUIANGULAR}
 
 
 def Sphere(r, p, c=(0, 0, 0), radiance=(0, 0, 0), material=0, eta=(0, 0, 0), kappa=(0, 0, 0), alpha=0.0) -> np.ndarray:
@@ -143,6 +143,27 @@ def grid_ratio_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, states, major
                                           t.ctypes.data, s.ctypes.data, len(ry), that.ctypes.data, so.ctypes.data,
                                           steps.ctypes.data))
     return that, so, steps
+
+
+def _eqa_probe_args(rays, tmax, light, states):
+    r, t, s, _, _, so = _probe_args(rays, tmax, states)
+    lp = np.ascontiguousarray(np.broadcast_to(np.asarray(light, dtype=np.float64), (len(r), 3)))
+    return r, t, lp, s, [np.zeros(len(r)) for _ in range(5)], so
+
+
+def grid_eqa_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, light, states, interpolation: str = "nearest"):
+    """csrc/vpt_grid_eqa.h on the host (vpt_grid_eqa_probe_host, no GPU): one equi-angular distance decision of
+    estimator "hetero_equiangular" per ray (unit direction) with surface distance tmax, toward the light position(s)
+    `light` (one, or one per ray), from `states`.  Returns (psurf, dist, pdf, T, rho_t, states): the surface
+    probability, the sampled distance (-1 where the coin chose the surface), its pdf times 1 - psurf, the
+    transmittance to the sampled point, the density there, and the erand48 states after the two draws."""
+    mode = _interp_mode(interpolation)
+    d, r = _grid_args(rho, lo, hi)
+    ry, t, lp, s, res, so = _eqa_probe_args(rays, tmax, light, states)
+    check(lib().vpt_grid_eqa_probe_host(byref(d), r.ctypes.data, mode, float(sigma_t), ry.ctypes.data, t.ctypes.data,
+                                        lp.ctypes.data, s.ctypes.data, len(ry), *[a.ctypes.data for a in res],
+                                        so.ctypes.data))
+    return (*res, so)
 
 
 def _emission_args(eps, rgb, shape) -> tuple[np.ndarray, np.ndarray]:
@@ -336,6 +357,14 @@ class Tracer:
         check(lib().vpt_grid_ratio_probe(self._ctx, float(sigma_t), ry.ctypes.data, t.ctypes.data, s.ctypes.data, len(ry),
                                          that.ctypes.data, so.ctypes.data, steps.ctypes.data))
         return that, so, steps
+
+    def grid_eqa_probe(self, sigma_t: float, rays, tmax, light, states):
+        """grid_eqa_probe_host's quantities for the tracer's grid and interpolation, computed on the GPU
+        (vpt_grid_eqa_probe)."""
+        ry, t, lp, s, res, so = _eqa_probe_args(rays, tmax, light, states)
+        check(lib().vpt_grid_eqa_probe(self._ctx, float(sigma_t), ry.ctypes.data, t.ctypes.data, lp.ctypes.data,
+                                       s.ctypes.data, len(ry), *[a.ctypes.data for a in res], so.ctypes.data))
+        return (*res, so)
 
     # ---- main()'s pixel loop (src/rt.cpp:767-805) ----
     def render(self, cfg: Optional[RenderConfig] = None, **kw) -> np.ndarray:
