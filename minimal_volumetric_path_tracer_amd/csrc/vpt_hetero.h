@@ -309,54 +309,36 @@ struct KParams;  /* a render's launch parameters (vpt_render_simple.h) */
 
 }  // namespace vpt
 
-/* vpt_hetero.hip: the persistent-wave render kernel of estimator 10 or 11 (K.est), enqueued on `stream` (the caller owns
- * the queue word K.queue and has zeroed it in stream order); lm: the grid has a majorant grid (the kernel's LM
- * instantiation) */
-int vpt_int_hetero_launch(int device, const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
-/* render_kernel_simple<10 or 11> for the same render; counting iff K.counters (vpt_count_work's device counters) is set */
-int vpt_int_hetero_simple_launch(const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
-/* the per-sample call (est: 10 or 11) and the grid probes on device arrays, default stream (the caller reads hipGetLastError);
- * lm: the grid behind `grid` has a majorant grid; stats: vpt_debug_hetero_steps' two counters (estimator 10), else NULL; steps: the
- * probe's per-ray tentative steps, else NULL */
-void vpt_int_hetero_trace_launch(int est, const vpt_ray* rays, const uint64_t* states, int n, const vpt::Medium& m,
-                                 const DevScene* S, const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states,
-                                 unsigned long long* stats);
-void vpt_int_grid_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays, const double* tmax,
-                               const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out,
-                               uint32_t* steps);
-void vpt_int_grid_ratio_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
-                                     const double* tmax, const uint64_t* states, int n, double* that, uint64_t* states_out,
-                                     uint32_t* steps);
-/* every launch of the list above also exists with the suffix _tl: the same call on the TL = true kernels (vpt_hetero_tl.hip),
- * which the caller takes where the context's view has interp == 1 */
-int vpt_int_hetero_launch_tl(int device, const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
-int vpt_int_hetero_simple_launch_tl(const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
-void vpt_int_hetero_trace_launch_tl(int est, const vpt_ray* rays, const uint64_t* states, int n, const vpt::Medium& m,
-                                    const DevScene* S, const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states,
-                                    unsigned long long* stats);
-void vpt_int_grid_probe_launch_tl(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays, const double* tmax,
-                                  const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out,
-                                  uint32_t* steps);
-void vpt_int_grid_ratio_probe_launch_tl(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
-                                        const double* tmax, const uint64_t* states, int n, double* that, uint64_t* states_out,
-                                        uint32_t* steps);
-/* and, but for the two probes, with the suffixes _em and _em_tl: the EM = true kernels (vpt_hetero_em.hip,
- * vpt_hetero_em_tl.hip), which the caller takes where the view has an emission grid.  Their probe is the emitting track's */
-int vpt_int_hetero_launch_em(int device, const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
-int vpt_int_hetero_simple_launch_em(const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
-void vpt_int_hetero_trace_launch_em(int est, const vpt_ray* rays, const uint64_t* states, int n, const vpt::Medium& m,
-                                    const DevScene* S, const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states,
-                                    unsigned long long* stats);
-void vpt_int_grid_emission_probe_launch_em(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
-                                           const double* tmax, const uint64_t* states, int n, double* t_coll, double* esum,
-                                           uint64_t* states_out, uint32_t* steps);
-int vpt_int_hetero_launch_em_tl(int device, const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
-int vpt_int_hetero_simple_launch_em_tl(const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
-void vpt_int_hetero_trace_launch_em_tl(int est, const vpt_ray* rays, const uint64_t* states, int n, const vpt::Medium& m,
-                                       const DevScene* S, const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states,
-                                       unsigned long long* stats);
-void vpt_int_grid_emission_probe_launch_em_tl(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
-                                              const double* tmax, const uint64_t* states, int n, double* t_coll, double* esum,
-                                              uint64_t* states_out, uint32_t* steps);
+/* What a code object of estimators 10 and 11 exports: its launches.  vpt_hetero.hip defines one table per unit, the four
+ * units being the values of (TL, EM) -- nearest or trilinear lookup (the view's interp word), without or with the emission
+ * grid -- and the caller picks the table in one place (vpt_kernels.hip hetero_unit).  lm: the grid behind the view has a
+ * majorant grid (the kernel's LM instantiation). */
+struct vpt_hetero_unit {
+    /* the persistent-wave render kernel of estimator 10 or 11 (K.est), enqueued on `stream` (the caller owns the queue
+     * word K.queue and has zeroed it in stream order) */
+    int (*launch)(int device, const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
+    /* render_kernel_simple<10 or 11> for the same render; counting iff K.counters (vpt_count_work's device counters) is set */
+    int (*simple_launch)(const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
+    /* the per-sample call (est: 10 or 11) and, below, the probes on device arrays, default stream (the caller reads
+     * hipGetLastError); stats: vpt_debug_hetero_steps' two counters (estimator 10), else NULL; steps: a probe's per-ray
+     * tentative steps, else NULL */
+    void (*trace_launch)(int est, const vpt_ray* rays, const uint64_t* states, int n, const vpt::Medium& m, const DevScene* S,
+                         const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states, unsigned long long* stats);
+    /* the two grid probes: the EM = false units', NULL in the others */
+    void (*grid_probe_launch)(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays, const double* tmax,
+                              const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out,
+                              uint32_t* steps);
+    void (*grid_ratio_probe_launch)(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
+                                    const double* tmax, const uint64_t* states, int n, double* that, uint64_t* states_out,
+                                    uint32_t* steps);
+    /* the emitting track's probe: the EM = true units', NULL in the others */
+    void (*grid_emission_probe_launch)(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
+                                       const double* tmax, const uint64_t* states, int n, double* t_coll, double* esum,
+                                       uint64_t* states_out, uint32_t* steps);
+};
+extern const vpt_hetero_unit vpt_int_hetero_unit;        /* vpt_hetero.hip: TL = false, EM = false */
+extern const vpt_hetero_unit vpt_int_hetero_unit_tl;     /* vpt_hetero_tl.hip: TL = true */
+extern const vpt_hetero_unit vpt_int_hetero_unit_em;     /* vpt_hetero_em.hip: EM = true */
+extern const vpt_hetero_unit vpt_int_hetero_unit_em_tl;  /* vpt_hetero_em_tl.hip: both */
 
 #endif

@@ -17,23 +17,24 @@
  * the occupancy: the registers already hold it at two workgroups per CU.
  *
  * Trilinear interpolation: every kernel here takes the template parameter TL (vpt_hetero.h) and the unit instantiates
- * one value of it, VPT_HETERO_TL.  Compiled as it stands (0) the unit holds the nearest-lookup kernels and exports the
- * vpt_int_* launches; vpt_hetero_tl.hip includes this file with VPT_HETERO_TL = 1 and exports the same launches with
- * the suffix _tl, so the trilinear kernels are a code object of their own and this unit's stays what it was.  The LDS
- * prologue serves both lookups as it is.
+ * one value of it, VPT_HETERO_TL.  Compiled as it stands (0) the unit holds the nearest-lookup kernels and exports their
+ * launches as the table vpt_int_hetero_unit (vpt_hetero.h); vpt_hetero_tl.hip includes this file with VPT_HETERO_TL = 1
+ * and exports vpt_int_hetero_unit_tl, so the trilinear kernels are a code object of their own and this unit's stays what
+ * it was.  The LDS prologue serves both lookups as it is.
  *
  * Emission: the template parameter EM (vpt_hetero.h) in the same way, VPT_HETERO_EM.  vpt_hetero_em.hip and
- * vpt_hetero_em_tl.hip include this file with VPT_HETERO_EM = 1 and export the launches with the suffixes _em and _em_tl
- * (the emitting track's probe in place of the two grid probes), two more code objects; this unit's kernels and the
+ * vpt_hetero_em_tl.hip include this file with VPT_HETERO_EM = 1 and export vpt_int_hetero_unit_em and _em_tl (the
+ * emitting track's probe in place of the two grid probes), two more code objects; this unit's kernels and the
  * trilinear unit's stay what they were.  The emission grid is read from global memory: the LDS prologue stages the
  * density and the majorants as before.
+ *
+ * The launches at the end of the file are static and reach the caller through that table alone; what a launch does on
+ * the host (flags to template arguments, the persistent-wave grid, render_kernel_simple's) is vpt_hetero_launch.h's.
  */
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
 #include "vpt_wave.h"
-#include "vpt_internal.h"
+#include "vpt_hetero_launch.h"
 
 #ifndef VPT_HETERO_LDS
 #define VPT_HETERO_LDS 1
@@ -249,100 +250,61 @@ __global__ __launch_bounds__(256) void grid_emission_probe_kernel(const vpt_grid
 
 }  // namespace
 
-/* estimator 11's launches stand at the end of the unit (below): the kernels are instantiated in the order of their
- * first use, and estimator 10's keep the places -- and with them the label numbers -- they had */
+/* the unit's launches, the slots of vpt_hetero_unit (vpt_hetero.h says what each does).  Estimator 11's stand at the end
+ * of the unit (below): the kernels are instantiated in the order of their first use, and estimator 10's keep the places
+ * -- and with them the label numbers -- they had */
 static void ratio_trace_launch(const vpt_ray* rays, const uint64_t* states, int n, const Medium& m, const DevScene* S,
                                const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states);
 static int ratio_simple_launch(const KParams& K, const DevScene* S, bool lm, void* stream);
 static int ratio_launch(int device, const KParams& K, const DevScene* S, bool lm, void* stream);
 
-void VPT_HX(vpt_int_hetero_trace_launch)(int est, const vpt_ray* rays, const uint64_t* states, int n, const Medium& m,
-                                 const DevScene* S, const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states,
-                                 unsigned long long* stats)
+static void trace_launch(int est, const vpt_ray* rays, const uint64_t* states, int n, const Medium& m, const DevScene* S,
+                         const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states, unsigned long long* stats)
 {
     if (est == VPT_HETERO_RATIO) return ratio_trace_launch(rays, states, n, m, S, grid, lm, out, out_states);
-    const dim3 g((unsigned)((n + 255) / 256)), b(256);
+    const dim3 g = vpt_ray_grid(n), b(256);
     if (lm) trace_batch_hetero_kernel<true, TLU, EMU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states, stats);
     else trace_batch_hetero_kernel<false, TLU, EMU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states, stats);
 }
 
 #if VPT_HETERO_EM
-void VPT_HX(vpt_int_grid_emission_probe_launch)(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
-                                                const double* tmax, const uint64_t* states, int n, double* t_coll, double* esum,
-                                                uint64_t* states_out, uint32_t* steps)
+static void grid_emission_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
+                                       const double* tmax, const uint64_t* states, int n, double* t_coll, double* esum,
+                                       uint64_t* states_out, uint32_t* steps)
 {
-    const dim3 g((unsigned)((n + 255) / 256)), b(256);
+    const dim3 g = vpt_ray_grid(n), b(256);
     if (lm) grid_emission_probe_kernel<true, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, t_coll, esum, states_out, steps);
     else grid_emission_probe_kernel<false, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, t_coll, esum, states_out, steps);
 }
 #else
-void VPT_HX(vpt_int_grid_probe_launch)(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays, const double* tmax,
-                               const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out,
-                               uint32_t* steps)
+static void grid_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays, const double* tmax,
+                              const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out,
+                              uint32_t* steps)
 {
-    const dim3 g((unsigned)((n + 255) / 256)), b(256);
+    const dim3 g = vpt_ray_grid(n), b(256);
     if (lm) grid_probe_kernel<true, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, steps);
     else grid_probe_kernel<false, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, steps);
 }
 #endif
-/* run-time flags as compile-time constants: f(std::bool_constant<flag>{}...) */
-template <class F>
-static int with_flags(F f)
+
+template <int EST>
+static int simple_launch_of(const KParams& K, const DevScene* S, bool lm, void* stream)
 {
-    return f();
-}
-template <class F, class... Bools>
-static int with_flags(F f, bool flag, Bools... rest)
-{
-    if (flag) return with_flags([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
-    return with_flags([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+    return with_flags([&](auto lmc) { return vpt_simple_launch<EST, decltype(lmc)::value, TLU, EMU>(K, S, stream); }, lm);
 }
 
-/* render_kernel_simple<EST> (vpt_render_simple.h): counting mode (K.counters != NULL) and VPT_SIMPLE_KERNEL=1 */
-template <int EST>
 static int simple_launch(const KParams& K, const DevScene* S, bool lm, void* stream)
 {
-    return with_flags([&](auto lmc, auto count, auto f32) {
-        constexpr int FB = decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64;
-        dim3 grid((unsigned)((K.w + 15) / 16), (unsigned)((K.shard_rows + 15) / 16));
-        render_kernel_simple<EST, decltype(count)::value, FB, decltype(lmc)::value, TLU, EMU><<<grid, dim3(256), 0, (hipStream_t)stream>>>(K, S);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "render_kernel_simple<%d> launch: %s", EST, hipGetErrorString(e));
-        return (int)VPT_OK;
-    }, lm, K.counters != nullptr, K.fb == VPT_FB_F32);
-}
-
-int VPT_HX(vpt_int_hetero_simple_launch)(const KParams& K, const DevScene* S, bool lm, void* stream)
-{
     if (K.est == VPT_HETERO_RATIO) return ratio_simple_launch(K, S, lm, stream);
-    return simple_launch<VPT_HETERO_FREE>(K, S, lm, stream);
+    return simple_launch_of<VPT_HETERO_FREE>(K, S, lm, stream);
 }
 
-/* a persistent-wave kernel on as many workgroups as the device holds, at most one per four tiles */
-static int persistent_launch(void (*kern)(KParams, const DevScene*), int device, const KParams& K, const DevScene* S,
-                             void* stream)
-{
-    int per_cu = 0, cus = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_kernel: %s", hipGetErrorString(e));
-    int blocks = (per_cu < 1 ? 1 : per_cu) * cus;
-    const int tiles = K.tiles_x * K.tiles_y;
-    const int need = (tiles + 3) / 4;  /* 4 waves per block, one tile per wave to start */
-    if (blocks > need) blocks = need;
-    if (blocks < 1) blocks = 1;
-    kern<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(K, S);
-    e = hipGetLastError();
-    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_kernel launch: %s", hipGetErrorString(e));
-    return (int)VPT_OK;
-}
-
-int VPT_HX(vpt_int_hetero_launch)(int device, const KParams& K, const DevScene* S, bool lm, void* stream)
+static int launch(int device, const KParams& K, const DevScene* S, bool lm, void* stream)
 {
     if (K.est == VPT_HETERO_RATIO) return ratio_launch(device, K, S, lm, stream);
     return with_flags([&](auto lmc, auto f32) {
-        return persistent_launch(hetero_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU, EMU>,
-                                 device, K, S, stream);
+        return vpt_persistent_launch(hetero_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU, EMU>,
+                                     "hetero_kernel", device, K, S, stream);
     }, lm, K.fb == VPT_FB_F32);
 }
 
@@ -350,17 +312,17 @@ int VPT_HX(vpt_int_hetero_launch)(int device, const KParams& K, const DevScene* 
 static void ratio_trace_launch(const vpt_ray* rays, const uint64_t* states, int n, const Medium& m, const DevScene* S,
                                const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states)
 {
-    const dim3 g((unsigned)((n + 255) / 256)), b(256);
+    const dim3 g = vpt_ray_grid(n), b(256);
     if (lm) trace_batch_hetero_ratio_kernel<true, TLU, EMU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states);
     else trace_batch_hetero_ratio_kernel<false, TLU, EMU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states);
 }
 
 #if !VPT_HETERO_EM
-void VPT_HX(vpt_int_grid_ratio_probe_launch)(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
-                                     const double* tmax, const uint64_t* states, int n, double* that, uint64_t* states_out,
-                                     uint32_t* steps)
+static void grid_ratio_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
+                                    const double* tmax, const uint64_t* states, int n, double* that, uint64_t* states_out,
+                                    uint32_t* steps)
 {
-    const dim3 g((unsigned)((n + 255) / 256)), b(256);
+    const dim3 g = vpt_ray_grid(n), b(256);
     if (lm) grid_ratio_probe_kernel<true, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, that, states_out, steps);
     else grid_ratio_probe_kernel<false, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, that, states_out, steps);
 }
@@ -368,13 +330,22 @@ void VPT_HX(vpt_int_grid_ratio_probe_launch)(const vpt_grid_view* grid, bool lm,
 
 static int ratio_simple_launch(const KParams& K, const DevScene* S, bool lm, void* stream)
 {
-    return simple_launch<VPT_HETERO_RATIO>(K, S, lm, stream);
+    return simple_launch_of<VPT_HETERO_RATIO>(K, S, lm, stream);
 }
 
 static int ratio_launch(int device, const KParams& K, const DevScene* S, bool lm, void* stream)
 {
     return with_flags([&](auto lmc, auto f32) {
-        return persistent_launch(hetero_ratio_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU, EMU>,
-                                 device, K, S, stream);
+        return vpt_persistent_launch(hetero_ratio_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU, EMU>,
+                                     "hetero_kernel", device, K, S, stream);
     }, lm, K.fb == VPT_FB_F32);
 }
+
+/* what the unit exports: its launches by slot; the probes a unit does not hold are NULL.  Host pass only: a const object
+ * with a constant initialiser is emitted for the device as well, and these are host functions */
+#if defined(__HIP_DEVICE_COMPILE__)
+#elif VPT_HETERO_EM
+const vpt_hetero_unit VPT_HX(vpt_int_hetero_unit) = {launch, simple_launch, trace_launch, nullptr, nullptr, grid_emission_probe_launch};
+#else
+const vpt_hetero_unit VPT_HX(vpt_int_hetero_unit) = {launch, simple_launch, trace_launch, grid_probe_launch, grid_ratio_probe_launch, nullptr};
+#endif

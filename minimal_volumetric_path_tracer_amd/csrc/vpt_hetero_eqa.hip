@@ -8,15 +8,14 @@
  * there is no majorant grid to stage, because nothing tracks.
  *
  * Trilinear interpolation: the unit instantiates one value of TL, VPT_HETERO_TL.  Compiled as it stands (0) it holds the
- * nearest-lookup kernels and exports the vpt_int_* launches; vpt_hetero_eqa_tl.hip includes this file with
- * VPT_HETERO_TL = 1 and exports the same launches with the suffix _tl.
+ * nearest-lookup kernels and exports their launches as the table vpt_int_hetero_eqa_unit (vpt_hetero_eqa.h);
+ * vpt_hetero_eqa_tl.hip includes this file with VPT_HETERO_TL = 1 and exports vpt_int_hetero_eqa_unit_tl.  The launches
+ * are static; their host side is vpt_hetero_launch.h's, shared with vpt_hetero.hip.
  */
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
 #include "vpt_wave.h"
-#include "vpt_internal.h"
+#include "vpt_hetero_launch.h"
 
 #ifndef VPT_HETERO_LDS
 #define VPT_HETERO_LDS 1
@@ -107,68 +106,38 @@ __global__ __launch_bounds__(256) void grid_eqa_probe_kernel(const vpt_grid_view
     states_out[i] = X;
 }
 
-/* run-time flags as compile-time constants (vpt_hetero.hip's) */
-template <class F>
-static int with_flags(F f)
-{
-    return f();
-}
-template <class F, class... Bools>
-static int with_flags(F f, bool flag, Bools... rest)
-{
-    if (flag) return with_flags([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
-    return with_flags([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
-}
-
 }  // namespace
 
-void VPT_HX(vpt_int_hetero_eqa_trace_launch)(const vpt_ray* rays, const uint64_t* states, int n, const Medium& m,
-                                             const DevScene* S, const vpt_grid_view* grid, double* out, uint64_t* out_states)
+/* the unit's launches, the slots of vpt_hetero_eqa_unit (vpt_hetero_eqa.h) */
+static void trace_launch(const vpt_ray* rays, const uint64_t* states, int n, const Medium& m, const DevScene* S,
+                         const vpt_grid_view* grid, double* out, uint64_t* out_states)
 {
-    trace_batch_hetero_eqa_kernel<TLU><<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(rays, states, n, m, S, grid, out,
-                                                                                          out_states);
+    trace_batch_hetero_eqa_kernel<TLU><<<vpt_ray_grid(n), dim3(256)>>>(rays, states, n, m, S, grid, out, out_states);
 }
 
-void VPT_HX(vpt_int_grid_eqa_probe_launch)(const vpt_grid_view* grid, double sigma_t, const vpt_ray* rays, const double* tmax,
-                                           const double* light, const uint64_t* states, int n, double* psurf, double* dist,
-                                           double* pdf, double* T, double* rho_t, uint64_t* states_out)
+static void grid_eqa_probe_launch(const vpt_grid_view* grid, double sigma_t, const vpt_ray* rays, const double* tmax,
+                                  const double* light, const uint64_t* states, int n, double* psurf, double* dist,
+                                  double* pdf, double* T, double* rho_t, uint64_t* states_out)
 {
-    grid_eqa_probe_kernel<TLU><<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(grid, sigma_t, rays, tmax, light, states, n,
-                                                                                  psurf, dist, pdf, T, rho_t, states_out);
+    grid_eqa_probe_kernel<TLU><<<vpt_ray_grid(n), dim3(256)>>>(grid, sigma_t, rays, tmax, light, states, n, psurf, dist, pdf,
+                                                                T, rho_t, states_out);
 }
 
-/* render_kernel_simple<12> (vpt_render_simple.h): counting mode (K.counters != NULL) and VPT_SIMPLE_KERNEL=1 */
-int VPT_HX(vpt_int_hetero_eqa_simple_launch)(const KParams& K, const DevScene* S, void* stream)
+static int simple_launch(const KParams& K, const DevScene* S, void* stream)
 {
-    return with_flags([&](auto count, auto f32) {
-        constexpr int FB = decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64;
-        dim3 grid((unsigned)((K.w + 15) / 16), (unsigned)((K.shard_rows + 15) / 16));
-        render_kernel_simple<VPT_HETERO_EQUIANGULAR, decltype(count)::value, FB, false, TLU><<<grid, dim3(256), 0, (hipStream_t)stream>>>(K, S);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return vpt_fail(VPT_E_HIP, "render_kernel_simple<%d> launch: %s", (int)VPT_HETERO_EQUIANGULAR, hipGetErrorString(e));
-        return (int)VPT_OK;
-    }, K.counters != nullptr, K.fb == VPT_FB_F32);
+    return vpt_simple_launch<VPT_HETERO_EQUIANGULAR, false, TLU, false>(K, S, stream);
 }
 
-/* the persistent-wave kernel on as many workgroups as the device holds, at most one per four tiles (vpt_hetero.hip's
- * persistent_launch) */
-int VPT_HX(vpt_int_hetero_eqa_launch)(int device, const KParams& K, const DevScene* S, void* stream)
+static int launch(int device, const KParams& K, const DevScene* S, void* stream)
 {
     return with_flags([&](auto f32) {
-        void (*kern)(KParams, const DevScene*) = hetero_eqa_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, TLU>;
-        int per_cu = 0, cus = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-        if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_eqa_kernel: %s", hipGetErrorString(e));
-        int blocks = (per_cu < 1 ? 1 : per_cu) * cus;
-        const int tiles = K.tiles_x * K.tiles_y;
-        const int need = (tiles + 3) / 4;  /* 4 waves per block, one tile per wave to start */
-        if (blocks > need) blocks = need;
-        if (blocks < 1) blocks = 1;
-        kern<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(K, S);
-        e = hipGetLastError();
-        if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_eqa_kernel launch: %s", hipGetErrorString(e));
-        return (int)VPT_OK;
+        return vpt_persistent_launch(hetero_eqa_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, TLU>,
+                                     "hetero_eqa_kernel", device, K, S, stream);
     }, K.fb == VPT_FB_F32);
 }
+
+/* what the unit exports.  Host pass only: a const object with a constant initialiser is emitted for the device as well,
+ * and these are host functions */
+#if !defined(__HIP_DEVICE_COMPILE__)
+const vpt_hetero_eqa_unit VPT_HX(vpt_int_hetero_eqa_unit) = {launch, simple_launch, trace_launch, grid_eqa_probe_launch};
+#endif

@@ -19,7 +19,7 @@
 #include "vpt_device.h"
 #include "vpt_pool.h"
 #include "vpt_wave.h"
-#include "vpt_internal.h"
+#include "vpt_hetero_launch.h"
 
 /* the EST = 1 pool kernel comes from vpt_pool_mis.hip, compiled with flags of its own (VPT_MIS_TU;
  * -DVPT_MIS_TU=0 instantiates it here, as the syntax checks of tests/test_knobs.py do) */
@@ -48,6 +48,65 @@ namespace {
         if (e_ != hipSuccess)                                                                \
             return vpt_fail(VPT_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));       \
     } while (0)
+
+/* The device arrays of one per-ray call (the per-sample calls and the probes at the end of this file).  Every step is
+ * a synchronous HIP call on the default stream; the first error is kept and every later step does nothing, so a call
+ * reads as a straight sequence -- alloc, up, launch, down -- and asks once, with status().  The destructor frees what
+ * was allocated. */
+class Staging {
+public:
+    Staging() = default;
+    Staging(const Staging&) = delete;
+    Staging& operator=(const Staging&) = delete;
+    ~Staging()
+    {
+        for (void* d : owned_) (void)hipFree(d);
+    }
+    /* `count` elements of T on the device, an allocation of their own; NULL after an error */
+    template <class T>
+    T* alloc(size_t count)
+    {
+        void* d = nullptr;
+        if (err_ == hipSuccess) err_ = hipMalloc(&d, sizeof(T) * count);
+        if (err_ == hipSuccess) owned_.push_back(d);
+        return (T*)d;
+    }
+    /* alloc where the caller passed the optional array `host`, else NULL */
+    template <class T>
+    T* alloc_if(const T* host, size_t count)
+    {
+        return host ? alloc<T>(count) : nullptr;
+    }
+    template <class T>
+    void up(T* dev, const T* host, size_t count)
+    {
+        if (err_ == hipSuccess) err_ = hipMemcpy(dev, host, sizeof(T) * count, hipMemcpyHostToDevice);
+    }
+    /* a result to the host; an optional output the caller left NULL is skipped */
+    template <class T>
+    void down(T* host, const T* dev, size_t count)
+    {
+        if (err_ == hipSuccess && host) err_ = hipMemcpy(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost);
+    }
+    /* f launches the call's kernel */
+    template <class F>
+    void launch(F f)
+    {
+        if (err_ != hipSuccess) return;
+        f();
+        err_ = hipGetLastError();
+    }
+    /* VPT_OK, or VPT_E_HIP with "<who>: <hip error string>" */
+    int status(const char* who) const
+    {
+        if (err_ != hipSuccess) return vpt_fail(VPT_E_HIP, "%s: %s", who, hipGetErrorString(err_));
+        return VPT_OK;
+    }
+
+private:
+    std::vector<void*> owned_;
+    hipError_t err_ = hipSuccess;
+};
 
 /* the persistent-wave loop (vpt_wave.h) on the estimators 0-9: the round-1 design, which the pool kernel
  * replaced; an A/B path of -DVPT_DEBUG_ENV=1 builds (launch_wave) */
@@ -410,11 +469,7 @@ static int check_guard(vpt_context* ctx, const char* who)
 template <typename Kern>
 static int persistent_grid(vpt_context* ctx, Kern kern, int* blocks, int threads = 256)
 {
-    int per_cu = 0, cus = 0;
-    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, 0));
-    HIP_OK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    if (per_cu < 1) per_cu = 1;
-    *blocks = per_cu * cus;
+    HIP_OK(vpt_resident_blocks(kern, threads, ctx->device, blocks));
     return VPT_OK;
 }
 
@@ -466,39 +521,34 @@ static bool hetero_simple_kernel()
     return v && *v && atoi(v) != 0;
 }
 
-/* estimators 10 and 11 (vpt_hetero.hip, by K.est): hetero_kernel / hetero_ratio_kernel on the stream's queue word;
- * counting mode and VPT_SIMPLE_KERNEL=1: render_kernel_simple<10 or 11> */
+/* The code object that holds the kernels of estimators 10 and 11 for a lookup (tl: trilinear) and a medium without or
+ * with emission (vpt_hetero.h), and estimator 12's for a lookup (vpt_hetero_eqa.h).  The one place where the two settings
+ * turn into a unit: every launch below goes through the table returned here.  The two grid probes exist in the units
+ * without emission only, so their callers pass em = false whatever the context holds. */
+static const vpt_hetero_unit& hetero_unit(bool tl, bool em)
+{
+    if (em) return tl ? vpt_int_hetero_unit_em_tl : vpt_int_hetero_unit_em;
+    return tl ? vpt_int_hetero_unit_tl : vpt_int_hetero_unit;
+}
+static const vpt_hetero_eqa_unit& hetero_eqa_unit(bool tl) { return tl ? vpt_int_hetero_eqa_unit_tl : vpt_int_hetero_eqa_unit; }
+
+/* estimators 10, 11 (by K.est: hetero_kernel / hetero_ratio_kernel) and 12 (hetero_eqa_kernel; the majorant block plays no
+ * part) on the stream's queue word; counting mode and VPT_SIMPLE_KERNEL=1: render_kernel_simple<K.est> */
 static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
 {
-    const bool lm = ctx->h_grid.block > 0, tl = ctx->h_grid.interp != 0, em = ctx->h_grid.emit != nullptr;
+    const vpt_grid_view& g = ctx->h_grid;
+    const bool eqa = K.est == VPT_HETERO_EQUIANGULAR, lm = g.block > 0;
+    const vpt_hetero_unit& u = hetero_unit(g.interp != 0, g.emit != nullptr);
+    const vpt_hetero_eqa_unit& q = hetero_eqa_unit(g.interp != 0);
     if (K.counters || hetero_simple_kernel())
-        return (em ? (tl ? vpt_int_hetero_simple_launch_em_tl : vpt_int_hetero_simple_launch_em)
-                   : (tl ? vpt_int_hetero_simple_launch_tl : vpt_int_hetero_simple_launch))(K, ctx->d_scene, lm, stream);
+        return eqa ? q.simple_launch(K, ctx->d_scene, stream) : u.simple_launch(K, ctx->d_scene, lm, stream);
     std::lock_guard<std::mutex> lock(ctx->mu);
     StreamSlot* sl = nullptr;
     int rc = stream_slot(ctx, stream, 0, &sl);
     if (rc) return rc;
     K.queue = sl->d_queue;
     HIP_OK(hipMemsetAsync(K.queue, 0, sizeof(unsigned), stream));
-    rc = (em ? (tl ? vpt_int_hetero_launch_em_tl : vpt_int_hetero_launch_em)
-             : (tl ? vpt_int_hetero_launch_tl : vpt_int_hetero_launch))(ctx->device, K, ctx->d_scene, lm, stream);
-    if (rc) return rc;
-    return slot_done(sl, stream);
-}
-
-/* estimator 12 (vpt_hetero_eqa.hip): hetero_eqa_kernel in the same way; the majorant block plays no part */
-static int launch_hetero_eqa(vpt_context* ctx, KParams K, hipStream_t stream)
-{
-    const bool tl = ctx->h_grid.interp != 0;
-    if (K.counters || hetero_simple_kernel())
-        return (tl ? vpt_int_hetero_eqa_simple_launch_tl : vpt_int_hetero_eqa_simple_launch)(K, ctx->d_scene, stream);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    StreamSlot* sl = nullptr;
-    int rc = stream_slot(ctx, stream, 0, &sl);
-    if (rc) return rc;
-    K.queue = sl->d_queue;
-    HIP_OK(hipMemsetAsync(K.queue, 0, sizeof(unsigned), stream));
-    rc = (tl ? vpt_int_hetero_eqa_launch_tl : vpt_int_hetero_eqa_launch)(ctx->device, K, ctx->d_scene, stream);
+    rc = eqa ? q.launch(ctx->device, K, ctx->d_scene, stream) : u.launch(ctx->device, K, ctx->d_scene, lm, stream);
     if (rc) return rc;
     return slot_done(sl, stream);
 }
@@ -506,10 +556,8 @@ static int launch_hetero_eqa(vpt_context* ctx, KParams K, hipStream_t stream)
 template <int EST, bool COUNT, int FB>
 static int launch_one(vpt_context* ctx, KParams K, hipStream_t stream)
 {
-    if constexpr (EST == VPT_HETERO_FREE || EST == VPT_HETERO_RATIO) {  /* their kernels live in vpt_hetero.hip */
+    if constexpr (EST >= VPT_HETERO_FREE) {  /* the kernels of 10 and 11 live in vpt_hetero.hip, 12's in vpt_hetero_eqa.hip */
         return launch_hetero(ctx, K, stream);
-    } else if constexpr (EST == VPT_HETERO_EQUIANGULAR) {  /* and estimator 12's in vpt_hetero_eqa.hip */
-        return launch_hetero_eqa(ctx, K, stream);
     } else {
         const DevScene* S = ctx->d_scene;
         /* counting (vpt_count_work) needs only the totals: the one-lane-per-pixel kernel, which is
@@ -674,10 +722,7 @@ static int launch_wave(vpt_context* ctx, KParams K, hipStream_t stream)
     int blocks = 0;
     int rc = persistent_grid(ctx, render_kernel<EST, COUNT, FB>, &blocks);
     if (rc) return rc;
-    const int tiles = K.tiles_x * K.tiles_y;
-    const int need = (tiles + 3) / 4;  /* 4 waves per block, one tile per wave to start */
-    if (blocks > need) blocks = need;
-    if (blocks < 1) blocks = 1;
+    blocks = vpt_wave_blocks(blocks, K);
     std::lock_guard<std::mutex> lock(ctx->mu);
     StreamSlot* sl = nullptr;
     rc = stream_slot(ctx, stream, 0, &sl);
@@ -1048,50 +1093,33 @@ static int grid_probe(vpt_context* ctx, bool lm, double sigma_t, const vpt_ray* 
     if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "%s: no density grid set (vpt_set_density_grid)", who);
     if (n == 0) return VPT_OK;
     HIP_OK(hipSetDevice(ctx->device));
-    /* the existing probe keeps its global-majorant behaviour: a copy of the view without the majorant grid */
-    vpt_grid_view* dview = ctx->d_grid;
-    vpt_grid_view* dplain = nullptr;
-    uint32_t* dst = nullptr;
-    vpt_ray* dr = nullptr;
-    uint64_t *ds = nullptr, *dso = nullptr;
-    double *dtm = nullptr, *dtau = nullptr, *dtc = nullptr;
+    Staging st;
     const size_t nn = (size_t)n;
-    hipError_t e = hipMalloc((void**)&dr, sizeof(vpt_ray) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&ds, sizeof(uint64_t) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&dso, sizeof(uint64_t) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&dtm, sizeof(double) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&dtau, sizeof(double) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&dtc, sizeof(double) * nn);
-    if (e == hipSuccess && steps) e = hipMalloc((void**)&dst, sizeof(uint32_t) * nn);
-    if (e == hipSuccess && !lm && ctx->h_grid.block > 0) {
+    vpt_ray* dr = st.alloc<vpt_ray>(nn);
+    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn);
+    double *dtm = st.alloc<double>(nn), *dtau = st.alloc<double>(nn), *dtc = st.alloc<double>(nn);
+    uint32_t* dst = st.alloc_if(steps, nn);
+    /* the existing probe keeps its global-majorant behaviour: a copy of the view without the majorant grid */
+    const vpt_grid_view* dview = ctx->d_grid;
+    if (!lm && ctx->h_grid.block > 0) {
         vpt_grid_view G = ctx->h_grid;
         vpt_grid_view_set_majorant(&G, 0, nullptr);
-        e = hipMalloc((void**)&dplain, sizeof G);
-        if (e == hipSuccess) e = hipMemcpy(dplain, &G, sizeof G, hipMemcpyHostToDevice);
+        vpt_grid_view* dplain = st.alloc<vpt_grid_view>(1);
+        st.up(dplain, &G, 1);
         dview = dplain;
     }
-    if (e == hipSuccess) e = hipMemcpy(dr, rays, sizeof(vpt_ray) * nn, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ds, states, sizeof(uint64_t) * nn, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dtm, tmax, sizeof(double) * nn, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        (ctx->h_grid.interp ? vpt_int_grid_probe_launch_tl : vpt_int_grid_probe_launch)(dview, lm && ctx->h_grid.block > 0, sigma_t, dr,
-                                                                                        dtm, ds, n, dtau, dtc, dso, dst);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(tau, dtau, sizeof(double) * nn, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(t_coll, dtc, sizeof(double) * nn, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(states_out, dso, sizeof(uint64_t) * nn, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && steps) e = hipMemcpy(steps, dst, sizeof(uint32_t) * nn, hipMemcpyDeviceToHost);
-    if (dplain) (void)hipFree(dplain);
-    if (dst) (void)hipFree(dst);
-    (void)hipFree(dr);
-    (void)hipFree(ds);
-    (void)hipFree(dso);
-    (void)hipFree(dtm);
-    (void)hipFree(dtau);
-    (void)hipFree(dtc);
-    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "%s: %s", who, hipGetErrorString(e));
-    return VPT_OK;
+    st.up(dr, rays, nn);
+    st.up(ds, states, nn);
+    st.up(dtm, tmax, nn);
+    st.launch([&] {
+        hetero_unit(ctx->h_grid.interp != 0, false).grid_probe_launch(dview, lm && ctx->h_grid.block > 0, sigma_t, dr, dtm, ds, n,
+                                                                      dtau, dtc, dso, dst);
+    });
+    st.down(tau, dtau, nn);
+    st.down(t_coll, dtc, nn);
+    st.down(states_out, dso, nn);
+    st.down(steps, dst, nn);
+    return st.status(who);
 }
 
 int vpt_grid_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
@@ -1115,36 +1143,23 @@ int vpt_grid_ratio_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, 
     if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "vpt_grid_ratio_probe: no density grid set (vpt_set_density_grid)");
     if (n == 0) return VPT_OK;
     HIP_OK(hipSetDevice(ctx->device));
-    uint32_t* dst = nullptr;
-    vpt_ray* dr = nullptr;
-    uint64_t *ds = nullptr, *dso = nullptr;
-    double *dtm = nullptr, *dth = nullptr;
+    Staging st;
     const size_t nn = (size_t)n;
-    hipError_t e = hipMalloc((void**)&dr, sizeof(vpt_ray) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&ds, sizeof(uint64_t) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&dso, sizeof(uint64_t) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&dtm, sizeof(double) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&dth, sizeof(double) * nn);
-    if (e == hipSuccess && steps) e = hipMalloc((void**)&dst, sizeof(uint32_t) * nn);
-    if (e == hipSuccess) e = hipMemcpy(dr, rays, sizeof(vpt_ray) * nn, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ds, states, sizeof(uint64_t) * nn, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dtm, tmax, sizeof(double) * nn, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        (ctx->h_grid.interp ? vpt_int_grid_ratio_probe_launch_tl : vpt_int_grid_ratio_probe_launch)(
-            ctx->d_grid, ctx->h_grid.block > 0, sigma_t, dr, dtm, ds, n, dth, dso, dst);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(that, dth, sizeof(double) * nn, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(states_out, dso, sizeof(uint64_t) * nn, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && steps) e = hipMemcpy(steps, dst, sizeof(uint32_t) * nn, hipMemcpyDeviceToHost);
-    if (dst) (void)hipFree(dst);
-    (void)hipFree(dr);
-    (void)hipFree(ds);
-    (void)hipFree(dso);
-    (void)hipFree(dtm);
-    (void)hipFree(dth);
-    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "vpt_grid_ratio_probe: %s", hipGetErrorString(e));
-    return VPT_OK;
+    vpt_ray* dr = st.alloc<vpt_ray>(nn);
+    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn);
+    double *dtm = st.alloc<double>(nn), *dth = st.alloc<double>(nn);
+    uint32_t* dst = st.alloc_if(steps, nn);
+    st.up(dr, rays, nn);
+    st.up(ds, states, nn);
+    st.up(dtm, tmax, nn);
+    st.launch([&] {
+        hetero_unit(ctx->h_grid.interp != 0, false).grid_ratio_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, sigma_t, dr, dtm, ds,
+                                                                            n, dth, dso, dst);
+    });
+    st.down(that, dth, nn);
+    st.down(states_out, dso, nn);
+    st.down(steps, dst, nn);
+    return st.status("vpt_grid_ratio_probe");
 }
 
 int vpt_grid_eqa_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const double* light,
@@ -1157,37 +1172,24 @@ int vpt_grid_eqa_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, co
     if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "vpt_grid_eqa_probe: no density grid set (vpt_set_density_grid)");
     if (n == 0) return VPT_OK;
     HIP_OK(hipSetDevice(ctx->device));
-    vpt_ray* dr = nullptr;
-    uint64_t *ds = nullptr, *dso = nullptr;
-    double *dtm = nullptr, *dl = nullptr, *dres = nullptr;  /* dres: the five result arrays, one behind the other */
+    Staging st;
     const size_t nn = (size_t)n;
-    hipError_t e = hipMalloc((void**)&dr, sizeof(vpt_ray) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&ds, sizeof(uint64_t) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&dso, sizeof(uint64_t) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&dtm, sizeof(double) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&dl, sizeof(double) * 3 * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&dres, sizeof(double) * 5 * nn);
-    if (e == hipSuccess) e = hipMemcpy(dr, rays, sizeof(vpt_ray) * nn, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ds, states, sizeof(uint64_t) * nn, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dtm, tmax, sizeof(double) * nn, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dl, light, sizeof(double) * 3 * nn, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        (ctx->h_grid.interp ? vpt_int_grid_eqa_probe_launch_tl : vpt_int_grid_eqa_probe_launch)(
-            ctx->d_grid, sigma_t, dr, dtm, dl, ds, n, dres, dres + nn, dres + 2 * nn, dres + 3 * nn, dres + 4 * nn, dso);
-        e = hipGetLastError();
-    }
+    vpt_ray* dr = st.alloc<vpt_ray>(nn);
+    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn);
+    double *dtm = st.alloc<double>(nn), *dl = st.alloc<double>(3 * nn);
+    double* dres = st.alloc<double>(5 * nn);  /* the five result arrays, one behind the other */
+    st.up(dr, rays, nn);
+    st.up(ds, states, nn);
+    st.up(dtm, tmax, nn);
+    st.up(dl, light, 3 * nn);
+    st.launch([&] {
+        hetero_eqa_unit(ctx->h_grid.interp != 0).grid_eqa_probe_launch(ctx->d_grid, sigma_t, dr, dtm, dl, ds, n, dres, dres + nn,
+                                                                       dres + 2 * nn, dres + 3 * nn, dres + 4 * nn, dso);
+    });
     double* const res[5] = {psurf, dist, pdf, T, rho_t};
-    for (int k = 0; k < 5; ++k)
-        if (e == hipSuccess) e = hipMemcpy(res[k], dres + (size_t)k * nn, sizeof(double) * nn, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(states_out, dso, sizeof(uint64_t) * nn, hipMemcpyDeviceToHost);
-    if (dr) (void)hipFree(dr);
-    if (ds) (void)hipFree(ds);
-    if (dso) (void)hipFree(dso);
-    if (dtm) (void)hipFree(dtm);
-    if (dl) (void)hipFree(dl);
-    if (dres) (void)hipFree(dres);
-    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "vpt_grid_eqa_probe: %s", hipGetErrorString(e));
-    return VPT_OK;
+    for (int k = 0; k < 5; ++k) st.down(res[k], dres + (size_t)k * nn, nn);
+    st.down(states_out, dso, nn);
+    return st.status("vpt_grid_eqa_probe");
 }
 
 int vpt_grid_emission_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
@@ -1200,39 +1202,24 @@ int vpt_grid_emission_probe(vpt_context* ctx, double sigma_t, const vpt_ray* ray
         return vpt_fail(VPT_E_INVALID, "vpt_grid_emission_probe: no emission grid set (vpt_set_emission_grid)");
     if (n == 0) return VPT_OK;
     HIP_OK(hipSetDevice(ctx->device));
-    uint32_t* dst = nullptr;
-    vpt_ray* dr = nullptr;
-    uint64_t *ds = nullptr, *dso = nullptr;
-    double *dtm = nullptr, *dtc = nullptr, *des = nullptr;
+    Staging st;
     const size_t nn = (size_t)n;
-    hipError_t e = hipMalloc((void**)&dr, sizeof(vpt_ray) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&ds, sizeof(uint64_t) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&dso, sizeof(uint64_t) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&dtm, sizeof(double) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&dtc, sizeof(double) * nn);
-    if (e == hipSuccess) e = hipMalloc((void**)&des, sizeof(double) * nn);
-    if (e == hipSuccess && steps) e = hipMalloc((void**)&dst, sizeof(uint32_t) * nn);
-    if (e == hipSuccess) e = hipMemcpy(dr, rays, sizeof(vpt_ray) * nn, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ds, states, sizeof(uint64_t) * nn, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dtm, tmax, sizeof(double) * nn, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        (ctx->h_grid.interp ? vpt_int_grid_emission_probe_launch_em_tl : vpt_int_grid_emission_probe_launch_em)(
-            ctx->d_grid, ctx->h_grid.block > 0, sigma_t, dr, dtm, ds, n, dtc, des, dso, dst);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(t_coll, dtc, sizeof(double) * nn, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(esum, des, sizeof(double) * nn, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(states_out, dso, sizeof(uint64_t) * nn, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && steps) e = hipMemcpy(steps, dst, sizeof(uint32_t) * nn, hipMemcpyDeviceToHost);
-    if (dst) (void)hipFree(dst);
-    if (dr) (void)hipFree(dr);
-    if (ds) (void)hipFree(ds);
-    if (dso) (void)hipFree(dso);
-    if (dtm) (void)hipFree(dtm);
-    if (dtc) (void)hipFree(dtc);
-    if (des) (void)hipFree(des);
-    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "vpt_grid_emission_probe: %s", hipGetErrorString(e));
-    return VPT_OK;
+    vpt_ray* dr = st.alloc<vpt_ray>(nn);
+    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn);
+    double *dtm = st.alloc<double>(nn), *dtc = st.alloc<double>(nn), *des = st.alloc<double>(nn);
+    uint32_t* dst = st.alloc_if(steps, nn);
+    st.up(dr, rays, nn);
+    st.up(ds, states, nn);
+    st.up(dtm, tmax, nn);
+    st.launch([&] {
+        hetero_unit(ctx->h_grid.interp != 0, true).grid_emission_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, sigma_t, dr, dtm,
+                                                                              ds, n, dtc, des, dso, dst);
+    });
+    st.down(t_coll, dtc, nn);
+    st.down(esum, des, nn);
+    st.down(states_out, dso, nn);
+    st.down(steps, dst, nn);
+    return st.status("vpt_grid_emission_probe");
 }
 
 int vpt_render_device(vpt_context* ctx, const vpt_params* p, void* d_out, void* stream)
@@ -1324,18 +1311,17 @@ static int trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* ray
     if (rc) return rc;
     if (n == 0) return VPT_OK;
     HIP_OK(hipSetDevice(ctx->device));
-    vpt_ray* dr = nullptr;
-    uint64_t *ds = nullptr, *dso = nullptr;
-    double* dout = nullptr;
-    hipError_t e = hipMalloc((void**)&dr, sizeof(vpt_ray) * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc((void**)&ds, sizeof(uint64_t) * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc((void**)&dso, sizeof(uint64_t) * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc((void**)&dout, sizeof(double) * 3 * (size_t)n);
-    if (e == hipSuccess) e = hipMemcpy(dr, rays, sizeof(vpt_ray) * (size_t)n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ds, states, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
+    Staging st;
+    const size_t nn = (size_t)n;
+    vpt_ray* dr = st.alloc<vpt_ray>(nn);
+    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn);
+    double* dout = st.alloc<double>(3 * nn);
+    st.up(dr, rays, nn);
+    st.up(ds, states, nn);
+    st.launch([&] {
         Medium mm{m->sigma_a, m->sigma_s, m->hg_g, m->max_depth, m->march_step, m->march_light};
-        dim3 grid((unsigned)((n + 255) / 256)), block(256);
+        const dim3 grid = vpt_ray_grid(n), block(256);
+        const vpt_grid_view& g = ctx->h_grid;
         switch (m->estimator) {
         case 0: trace_batch_kernel<0><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         case 1: trace_batch_kernel<1><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
@@ -1347,21 +1333,19 @@ static int trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* ray
         case 7: trace_batch_kernel<7><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         case 8: trace_batch_kernel<8><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         case VPT_HETERO_FREE:
-        case VPT_HETERO_RATIO: (ctx->h_grid.emit ? (ctx->h_grid.interp ? vpt_int_hetero_trace_launch_em_tl : vpt_int_hetero_trace_launch_em)
-                                                 : (ctx->h_grid.interp ? vpt_int_hetero_trace_launch_tl : vpt_int_hetero_trace_launch))(m->estimator, dr, ds, n, mm, ctx->d_scene, ctx->d_grid, ctx->h_grid.block > 0, dout, dso, stats); break;
-        case VPT_HETERO_EQUIANGULAR: (ctx->h_grid.interp ? vpt_int_hetero_eqa_trace_launch_tl : vpt_int_hetero_eqa_trace_launch)(dr, ds, n, mm, ctx->d_scene, ctx->d_grid, dout, dso); break;
+        case VPT_HETERO_RATIO:
+            hetero_unit(g.interp != 0, g.emit != nullptr).trace_launch(m->estimator, dr, ds, n, mm, ctx->d_scene, ctx->d_grid,
+                                                                       g.block > 0, dout, dso, stats);
+            break;
+        case VPT_HETERO_EQUIANGULAR:
+            hetero_eqa_unit(g.interp != 0).trace_launch(dr, ds, n, mm, ctx->d_scene, ctx->d_grid, dout, dso);
+            break;
         default: trace_batch_kernel<9><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out_rgb, dout, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_states) e = hipMemcpy(out_states, dso, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost);
-    (void)hipFree(dr);
-    (void)hipFree(ds);
-    (void)hipFree(dso);
-    (void)hipFree(dout);
-    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "vpt_trace_batch: %s", hipGetErrorString(e));
-    return VPT_OK;
+    });
+    st.down(out_rgb, dout, 3 * nn);
+    st.down(out_states, dso, nn);
+    return st.status("vpt_trace_batch");
 }
 
 extern "C" {
@@ -1376,21 +1360,15 @@ int vpt_punctual_volumetric(vpt_context* ctx, int idsource, const double* x, int
         return vpt_fail(VPT_E_INVALID, "idsource %d is not a sphere of the scene (%d)", idsource, ctx->h_scene.n);
     if (n == 0) return VPT_OK;
     HIP_OK(hipSetDevice(ctx->device));
-    double *dx = nullptr, *dout = nullptr;
-    const size_t b = sizeof(double) * 3 * (size_t)n;
-    hipError_t e = hipMalloc((void**)&dx, b);
-    if (e == hipSuccess) e = hipMalloc((void**)&dout, b);
-    if (e == hipSuccess) e = hipMemcpy(dx, x, b, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        punctual_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(idsource, dx, n, phase, sigma_t, sigma_s,
-                                                                           ctx->d_scene, dout);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out_rgb, dout, b, hipMemcpyDeviceToHost);
-    (void)hipFree(dx);
-    (void)hipFree(dout);
-    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "vpt_punctual_volumetric: %s", hipGetErrorString(e));
-    return VPT_OK;
+    Staging st;
+    const size_t nn = (size_t)n;
+    double *dx = st.alloc<double>(3 * nn), *dout = st.alloc<double>(3 * nn);
+    st.up(dx, x, 3 * nn);
+    st.launch([&] {
+        punctual_kernel<<<vpt_ray_grid(n), dim3(256)>>>(idsource, dx, n, phase, sigma_t, sigma_s, ctx->d_scene, dout);
+    });
+    st.down(out_rgb, dout, 3 * nn);
+    return st.status("vpt_punctual_volumetric");
 }
 
 int vpt_ray_marching_batch(vpt_context* ctx, double sigma_t, double sigma_s, double steps, const vpt_ray* rays,
@@ -1405,37 +1383,24 @@ int vpt_ray_marching_batch(vpt_context* ctx, double sigma_t, double sigma_s, dou
     if (!is_finite(steps) || !(steps > 0)) return vpt_fail(VPT_E_INVALID, "steps must be finite and > 0");
     if (n == 0) return VPT_OK;
     HIP_OK(hipSetDevice(ctx->device));
-    vpt_ray* dr = nullptr;
-    uint64_t *ds = nullptr, *dso = nullptr;
-    double *dout = nullptr, *dxn = nullptr;
-    int* did = nullptr;
-    hipError_t e = hipMalloc((void**)&dr, sizeof(vpt_ray) * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc((void**)&ds, sizeof(uint64_t) * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc((void**)&dso, sizeof(uint64_t) * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc((void**)&dout, sizeof(double) * 3 * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc((void**)&dxn, sizeof(double) * 3 * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc((void**)&did, sizeof(int) * (size_t)n);
-    if (e == hipSuccess) e = hipMemcpy(dr, rays, sizeof(vpt_ray) * (size_t)n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ds, states, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dxn, x_new, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(did, idsource, sizeof(int) * (size_t)n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        ray_marching_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(dr, ds, n, sigma_t, sigma_s, steps,
-                                                                               ctx->d_scene, dout, dxn, did, dso);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out_rgb, dout, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(x_new, dxn, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(idsource, did, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_states) e = hipMemcpy(out_states, dso, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost);
-    (void)hipFree(dr);
-    (void)hipFree(ds);
-    (void)hipFree(dso);
-    (void)hipFree(dout);
-    (void)hipFree(dxn);
-    (void)hipFree(did);
-    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "vpt_ray_marching_batch: %s", hipGetErrorString(e));
-    return VPT_OK;
+    Staging st;
+    const size_t nn = (size_t)n;
+    vpt_ray* dr = st.alloc<vpt_ray>(nn);
+    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn);
+    double *dout = st.alloc<double>(3 * nn), *dxn = st.alloc<double>(3 * nn);
+    int32_t* did = st.alloc<int32_t>(nn);
+    st.up(dr, rays, nn);
+    st.up(ds, states, nn);
+    st.up(dxn, x_new, 3 * nn);
+    st.up(did, idsource, nn);
+    st.launch([&] {
+        ray_marching_kernel<<<vpt_ray_grid(n), dim3(256)>>>(dr, ds, n, sigma_t, sigma_s, steps, ctx->d_scene, dout, dxn, did, dso);
+    });
+    st.down(out_rgb, dout, 3 * nn);
+    st.down(x_new, dxn, 3 * nn);
+    st.down(idsource, did, nn);
+    st.down(out_states, dso, nn);
+    return st.status("vpt_ray_marching_batch");
 }
 
 int vpt_math_probe(vpt_context* ctx, int fn, const double* x, const double* y, double* out, int n)
@@ -1444,23 +1409,14 @@ int vpt_math_probe(vpt_context* ctx, int fn, const double* x, const double* y, d
     if (!ctx || !x || !y || !out || n < 0) return vpt_fail(VPT_E_INVALID, "vpt_math_probe: bad arguments");
     if (n == 0) return VPT_OK;
     HIP_OK(hipSetDevice(ctx->device));
-    double *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    size_t b = sizeof(double) * (size_t)n;
-    hipError_t e = hipMalloc((void**)&dx, b);
-    if (e == hipSuccess) e = hipMalloc((void**)&dy, b);
-    if (e == hipSuccess) e = hipMalloc((void**)&dout, b);
-    if (e == hipSuccess) e = hipMemcpy(dx, x, b, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dy, y, b, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        math_probe_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(fn, dx, dy, dout, n);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, dout, b, hipMemcpyDeviceToHost);
-    (void)hipFree(dx);
-    (void)hipFree(dy);
-    (void)hipFree(dout);
-    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "vpt_math_probe: %s", hipGetErrorString(e));
-    return VPT_OK;
+    Staging st;
+    const size_t nn = (size_t)n;
+    double *dx = st.alloc<double>(nn), *dy = st.alloc<double>(nn), *dout = st.alloc<double>(nn);
+    st.up(dx, x, nn);
+    st.up(dy, y, nn);
+    st.launch([&] { math_probe_kernel<<<vpt_ray_grid(n), dim3(256)>>>(fn, dx, dy, dout, n); });
+    st.down(out, dout, nn);
+    return st.status("vpt_math_probe");
 }
 
 int vpt_phase_probe(vpt_context* ctx, double g, const double din[3], const uint64_t* states, int n, double* dirs,
@@ -1473,31 +1429,19 @@ int vpt_phase_probe(vpt_context* ctx, double g, const double din[3], const uint6
     const int m = n > nw ? n : nw;
     if (m == 0) return VPT_OK;
     HIP_OK(hipSetDevice(ctx->device));
-    uint64_t *dX = nullptr, *dXo = nullptr;
-    double *dd = nullptr, *dw = nullptr, *dv = nullptr;
+    Staging st;
     const size_t n1 = (size_t)(n > 0 ? n : 1), w1 = (size_t)(nw > 0 ? nw : 1);
-    hipError_t e = hipMalloc((void**)&dX, n1 * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&dXo, n1 * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&dd, 3 * n1 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&dw, 3 * w1 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&dv, w1 * sizeof(double));
-    if (e == hipSuccess && n > 0) e = hipMemcpy(dX, states, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && nw > 0) e = hipMemcpy(dw, wl, 3 * (size_t)nw * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        phase_probe_kernel<<<dim3((unsigned)((m + 255) / 256)), dim3(256)>>>(g, din[0], din[1], din[2], dX, n, dd, dXo, dw,
-                                                                            nw, dv);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && n > 0) e = hipMemcpy(dirs, dd, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && n > 0) e = hipMemcpy(states_out, dXo, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && nw > 0) e = hipMemcpy(values, dv, (size_t)nw * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(dX);
-    (void)hipFree(dXo);
-    (void)hipFree(dd);
-    (void)hipFree(dw);
-    (void)hipFree(dv);
-    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "vpt_phase_probe: %s", hipGetErrorString(e));
-    return VPT_OK;
+    uint64_t *dX = st.alloc<uint64_t>(n1), *dXo = st.alloc<uint64_t>(n1);
+    double *dd = st.alloc<double>(3 * n1), *dw = st.alloc<double>(3 * w1), *dv = st.alloc<double>(w1);
+    if (n > 0) st.up(dX, states, (size_t)n);
+    if (nw > 0) st.up(dw, wl, 3 * (size_t)nw);
+    st.launch([&] {
+        phase_probe_kernel<<<vpt_ray_grid(m), dim3(256)>>>(g, din[0], din[1], din[2], dX, n, dd, dXo, dw, nw, dv);
+    });
+    if (n > 0) st.down(dirs, dd, 3 * (size_t)n);
+    if (n > 0) st.down(states_out, dXo, (size_t)n);
+    if (nw > 0) st.down(values, dv, (size_t)nw);
+    return st.status("vpt_phase_probe");
 }
 
 }  // extern "C"

@@ -22,7 +22,8 @@ def functions(path):
                 cur = cur
             continue
         out[cur].append(s)
-    return {k: v for k, v in out.items() if v}
+    # __hip_cuid_<hash>: the unit's id symbol, a hash of the source text and no code
+    return {k: v for k, v in out.items() if v and not k.startswith("__hip_cuid_")}
 
 
 def main():

@@ -114,3 +114,28 @@ def test_scene_constructors():
     s = vpt.scene(vpt.Sphere(1.0, (0, 0, 0), radiance=(1, 2, 3)), vpt.Sphere(2.0, (1, 2, 3), material=1, alpha=0.1))
     assert s.dtype == vpt.SPHERE_DTYPE and len(s) == 2
     assert np.array_equal(vpt.default_scene().view(np.uint8), SCENES["default"]().view(np.uint8))
+
+
+# the ten per-ray functions that stage host arrays on the device, and what each says of a NULL context
+PER_RAY_NULL_CONTEXT = {
+    "vpt_grid_probe": "vpt_grid_probe: bad arguments",
+    "vpt_grid_probe_lm": "vpt_grid_probe_lm: bad arguments",
+    "vpt_grid_ratio_probe": "vpt_grid_ratio_probe: bad arguments",
+    "vpt_grid_eqa_probe": "vpt_grid_eqa_probe: bad arguments",
+    "vpt_grid_emission_probe": "vpt_grid_emission_probe: bad arguments",
+    "vpt_trace_batch": "vpt_trace_batch: bad arguments",
+    "vpt_punctual_volumetric": "vpt_punctual_volumetric: bad arguments",
+    "vpt_ray_marching_batch": "vpt_ray_marching_batch: bad arguments",
+    "vpt_math_probe": "vpt_math_probe: bad arguments",
+    "vpt_phase_probe": "vpt_phase_probe: bad arguments",
+}
+
+
+@pytest.mark.parametrize("name", sorted(PER_RAY_NULL_CONTEXT))
+def test_per_ray_entry_points_refuse_a_null_context(name):
+    """The argument check comes before any GPU call: VPT_E_INVALID and the function's own message."""
+    L = vpt.lib()
+    fn = getattr(L, name)
+    rc = fn(*[t() for t in fn.argtypes])  # every argument zero or NULL, the context first
+    assert rc == _lib.VPT_E_INVALID
+    assert L.vpt_last_error().decode() == PER_RAY_NULL_CONTEXT[name]
