@@ -97,7 +97,7 @@ typedef enum {
                                     * expectation, other draws, a cost that follows the majorant optical depth and
                                     * not the grid's resolution; honours vpt_set_grid_majorant_block; not in the
                                     * accumulator (VPT_E_UNSUPPORTED) */
-    VPT_HETERO_EQUIANGULAR = 12    /* extension: MISVPTTracerRecursive's control flow in the density grid
+    VPT_HETERO_EQUIANGULAR = 12,   /* extension: MISVPTTracerRecursive's control flow in the density grid
                                     * (VPT_E_INVALID without one): the scattering distance is sampled equi-angularly
                                     * toward the picked light inside the part of [0, t] the box holds, the surface
                                     * probability and every transmittance factor are the grid's exact ones, and the
@@ -106,8 +106,18 @@ typedef enum {
                                     * expectation as estimator 10 without the 1 / d^2 noise of a vertex near a point
                                     * light; nearest and trilinear fields; with an emission grid and in the
                                     * accumulator VPT_E_UNSUPPORTED; csrc/vpt_grid_eqa.h, csrc/vpt_hetero_eqa.h */
+    VPT_HETERO_MIS = 13            /* extension: VPT_HETERO_EQUIANGULAR with its distance decision replaced by the
+                                    * one-sample combination of two strategies under the balance heuristic: with
+                                    * probability q (vpt_set_hetero_mis_fraction, default 0.5) the scattering distance
+                                    * is a delta track's, as in estimator 10 (the majorant block is honoured), else the
+                                    * equi-angular one, and the vertex is weighted by the combined pdf
+                                    * q sigma_t rho T + (1 - q) (1 - psurf) p_eq -- a weight bounded by
+                                    * (sigma_s / sigma_t) / q and by estimator 12's / (1 - q) at once; the same
+                                    * expectation as estimators 10 and 12; q = 0 is estimator 12 bit for bit, q = 1
+                                    * samples every distance by tracking; with an emission grid and in the accumulator
+                                    * VPT_E_UNSUPPORTED; csrc/vpt_grid_mis.h, csrc/vpt_hetero_mis.h */
 } vpt_estimator;
-#define VPT_NUM_ESTIMATORS 13
+#define VPT_NUM_ESTIMATORS 14
 
 typedef enum {
     VPT_FB_F32 = 0,            /* framebuffer: 3 x float per pixel */
@@ -419,6 +429,34 @@ int vpt_grid_eqa_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, co
 int vpt_grid_eqa_probe_host(const vpt_grid_desc* desc, const float* density, int interp, double sigma_t, const vpt_ray* rays,
                             const double* tmax, const double* light, const uint64_t* states, int n, double* psurf, double* dist,
                             double* pdf, double* T, double* rho_t, uint64_t* states_out);
+
+/* The track fraction q of estimator VPT_HETERO_MIS: the probability that a distance decision runs a delta track and not
+ * the equi-angular strategy.  Finite and in [0, 1], else VPT_E_INVALID and the previous value stays; the default is 0.5.
+ * Belongs to the context, like the majorant block: it needs no grid and survives grid and scene changes.  Takes effect
+ * with the next render or trace; other estimators do not read it. */
+int vpt_set_hetero_mis_fraction(vpt_context* ctx, double q);
+int vpt_multi_set_hetero_mis_fraction(vpt_multi* m, double q);
+
+/* MIS probe (csrc/vpt_grid_mis.h: vpt_grid_mis_one; one distance decision of estimator VPT_HETERO_MIS).  The inputs are
+ * vpt_grid_eqa_probe's and the track fraction q.  psurf[i] = the grid's transmittance over [0, tmax[i]]; two draws,
+ * always -- the equi-angular draw, then the coin c; c < q is the track strategy (strategy[i] = 1): a delta track from
+ * the state after the coin, with steps[i] tentative steps; else (strategy[i] = 0, steps[i] = 0) the equi-angular
+ * strategy with the surface coin (c - q) / (1 - q).  On the surface dist[i] = -1 and pdf[i] = pe[i] = T[i] = rho_t[i] = +0;
+ * at the track's step cap dist[i] = NaN and the four are +0.  Else dist[i] = the sampled distance, pe[i] = the
+ * equi-angular density there times 1 - psurf[i], rho_t[i] = the density at o + d dist[i], T[i] = the transmittance over
+ * [0, dist[i]] (+0 where rho_t[i] == 0: the path ends there) and pdf[i] = q * (sigma_t * rho_t[i] * T[i]) + (1 - q) * pe[i],
+ * the combined density the vertex is weighted by.  states_out[i] = the state after all draws.  Every output array may
+ * be NULL in the host probe and none in the GPU probe.  The GPU probe reads the context's grid, majorant block,
+ * interpolation and track fraction (VPT_E_INVALID without a grid); the host probe takes the density, the block size
+ * (0: the global majorant), the mode and q (not finite or outside [0, 1] -> VPT_E_INVALID).  At q == 0 psurf, dist, pdf,
+ * T, rho_t and states_out are vpt_grid_eqa_probe's bit for bit.  Host arrays, synchronous. */
+int vpt_grid_mis_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const double* light,
+                       const uint64_t* states, int n, double* psurf, int32_t* strategy, double* dist, double* pdf, double* pe,
+                       double* T, double* rho_t, uint32_t* steps, uint64_t* states_out);
+int vpt_grid_mis_probe_host(const vpt_grid_desc* desc, const float* density, int block, int interp, double sigma_t, double q,
+                            const vpt_ray* rays, const double* tmax, const double* light, const uint64_t* states, int n,
+                            double* psurf, int32_t* strategy, double* dist, double* pdf, double* pe, double* T, double* rho_t,
+                            uint32_t* steps, uint64_t* states_out);
 
 /* PPM writer of main() (src/rt.cpp:812-820): clamp to [0,1] (src/rt.cpp:803), gamma 1/2.2,
  * int(v*255 + .5) (include/mathUtilities.h:43-45), "P3\n%d %d\n255\n" then "%d %d %d " per

@@ -26,6 +26,7 @@ RAY_MARCHING_SA, RAY_MARCHING_GLOBAL, RAY_MARCHING_EXPLICIT = 7, 8, 9
 HETERO_FREE = 10
 HETERO_RATIO = 11
 HETERO_EQUIANGULAR = 12
+HETERO_MIS = 13
 FB_F32, FB_F64 = 0, 1
 GRID_NEAREST, GRID_TRILINEAR = 0, 1  # vpt_grid_interp
 
@@ -109,6 +110,7 @@ PROTOTYPES = [
     ("vpt_set_grid_majorant_block", c_int, [c_void_p, c_int]),
     ("vpt_set_grid_interpolation", c_int, [c_void_p, c_int]),
     ("vpt_set_emission_grid", c_int, [c_void_p, c_void_p, c_void_p]),
+    ("vpt_set_hetero_mis_fraction", c_int, [c_void_p, c_double]),
     ("vpt_render_device", c_int, [c_void_p, POINTER(vpt_params), c_void_p, c_void_p]),
     ("vpt_render", c_int, [c_void_p, POINTER(vpt_params), c_void_p]),
     ("vpt_multi_create", c_int, [c_int, POINTER(c_void_p)]),
@@ -117,6 +119,7 @@ PROTOTYPES = [
     ("vpt_multi_set_grid_majorant_block", c_int, [c_void_p, c_int]),
     ("vpt_multi_set_grid_interpolation", c_int, [c_void_p, c_int]),
     ("vpt_multi_set_emission_grid", c_int, [c_void_p, c_void_p, c_void_p]),
+    ("vpt_multi_set_hetero_mis_fraction", c_int, [c_void_p, c_double]),
     ("vpt_multi_render", c_int, [c_void_p, POINTER(vpt_params), c_void_p]),
     ("vpt_multi_destroy", None, [c_void_p]),
     ("vpt_render_multi", c_int, [c_void_p, c_int, POINTER(vpt_params), c_int, c_void_p]),
@@ -161,6 +164,11 @@ PROTOTYPES = [
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vpt_grid_eqa_probe_host", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vpt_grid_mis_probe", c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vpt_grid_mis_probe_host", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_int, c_double, c_double, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
     ("vpt_write_ppm", c_int, [c_char_p, c_void_p, c_int, c_int, c_int]),
     ("vpt_encode_ppm", c_int64, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64]),
     ("vpt_last_error", c_char_p, []),

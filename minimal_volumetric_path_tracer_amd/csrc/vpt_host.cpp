@@ -22,6 +22,7 @@
 #include "vpt_accum.h"
 #include "vpt_grid.h"
 #include "vpt_grid_eqa.h"
+#include "vpt_grid_mis.h"
 #include "vpt_internal.h"
 #include "vpt_rng.h"
 
@@ -387,6 +388,43 @@ int vpt_grid_eqa_probe_host(const vpt_grid_desc* desc, const float* density, int
         if (pdf) pdf[i] = pf;
         if (T) T[i] = tr;
         if (rho_t) rho_t[i] = rt;
+        if (states_out) states_out[i] = X;
+    }
+    return VPT_OK;
+}
+
+int vpt_grid_mis_probe_host(const vpt_grid_desc* desc, const float* density, int block, int interp, double sigma_t, double q,
+                            const vpt_ray* rays, const double* tmax, const double* light, const uint64_t* states, int n,
+                            double* psurf, int32_t* strategy, double* dist, double* pdf, double* pe, double* T, double* rho_t,
+                            uint32_t* steps, uint64_t* states_out)
+{
+    const char* who = "vpt_grid_mis_probe_host";
+    vpt_clear_error();
+    if (!rays || !tmax || !light || !states || n < 0) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
+    if (block < 0) return vpt_fail(VPT_E_INVALID, "%s: block %d (0 = the global majorant, else >= 1)", who, block);
+    if (interp != VPT_GRID_NEAREST && interp != VPT_GRID_TRILINEAR)
+        return vpt_fail(VPT_E_INVALID, "%s: interp %d (0 = nearest, 1 = trilinear)", who, interp);
+    if (!(q >= 0.0 && q <= 1.0)) return vpt_fail(VPT_E_INVALID, "%s: q %g (finite, in [0, 1])", who, q);
+    int rc = vpt_int_grid_check(desc, density, who);
+    if (rc) return rc;
+    vpt_grid_view G;
+    std::vector<float> maj;
+    probe_view(&G, maj, desc, density, block, interp);
+    for (int i = 0; i < n; ++i) {
+        uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
+        double ps, ds, pf, pq, tr, rt;
+        int sg = 0;
+        uint32_t ns = 0;
+        vpt_grid_mis_one(&G, interp, block != 0, sigma_t, q, rays[i].o, rays[i].d, tmax[i], light + 3 * (size_t)i, &X, &ps, &sg,
+                         &ds, &pf, &pq, &tr, &rt, &ns);
+        if (psurf) psurf[i] = ps;
+        if (strategy) strategy[i] = sg;
+        if (dist) dist[i] = ds;
+        if (pdf) pdf[i] = pf;
+        if (pe) pe[i] = pq;
+        if (T) T[i] = tr;
+        if (rho_t) rho_t[i] = rt;
+        if (steps) steps[i] = ns;
         if (states_out) states_out[i] = X;
     }
     return VPT_OK;

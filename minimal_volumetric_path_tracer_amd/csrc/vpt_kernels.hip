@@ -19,6 +19,7 @@
 #include "vpt_device.h"
 #include "vpt_pool.h"
 #include "vpt_wave.h"
+#include "vpt_hetero_mis.h"
 #include "vpt_hetero_launch.h"
 
 /* the EST = 1 pool kernel comes from vpt_pool_mis.hip, compiled with flags of its own (VPT_MIS_TU;
@@ -305,6 +306,8 @@ struct vpt_context {
     /* emission (vpt_set_emission_grid): the current grid's emission on the device -- the colour's VPT_EMIT_HEAD doubles,
      * then the voxels that h_grid.emit points to (vpt_hetero.h); NULL: none */
     double* d_emit = nullptr;
+    /* estimator 13's track fraction (vpt_set_hetero_mis_fraction): the context's, whatever grid and scene it holds */
+    double mis_fraction = 0.5;
 };
 
 /* The stream's slot, created on first use (or taken over from an idle stream once MAX_STREAM_SLOTS
@@ -376,9 +379,10 @@ static int check_medium(const vpt_medium* m)
  * (include/rayMarchingMethods.h:64,153), so the scene needs at least 6 spheres */
 static int check_march(const vpt_context* ctx, const vpt_medium* m)
 {
-    if (m->estimator == VPT_HETERO_FREE || m->estimator == VPT_HETERO_RATIO || m->estimator == VPT_HETERO_EQUIANGULAR) {
+    if (m->estimator >= VPT_HETERO_FREE && m->estimator <= VPT_HETERO_MIS) {
         if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "estimator %d needs a density grid (vpt_set_density_grid)", m->estimator);
-        if (m->estimator == VPT_HETERO_EQUIANGULAR && ctx->h_grid.emit)  /* emission is scored on a delta track */
+        /* emission is scored on a delta track, which estimator 12 does not run and estimator 13 runs only in part */
+        if ((m->estimator == VPT_HETERO_EQUIANGULAR || m->estimator == VPT_HETERO_MIS) && ctx->h_grid.emit)
             return vpt_fail(VPT_E_UNSUPPORTED, "estimator %d does not score an emission grid (estimators 10 and 11 do)",
                             m->estimator);
         return VPT_OK;
@@ -522,7 +526,7 @@ static bool hetero_simple_kernel()
 }
 
 /* The code object that holds the kernels of estimators 10 and 11 for a lookup (tl: trilinear) and a medium without or
- * with emission (vpt_hetero.h), and estimator 12's for a lookup (vpt_hetero_eqa.h).  The one place where the two settings
+ * with emission (vpt_hetero.h), and estimator 12's and 13's for a lookup (vpt_hetero_eqa.h, vpt_hetero_mis.h).  The one place where the two settings
  * turn into a unit: every launch below goes through the table returned here.  The two grid probes exist in the units
  * without emission only, so their callers pass em = false whatever the context holds. */
 static const vpt_hetero_unit& hetero_unit(bool tl, bool em)
@@ -531,24 +535,30 @@ static const vpt_hetero_unit& hetero_unit(bool tl, bool em)
     return tl ? vpt_int_hetero_unit_tl : vpt_int_hetero_unit;
 }
 static const vpt_hetero_eqa_unit& hetero_eqa_unit(bool tl) { return tl ? vpt_int_hetero_eqa_unit_tl : vpt_int_hetero_eqa_unit; }
+static const vpt_hetero_mis_unit& hetero_mis_unit(bool tl) { return tl ? vpt_int_hetero_mis_unit_tl : vpt_int_hetero_mis_unit; }
 
-/* estimators 10, 11 (by K.est: hetero_kernel / hetero_ratio_kernel) and 12 (hetero_eqa_kernel; the majorant block plays no
- * part) on the stream's queue word; counting mode and VPT_SIMPLE_KERNEL=1: render_kernel_simple<K.est> */
+/* estimators 10, 11 (by K.est: hetero_kernel / hetero_ratio_kernel), 12 (hetero_eqa_kernel; the majorant block plays no
+ * part) and 13 (hetero_mis_kernel, with the context's track fraction) on the stream's queue word; counting mode and
+ * VPT_SIMPLE_KERNEL=1: render_kernel_simple<K.est> */
 static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
 {
     const vpt_grid_view& g = ctx->h_grid;
-    const bool eqa = K.est == VPT_HETERO_EQUIANGULAR, lm = g.block > 0;
+    const bool eqa = K.est == VPT_HETERO_EQUIANGULAR, mis = K.est == VPT_HETERO_MIS, lm = g.block > 0;
     const vpt_hetero_unit& u = hetero_unit(g.interp != 0, g.emit != nullptr);
-    const vpt_hetero_eqa_unit& q = hetero_eqa_unit(g.interp != 0);
-    if (K.counters || hetero_simple_kernel())
-        return eqa ? q.simple_launch(K, ctx->d_scene, stream) : u.simple_launch(K, ctx->d_scene, lm, stream);
+    const vpt_hetero_eqa_unit& ue = hetero_eqa_unit(g.interp != 0);
+    const vpt_hetero_mis_unit& um = hetero_mis_unit(g.interp != 0);
+    if (K.counters || hetero_simple_kernel()) {
+        if (mis) return um.simple_launch(K, ctx->d_scene, lm, ctx->mis_fraction, stream);
+        return eqa ? ue.simple_launch(K, ctx->d_scene, stream) : u.simple_launch(K, ctx->d_scene, lm, stream);
+    }
     std::lock_guard<std::mutex> lock(ctx->mu);
     StreamSlot* sl = nullptr;
     int rc = stream_slot(ctx, stream, 0, &sl);
     if (rc) return rc;
     K.queue = sl->d_queue;
     HIP_OK(hipMemsetAsync(K.queue, 0, sizeof(unsigned), stream));
-    rc = eqa ? q.launch(ctx->device, K, ctx->d_scene, stream) : u.launch(ctx->device, K, ctx->d_scene, lm, stream);
+    if (mis) rc = um.launch(ctx->device, K, ctx->d_scene, lm, ctx->mis_fraction, stream);
+    else rc = eqa ? ue.launch(ctx->device, K, ctx->d_scene, stream) : u.launch(ctx->device, K, ctx->d_scene, lm, stream);
     if (rc) return rc;
     return slot_done(sl, stream);
 }
@@ -556,7 +566,7 @@ static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
 template <int EST, bool COUNT, int FB>
 static int launch_one(vpt_context* ctx, KParams K, hipStream_t stream)
 {
-    if constexpr (EST >= VPT_HETERO_FREE) {  /* the kernels of 10 and 11 live in vpt_hetero.hip, 12's in vpt_hetero_eqa.hip */
+    if constexpr (EST >= VPT_HETERO_FREE) {  /* the kernels of 10 and 11 live in vpt_hetero.hip, 12's in vpt_hetero_eqa.hip, 13's in vpt_hetero_mis.hip */
         return launch_hetero(ctx, K, stream);
     } else {
         const DevScene* S = ctx->d_scene;
@@ -760,6 +770,7 @@ static int launch_render(vpt_context* ctx, KParams K, hipStream_t stream)
         VPT_LAUNCH_EST(10)
         VPT_LAUNCH_EST(11)
         VPT_LAUNCH_EST(12)
+        VPT_LAUNCH_EST(13)
     }
 #undef VPT_LAUNCH_EST
     return vpt_fail(VPT_E_INVALID, "unknown estimator %d", K.est);
@@ -1046,6 +1057,16 @@ int vpt_set_grid_majorant_block(vpt_context* ctx, int block)
     return VPT_OK;
 }
 
+int vpt_set_hetero_mis_fraction(vpt_context* ctx, double q)
+{
+    vpt_clear_error();
+    if (!ctx) return vpt_fail(VPT_E_INVALID, "vpt_set_hetero_mis_fraction: NULL context");
+    if (!(q >= 0.0 && q <= 1.0))  /* a NaN fails both */
+        return vpt_fail(VPT_E_INVALID, "vpt_set_hetero_mis_fraction: q %g (finite, in [0, 1])", q);
+    ctx->mis_fraction = q;  /* a kernel argument of the next launch: nothing in flight reads it */
+    return VPT_OK;
+}
+
 int vpt_set_grid_interpolation(vpt_context* ctx, int mode)
 {
     vpt_clear_error();
@@ -1190,6 +1211,41 @@ int vpt_grid_eqa_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, co
     for (int k = 0; k < 5; ++k) st.down(res[k], dres + (size_t)k * nn, nn);
     st.down(states_out, dso, nn);
     return st.status("vpt_grid_eqa_probe");
+}
+
+int vpt_grid_mis_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const double* light,
+                       const uint64_t* states, int n, double* psurf, int32_t* strategy, double* dist, double* pdf, double* pe,
+                       double* T, double* rho_t, uint32_t* steps, uint64_t* states_out)
+{
+    vpt_clear_error();
+    if (!ctx || !rays || !tmax || !light || !states || !psurf || !strategy || !dist || !pdf || !pe || !T || !rho_t || !steps ||
+        !states_out || n < 0)
+        return vpt_fail(VPT_E_INVALID, "vpt_grid_mis_probe: bad arguments");
+    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "vpt_grid_mis_probe: no density grid set (vpt_set_density_grid)");
+    if (n == 0) return VPT_OK;
+    HIP_OK(hipSetDevice(ctx->device));
+    Staging st;
+    const size_t nn = (size_t)n;
+    vpt_ray* dr = st.alloc<vpt_ray>(nn);
+    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn);
+    double *dtm = st.alloc<double>(nn), *dl = st.alloc<double>(3 * nn);
+    double* dres = st.alloc<double>(6 * nn);  /* the six result arrays of doubles, one behind the other */
+    int32_t* dsg = st.alloc<int32_t>(nn);
+    uint32_t* dst = st.alloc<uint32_t>(nn);
+    st.up(dr, rays, nn);
+    st.up(ds, states, nn);
+    st.up(dtm, tmax, nn);
+    st.up(dl, light, 3 * nn);
+    st.launch([&] {
+        hetero_mis_unit(ctx->h_grid.interp != 0).grid_mis_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, sigma_t,
+                                                                       ctx->mis_fraction, dr, dtm, dl, ds, n, dres, dsg, dst, dso);
+    });
+    double* const res[6] = {psurf, dist, pdf, pe, T, rho_t};
+    for (int k = 0; k < 6; ++k) st.down(res[k], dres + (size_t)k * nn, nn);
+    st.down(strategy, dsg, nn);
+    st.down(steps, dst, nn);
+    st.down(states_out, dso, nn);
+    return st.status("vpt_grid_mis_probe");
 }
 
 int vpt_grid_emission_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
@@ -1339,6 +1395,10 @@ static int trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* ray
             break;
         case VPT_HETERO_EQUIANGULAR:
             hetero_eqa_unit(g.interp != 0).trace_launch(dr, ds, n, mm, ctx->d_scene, ctx->d_grid, dout, dso);
+            break;
+        case VPT_HETERO_MIS:
+            hetero_mis_unit(g.interp != 0).trace_launch(dr, ds, n, mm, ctx->d_scene, ctx->d_grid, g.block > 0,
+                                                        ctx->mis_fraction, dout, dso);
             break;
         default: trace_batch_kernel<9><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         }

@@ -241,6 +241,17 @@ int vpt_multi_set_grid_majorant_block(vpt_multi* m, int block)
     return VPT_OK;
 }
 
+int vpt_multi_set_hetero_mis_fraction(vpt_multi* m, double q)
+{
+    vpt_clear_error();
+    if (!m) return vpt_fail(VPT_E_INVALID, "vpt_multi_set_hetero_mis_fraction: NULL handle");
+    for (int g = 0; g < m->n; ++g) {
+        int rc = vpt_set_hetero_mis_fraction(m->ctx[g], q);
+        if (rc) return rc;
+    }
+    return VPT_OK;
+}
+
 int vpt_multi_set_emission_grid(vpt_multi* m, const float* eps, const double rgb[3])
 {
     vpt_clear_error();

@@ -23,7 +23,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (EXPLICIT_EQUIANGULAR, EXPLICIT_FREE, FB_F32, FB_F64, FREE_FLIGHT, HETERO_EQUIANGULAR, HETERO_FREE, HETERO_RATIO, IMPLICIT_FREE, MIS_EQUIANGULAR,
+from ._lib import (EXPLICIT_EQUIANGULAR, EXPLICIT_FREE, FB_F32, FB_F64, FREE_FLIGHT, HETERO_EQUIANGULAR, HETERO_FREE, HETERO_MIS, HETERO_RATIO, IMPLICIT_FREE, MIS_EQUIANGULAR,
                    RAY_DTYPE, RAY_MARCHING, RAY_MARCHING_EXPLICIT, RAY_MARCHING_GLOBAL, RAY_MARCHING_SA, SPHERE_DTYPE,
                    SURFACE_PT, check, lib)
 
@@ -32,7 +32,8 @@ ESTIMATORS = {"ff": FREE_FLIGHT, "free_flight": FREE_FLIGHT, "mis": MIS_EQUIANGU
               "explicit_equiangular": EXPLICIT_EQUIANGULAR, "surface_pt": SURFACE_PT, "path_tracer": SURFACE_PT,
               "ray_marching": RAY_MARCHING, "ray_marching_sa": RAY_MARCHING_SA, "ray_marching_global": RAY_MARCHING_GLOBAL,
               "ray_marching_explicit": RAY_MARCHING_EXPLICIT, "hetero": HETERO_FREE, "hetero_free": HETERO_FREE,
-              "hetero_ratio": HETERO_RATIO, "hetero_equiangular": HETERO_EQUIANGULAR, "hetero_eqa": HETERO_EQUIANGULAR}
+              "hetero_ratio": HETERO_RATIO, "hetero_equiangular": HETERO_EQUIANGULAR, "hetero_eqa": HETERO_EQUIANGULAR,
+              "hetero_mis": HETERO_MIS, "hetero_mis_equiangular": HETERO_MIS}
 
 
 def Sphere(r, p, c=(0, 0, 0), radiance=(0, 0, 0), material=0, eta=(0, 0, 0), kappa=(0, 0, 0), alpha=0.0) -> np.ndarray:
@@ -164,6 +165,34 @@ def grid_eqa_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, light, states, 
                                         lp.ctypes.data, s.ctypes.data, len(ry), *[a.ctypes.data for a in res],
                                         so.ctypes.data))
     return (*res, so)
+
+
+def _mis_probe_results(n):
+    """the output arrays of a MIS probe in the C argument order, and the tuple the Python probes return"""
+    f = [np.zeros(n) for _ in range(6)]  # psurf, dist, pdf, pe, T, rho_t
+    strategy, steps, so = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64)
+    c_order = [f[0], strategy, f[1], f[2], f[3], f[4], f[5], steps, so]
+    return c_order, (f[0], strategy, f[1], f[2], f[3], f[4], f[5], steps, so)
+
+
+def grid_mis_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, light, states, q: float = 0.5, majorant_block: int = 0,
+                        interpolation: str = "nearest"):
+    """csrc/vpt_grid_mis.h on the host (vpt_grid_mis_probe_host, no GPU): one distance decision of estimator
+    "hetero_mis" per ray -- grid_eqa_probe_host's inputs and the track fraction q in [0, 1]: with the coin below q the
+    distance is a delta track's (majorant_block as in grid_probe_host), else the equi-angular one.  Returns (psurf,
+    strategy, dist, pdf, pe, T, rho_t, steps, states): the surface probability, 1 where the track was taken, the
+    sampled distance (-1 on the surface, NaN at the track's step cap), the combined pdf
+    q sigma_t rho_t T + (1 - q) pe, the equi-angular pdf times 1 - psurf at the distance, the transmittance to the
+    sampled point, the density there, the track's tentative steps and the erand48 states after all draws.  q = 0
+    gives grid_eqa_probe_host's psurf, dist, pdf, T, rho_t and states bit for bit."""
+    mode = _interp_mode(interpolation)
+    d, r = _grid_args(rho, lo, hi)
+    ry, t, lp, s, _, _ = _eqa_probe_args(rays, tmax, light, states)
+    c_order, out = _mis_probe_results(len(ry))
+    check(lib().vpt_grid_mis_probe_host(byref(d), r.ctypes.data, int(majorant_block), mode, float(sigma_t), float(q),
+                                        ry.ctypes.data, t.ctypes.data, lp.ctypes.data, s.ctypes.data, len(ry),
+                                        *[a.ctypes.data for a in c_order]))
+    return out
 
 
 def _emission_args(eps, rgb, shape) -> tuple[np.ndarray, np.ndarray]:
@@ -320,6 +349,12 @@ class Tracer:
         check(lib().vpt_set_grid_majorant_block(self._ctx, int(block)))
         self._majorant_block = int(block)
 
+    def set_hetero_mis_fraction(self, q: float) -> None:
+        """The track fraction of estimator "hetero_mis": the probability q in [0, 1] (default 0.5) that a distance is
+        sampled by delta tracking and not equi-angularly; 0 is estimator "hetero_equiangular" bit for bit.  Belongs to
+        the tracer: it survives grid and scene changes.  A value that is refused leaves the setting as it was."""
+        check(lib().vpt_set_hetero_mis_fraction(self._ctx, float(q)))
+
     def set_grid_interpolation(self, interpolation: str) -> None:
         """How the density is read between the voxel centres: "nearest" (the default: constant per voxel) or
         "trilinear" (a smooth field, clamped at the border of the box; include/vpt.h vpt_set_grid_interpolation).
@@ -365,6 +400,15 @@ class Tracer:
         check(lib().vpt_grid_eqa_probe(self._ctx, float(sigma_t), ry.ctypes.data, t.ctypes.data, lp.ctypes.data,
                                        s.ctypes.data, len(ry), *[a.ctypes.data for a in res], so.ctypes.data))
         return (*res, so)
+
+    def grid_mis_probe(self, sigma_t: float, rays, tmax, light, states):
+        """grid_mis_probe_host's quantities for the tracer's grid, majorant block, interpolation and track fraction,
+        computed on the GPU (vpt_grid_mis_probe)."""
+        ry, t, lp, s, _, _ = _eqa_probe_args(rays, tmax, light, states)
+        c_order, out = _mis_probe_results(len(ry))
+        check(lib().vpt_grid_mis_probe(self._ctx, float(sigma_t), ry.ctypes.data, t.ctypes.data, lp.ctypes.data,
+                                       s.ctypes.data, len(ry), *[a.ctypes.data for a in c_order]))
+        return out
 
     # ---- main()'s pixel loop (src/rt.cpp:767-805) ----
     def render(self, cfg: Optional[RenderConfig] = None, **kw) -> np.ndarray:
@@ -626,6 +670,10 @@ class MultiTracer:
 
     def clear_emission_grid(self) -> None:
         check(lib().vpt_multi_set_emission_grid(self._m, None, None))
+
+    def set_hetero_mis_fraction(self, q: float) -> None:
+        """Tracer.set_hetero_mis_fraction on every rank's context."""
+        check(lib().vpt_multi_set_hetero_mis_fraction(self._m, float(q)))
 
     def set_majorant_block(self, block: int) -> None:
         """Tracer.set_majorant_block on every rank's context."""
