@@ -106,7 +106,7 @@ typedef enum {
                                     * expectation as estimator 10 without the 1 / d^2 noise of a vertex near a point
                                     * light; nearest and trilinear fields; with an emission grid and in the
                                     * accumulator VPT_E_UNSUPPORTED; csrc/vpt_grid_eqa.h, csrc/vpt_hetero_eqa.h */
-    VPT_HETERO_MIS = 13            /* extension: VPT_HETERO_EQUIANGULAR with its distance decision replaced by the
+    VPT_HETERO_MIS = 13,           /* extension: VPT_HETERO_EQUIANGULAR with its distance decision replaced by the
                                     * one-sample combination of two strategies under the balance heuristic: with
                                     * probability q (vpt_set_hetero_mis_fraction, default 0.5) the scattering distance
                                     * is a delta track's, as in estimator 10 (the majorant block is honoured), else the
@@ -116,8 +116,20 @@ typedef enum {
                                     * expectation as estimators 10 and 12; q = 0 is estimator 12 bit for bit, q = 1
                                     * samples every distance by tracking; with an emission grid and in the accumulator
                                     * VPT_E_UNSUPPORTED; csrc/vpt_grid_mis.h, csrc/vpt_hetero_mis.h */
+    VPT_HETERO_CHROMATIC = 14      /* extension: VPT_HETERO_FREE in a chromatic medium -- the context's medium colour
+                                    * (vpt_set_medium_colour) multiplies sigma_a and sigma_s per colour channel.  One
+                                    * draw per decision picks a hero channel whose extinction drives the delta track
+                                    * (the majorant block is honoured), and collisions, surfaces and every
+                                    * transmittance factor are weighted per channel by the balance heuristic over the
+                                    * three hero choices, evaluated exactly from the grid's optical depth: weights
+                                    * bounded by 3 ss_c / st_c and by 3.  With equal extinctions in the three channels
+                                    * (the default colour among them) no hero draw is taken and the paths are
+                                    * estimator 10's draw for draw; with the default colour the image is estimator
+                                    * 10's bit for bit.  A channel without extinction is VPT_E_INVALID; with an
+                                    * emission grid and in the accumulator VPT_E_UNSUPPORTED; csrc/vpt_grid_chroma.h,
+                                    * csrc/vpt_hetero_chroma.h */
 } vpt_estimator;
-#define VPT_NUM_ESTIMATORS 14
+#define VPT_NUM_ESTIMATORS 15
 
 typedef enum {
     VPT_FB_F32 = 0,            /* framebuffer: 3 x float per pixel */
@@ -457,6 +469,35 @@ int vpt_grid_mis_probe_host(const vpt_grid_desc* desc, const float* density, int
                             const vpt_ray* rays, const double* tmax, const double* light, const uint64_t* states, int n,
                             double* psurf, int32_t* strategy, double* dist, double* pdf, double* pe, double* T, double* rho_t,
                             uint32_t* steps, uint64_t* states_out);
+
+/* The medium colour of estimator VPT_HETERO_CHROMATIC: per colour channel c the multipliers absorb[c] of the medium's
+ * sigma_a and scatter[c] of its sigma_s, so that per unit density sa_c = sigma_a * absorb[c], ss_c = sigma_s * scatter[c]
+ * and st_c = sa_c + ss_c.  Every value finite and >= 0, else VPT_E_INVALID and the previous values stay; the default is
+ * (1, 1, 1) for both.  Belongs to the context, like the track fraction: it needs no grid and survives grid and scene
+ * changes.  Takes effect with the next render or trace; other estimators do not read it.  A render or trace of estimator
+ * VPT_HETERO_CHROMATIC with some st_c == 0 is VPT_E_INVALID. */
+int vpt_set_medium_colour(vpt_context* ctx, const double absorb[3], const double scatter[3]);
+int vpt_multi_set_medium_colour(vpt_multi* m, const double absorb[3], const double scatter[3]);
+
+/* Chromatic probe (csrc/vpt_grid_chroma.h: vpt_grid_chroma_one; one distance decision of estimator
+ * VPT_HETERO_CHROMATIC).  For each of the n rays (unit directions) with surface distance tmax[i] and erand48 state
+ * states[i]: hero[i] = the hero channel -- one draw, none and channel 0 where the three st_c are equal; a delta track
+ * under st_hero from the state after that draw, with steps[i] tentative steps: t_coll[i] = the collision distance, -1
+ * for "none", NaN at the step cap.  At a collision tau[i] = the optical depth over [0, t_coll[i]] and w = the weight
+ * that stands in the albedo's place, w_c = ss_c e_c / ((sum_k st_k e_k) / 3) with e_k = exp(-(st_k tau - min_j st_j tau));
+ * at "none" tau[i] = the optical depth over [0, tmax[i]] and w_c = e_c / ((sum_k e_k) / 3), the weight of the surface
+ * branch; at the cap tau[i] and w are +0.  w holds 3 n doubles, channel c of ray i at w[c * n + i].  states_out[i] = the
+ * state after all draws.  Every output array may be NULL in the host probe and none in the GPU probe.  The GPU probe
+ * reads the context's grid, majorant block, interpolation and medium colour (VPT_E_INVALID without a grid) and takes
+ * the medium's sigma_a and sigma_s; the host probe takes the density, the block size (0: the global majorant), the mode
+ * and the six coefficients sa[3], ss[3] per unit density themselves (st_c = sa[c] + ss[c]).  A coefficient that is not
+ * finite or negative, or some st_c == 0, is VPT_E_INVALID.  Host arrays, synchronous. */
+int vpt_grid_chroma_probe(vpt_context* ctx, double sigma_a, double sigma_s, const vpt_ray* rays, const double* tmax,
+                          const uint64_t* states, int n, int32_t* hero, double* t_coll, double* tau, double* w, uint32_t* steps,
+                          uint64_t* states_out);
+int vpt_grid_chroma_probe_host(const vpt_grid_desc* desc, const float* density, int block, int interp, const double sa[3],
+                               const double ss[3], const vpt_ray* rays, const double* tmax, const uint64_t* states, int n,
+                               int32_t* hero, double* t_coll, double* tau, double* w, uint32_t* steps, uint64_t* states_out);
 
 /* PPM writer of main() (src/rt.cpp:812-820): clamp to [0,1] (src/rt.cpp:803), gamma 1/2.2,
  * int(v*255 + .5) (include/mathUtilities.h:43-45), "P3\n%d %d\n255\n" then "%d %d %d " per

@@ -27,6 +27,7 @@ HETERO_FREE = 10
 HETERO_RATIO = 11
 HETERO_EQUIANGULAR = 12
 HETERO_MIS = 13
+HETERO_CHROMATIC = 14
 FB_F32, FB_F64 = 0, 1
 GRID_NEAREST, GRID_TRILINEAR = 0, 1  # vpt_grid_interp
 
@@ -111,6 +112,7 @@ PROTOTYPES = [
     ("vpt_set_grid_interpolation", c_int, [c_void_p, c_int]),
     ("vpt_set_emission_grid", c_int, [c_void_p, c_void_p, c_void_p]),
     ("vpt_set_hetero_mis_fraction", c_int, [c_void_p, c_double]),
+    ("vpt_set_medium_colour", c_int, [c_void_p, c_void_p, c_void_p]),
     ("vpt_render_device", c_int, [c_void_p, POINTER(vpt_params), c_void_p, c_void_p]),
     ("vpt_render", c_int, [c_void_p, POINTER(vpt_params), c_void_p]),
     ("vpt_multi_create", c_int, [c_int, POINTER(c_void_p)]),
@@ -120,6 +122,7 @@ PROTOTYPES = [
     ("vpt_multi_set_grid_interpolation", c_int, [c_void_p, c_int]),
     ("vpt_multi_set_emission_grid", c_int, [c_void_p, c_void_p, c_void_p]),
     ("vpt_multi_set_hetero_mis_fraction", c_int, [c_void_p, c_double]),
+    ("vpt_multi_set_medium_colour", c_int, [c_void_p, c_void_p, c_void_p]),
     ("vpt_multi_render", c_int, [c_void_p, POINTER(vpt_params), c_void_p]),
     ("vpt_multi_destroy", None, [c_void_p]),
     ("vpt_render_multi", c_int, [c_void_p, c_int, POINTER(vpt_params), c_int, c_void_p]),
@@ -169,6 +172,11 @@ PROTOTYPES = [
     ("vpt_grid_mis_probe_host", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_int, c_double, c_double, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p]),
+    ("vpt_grid_chroma_probe", c_int, [c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vpt_grid_chroma_probe_host", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p]),
     ("vpt_write_ppm", c_int, [c_char_p, c_void_p, c_int, c_int, c_int]),
     ("vpt_encode_ppm", c_int64, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64]),
     ("vpt_last_error", c_char_p, []),

@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "vpt_math.h"
 #include "vpt_rng.h"
 #include "vpt_scene.h"
@@ -551,11 +553,18 @@ VPT_DEV double transmitance(dv3 a, dv3 b, double sigma_t)
  * TrHom (the default) selects the code above, unchanged; a policy with hom == false supplies
  * between(a, b, sigma_t) and along(o, unit d, dist, sigma_t) -- the density grid's transmittance.  A policy
  * with draws == true estimates the factor stochastically and takes the sampler as its first argument (estimator
- * 11's ratio tracking): the draws are taken where the factor is evaluated. */
+ * 11's ratio tracking): the draws are taken where the factor is evaluated.  A policy that declares vec == true returns
+ * one factor per colour channel, a dv3, and the helpers multiply by it componentwise (estimator 14's chromatic medium,
+ * vpt_hetero_chroma.h); a policy without the member is scalar, so the policies above and their instantiations stay as
+ * they were. */
 struct TrHom {
     static constexpr bool hom = true;
     static constexpr bool draws = false;
 };
+template <class TP, class = void>
+struct tp_vec : std::false_type {};
+template <class TP>
+struct tp_vec<TP, std::enable_if_t<TP::vec>> : std::true_type {};
 
 /* multipleT, include/volumetricBasicFunctions.h:26-57 (material-3 spheres only) */
 template <bool COUNT>
@@ -950,6 +959,8 @@ VPT_DEV dv3 mis_v2(const DevScene* __restrict__ S, Sampler<COUNT>& smp, int obj,
             if (TR) f = scl(f, transmitance(x, sph_p(S, light), sigma_t));
         } else if constexpr (TP::draws) {
             if (TR) f = scl(f, tp.between(smp, x, sph_p(S, light), sigma_t));
+        } else if constexpr (tp_vec<TP>::value) {
+            if (TR) f = mul(f, tp.between(x, sph_p(S, light), sigma_t));
         } else {
             if (TR) f = scl(f, tp.between(x, sph_p(S, light), sigma_t));
         }
@@ -1438,6 +1449,7 @@ VPT_DEV dv3 point_shadow_value(const DevScene* __restrict__ S, Sampler<COUNT>& s
     dv3 Ls;
     if constexpr (TP::hom) Ls = scl(scl(Le, VPT_PL_REUSE ? lm_exp(sigma_t * mag * -1.0) : transmitance(xt, lp, sigma_t)), ph);
     else if constexpr (TP::draws) Ls = scl(scl(Le, tp.between(smp, xt, lp, sigma_t)), ph);
+    else if constexpr (tp_vec<TP>::value) Ls = scl(mul(Le, tp.between(xt, lp, sigma_t)), ph);
     else Ls = scl(scl(Le, tp.between(xt, lp, sigma_t)), ph);
     if (with_sigma) return scl(scl(scl(Ls, trxt), sigma_s), (1 / probSource));
     return scl(Ls, (1 / probSource));
@@ -1548,12 +1560,14 @@ VPT_DEV dv3 single_scattering(const DevScene* __restrict__ S, Sampler<COUNT>& sm
          * (SURVEY H5); zero_ok: the caller's update absorbs a signed zero (finite throughput and
          * pdf), so +0 is the same result without the exponential and the phase value */
         if (!(point && zero_ok && cmax == 1.0)) {
-            double it;
+            std::conditional_t<tp_vec<TP>::value, dv3, double> it;
             if constexpr (TP::hom) it = lm_exp(sigma_t * tdist * -1.0);
             else if constexpr (TP::draws) it = tp.along(smp, xt, wl, tdist, sigma_t);
             else it = tp.along(xt, wl, tdist, sigma_t);
             double ph = smp.g == 0.0 ? 1 / (4 * VPT_PI) : phase_value(smp.g, din, wl);
-            dv3 Ls = scl(scl(rad, it), ph);
+            dv3 Ls;
+            if constexpr (tp_vec<TP>::value) Ls = scl(mul(rad, it), ph);
+            else Ls = scl(scl(rad, it), ph);
             if (with_sigma) Ld = scl(scl(scl(scl(Ls, trxt), sigma_s), (1 / prob_wl)), (1 / probSource));
             else Ld = scl(scl(Ls, (1 / prob_wl)), (1 / probSource));
         }

@@ -1,0 +1,233 @@
+/*
+ * vpt_hetero_chroma.hip -- the kernels of estimator 14 (VPT_HETERO_CHROMATIC, vpt_hetero_chroma.h) in a translation unit
+ * of their own, as vpt_hetero_mis.hip is for estimator 13: the code objects of the other estimators stay what they were.
+ *
+ * hetero_chroma_kernel: the persistent-wave loop of vpt_wave.h on estimator 14's steps (HeteroChromaSteps).  A lane owns
+ * one pixel and runs that pixel's samples strictly in order, so the image is render_kernel_simple<14>'s bit for bit.  The
+ * prologue that stages a grid of at most 64 KiB in LDS, and with local majorants the majorant grid in what the density
+ * left of the budget, is vpt_hetero.hip's, restated as estimators 11 to 13 restated it.
+ *
+ * The six per-channel coefficients (ChromaCoef) are a kernel argument of every kernel here (KParams keeps its layout),
+ * so render_kernel_simple<14> is an overload with that argument: vpt_render_simple.h's kernel with trace_hetero_chroma
+ * in the estimator's place.
+ *
+ * Trilinear interpolation: the unit instantiates one value of TL, VPT_HETERO_TL.  Compiled as it stands (0) it holds the
+ * nearest-lookup kernels and exports their launches as the table vpt_int_hetero_chroma_unit (vpt_hetero_chroma.h);
+ * vpt_hetero_chroma_tl.hip includes this file with VPT_HETERO_TL = 1 and exports vpt_int_hetero_chroma_unit_tl.  The
+ * launches are static; their host side is vpt_hetero_launch.h's, shared with the other density-grid units.
+ */
+#include <hip/hip_runtime.h>
+
+#include "vpt_wave.h"
+#include "vpt_hetero_chroma.h"
+#include "vpt_hetero_launch.h"
+
+#ifndef VPT_HETERO_LDS
+#define VPT_HETERO_LDS 1
+#endif
+#define VPT_HETERO_LDS_BYTES 65536
+#ifndef VPT_HETERO_TL
+#define VPT_HETERO_TL 0
+#endif
+#if VPT_HETERO_TL
+#define VPT_HX(name) name##_tl
+#else
+#define VPT_HX(name) name
+#endif
+#ifndef VPT_HETERO_LDS_MAJ
+#define VPT_HETERO_LDS_MAJ 1
+#endif
+
+namespace vpt {
+
+template <bool COUNT, int FB, bool LM, bool TL>
+__global__ __launch_bounds__(256, 2) void hetero_chroma_kernel(KParams P, const DevScene* __restrict__ S, ChromaCoef c)
+{
+    using TP = GridChromaTr<TL>;
+    /* the view lives in the steps object from the start, as in hetero_kernel: the walkers take its address */
+    HeteroChromaSteps<LM, TL> st{TP::template load<LM>(P.grid, c)};
+    [[maybe_unused]] auto& G = st.tp.G;
+#if VPT_HETERO_LDS
+    __shared__ float lds_rho[VPT_HETERO_LDS_BYTES / sizeof(float)];
+    {
+        const int64_t nv = (int64_t)G.n[0] * G.n[1] * G.n[2];
+        if (nv <= (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float))) {  /* workgroup-uniform */
+            for (int k = threadIdx.x; k < (int)nv; k += blockDim.x) lds_rho[k] = G.rho[k];
+            __syncthreads();
+            G.rho = lds_rho;
+        }
+#if VPT_HETERO_LDS_MAJ
+        if (LM) {  /* the majorant grid goes into what the density left of the budget */
+            const int64_t cap = (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float));
+            const int64_t used = nv <= cap ? nv : 0;
+            const int64_t nbv = (int64_t)G.nb[0] * G.nb[1] * G.nb[2];
+            if (nbv <= cap - used) {  /* workgroup-uniform */
+                for (int k = threadIdx.x; k < (int)nbv; k += blockDim.x) lds_rho[used + k] = G.maj[k];
+                __syncthreads();
+                G.maj = lds_rho + used;
+            }
+        }
+#endif
+    }
+#endif
+    wave_render<HeteroChromaSteps<LM, TL>, COUNT, FB>(P, S, st);
+}
+
+}  // namespace vpt
+
+using namespace vpt;
+
+namespace {
+
+constexpr bool TLU = VPT_HETERO_TL != 0;  /* the unit's value of TL */
+
+/* render_kernel_simple (vpt_render_simple.h) for estimator 14: one lane per pixel, the samples in sequence; c holds the
+ * per-channel coefficients */
+template <int EST, bool COUNT, int FB, bool LM, bool TL>
+__global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const DevScene* __restrict__ S, ChromaCoef c)
+{
+    static_assert(EST == VPT_HETERO_CHROMATIC, "the overload with per-channel coefficients is estimator 14's");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
+    const int lr = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    if (x >= P.w || lr >= P.shard_rows) return;
+    const PixelRow row = pixel_row(P, x, lr);
+    const Medium m = medium_of(P);
+    const dv3 o = mk(P.o[0], P.o[1], P.o[2]);
+    const GridChromaTr<TL> tp = GridChromaTr<TL>::template load<LM>(P.grid, c);
+    dv3 acc = mk(0, 0, 0);
+    uint64_t tests = 0, iters = 0, mism = 0;
+    for (int i = 0; i < P.spp; ++i) {
+        Sampler<COUNT> smp;
+        smp.X = vpt_stream_start(P.seed, row.idx, (uint64_t)i);
+        smp.g = P.g;
+        smp.cnt.tests = 0;
+        smp.cnt.iterations = 0;
+        smp.cnt.draw_mismatch = 0;
+        const dv3 dir = camera_dir(P, smp, x, row.y);
+        const dv3 L = trace_hetero_chroma<COUNT, LM, TL>(S, tp, smp, o, dir, m);
+        acc = add(L, acc);
+        if (COUNT) {
+            tests += smp.cnt.tests;
+            iters += smp.cnt.iterations;
+            mism += smp.cnt.draw_mismatch;
+        }
+    }
+    store_pixel<FB>(P, x, lr, acc);
+    if (COUNT) {
+        atomicAdd(&P.counters[0], (unsigned long long)tests);
+        atomicAdd(&P.counters[1], (unsigned long long)iters);
+        if (mism) atomicAdd(&P.counters[2], (unsigned long long)mism);
+    }
+}
+
+/* estimator 14's per-sample call (vpt_hetero_chroma.h) */
+template <bool LM, bool TL>
+__global__ __launch_bounds__(256) void trace_batch_hetero_chroma_kernel(const vpt_ray* __restrict__ rays,
+                                                                        const uint64_t* __restrict__ states, int n, Medium m,
+                                                                        const DevScene* __restrict__ S,
+                                                                        const vpt_grid_view* __restrict__ grid, ChromaCoef c,
+                                                                        double* out, uint64_t* out_states)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Sampler<false> smp;
+    smp.X = states[i] & 0xFFFFFFFFFFFFull;
+    smp.g = m.g;
+    dv3 L = trace_hetero_chroma<false, LM, TL>(S, GridChromaTr<TL>::template load<LM>(grid, c), smp, ld3(rays[i].o),
+                                               ld3(rays[i].d), m);
+    out[3 * i] = L.x;
+    out[3 * i + 1] = L.y;
+    out[3 * i + 2] = L.z;
+    out_states[i] = smp.X;
+}
+
+/* one decision per lane (vpt_grid_chroma.h: vpt_grid_chroma_one; vpt_grid_chroma_probe).  res: five arrays of n doubles,
+ * one behind the other */
+template <bool LM, bool TL>
+__global__ __launch_bounds__(256) void grid_chroma_probe_kernel(const vpt_grid_view* __restrict__ grid, ChromaCoef c,
+                                                                const vpt_ray* __restrict__ rays, const double* __restrict__ tmax,
+                                                                const uint64_t* __restrict__ states, int n, double* res,
+                                                                int32_t* hero, uint32_t* steps, uint64_t* states_out)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const vpt_grid_fields G = *grid;
+    const double o[3] = {rays[i].o[0], rays[i].o[1], rays[i].o[2]}, d[3] = {rays[i].d[0], rays[i].d[1], rays[i].d[2]};
+    uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
+    double tc, tau, w[3];
+    int h = 0;
+    uint32_t ns = 0;
+    vpt_grid_chroma_one(&G, TL, LM, c.ss, c.st, o, d, tmax[i], &X, &h, &tc, &tau, w, &ns);
+    const size_t nn = (size_t)n;
+    res[i] = tc;
+    res[nn + i] = tau;
+    res[2 * nn + i] = w[0];
+    res[3 * nn + i] = w[1];
+    res[4 * nn + i] = w[2];
+    hero[i] = h;
+    steps[i] = ns;
+    states_out[i] = X;
+}
+
+}  // namespace
+
+/* the unit's launches, the slots of vpt_hetero_chroma_unit (vpt_hetero_chroma.h) */
+static void trace_launch(const vpt_ray* rays, const uint64_t* states, int n, const Medium& m, const DevScene* S,
+                         const vpt_grid_view* grid, bool lm, const ChromaCoef& c, double* out, uint64_t* out_states)
+{
+    const dim3 g = vpt_ray_grid(n), b(256);
+    if (lm) trace_batch_hetero_chroma_kernel<true, TLU><<<g, b>>>(rays, states, n, m, S, grid, c, out, out_states);
+    else trace_batch_hetero_chroma_kernel<false, TLU><<<g, b>>>(rays, states, n, m, S, grid, c, out, out_states);
+}
+
+static void grid_chroma_probe_launch(const vpt_grid_view* grid, bool lm, const ChromaCoef& c, const vpt_ray* rays,
+                                     const double* tmax, const uint64_t* states, int n, double* res, int32_t* hero,
+                                     uint32_t* steps, uint64_t* states_out)
+{
+    const dim3 g = vpt_ray_grid(n), b(256);
+    if (lm) grid_chroma_probe_kernel<true, TLU><<<g, b>>>(grid, c, rays, tmax, states, n, res, hero, steps, states_out);
+    else grid_chroma_probe_kernel<false, TLU><<<g, b>>>(grid, c, rays, tmax, states, n, res, hero, steps, states_out);
+}
+
+/* render_kernel_simple<14>: vpt_simple_launch (vpt_hetero_launch.h) with the coefficients behind the scene */
+static int simple_launch(const KParams& K, const DevScene* S, bool lm, const ChromaCoef& c, void* stream)
+{
+    return with_flags([&](auto lmc, auto count, auto f32) {
+        constexpr int FB = decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64;
+        dim3 grid((unsigned)((K.w + 15) / 16), (unsigned)((K.shard_rows + 15) / 16));
+        render_kernel_simple<VPT_HETERO_CHROMATIC, decltype(count)::value, FB, decltype(lmc)::value, TLU>
+            <<<grid, dim3(256), 0, (hipStream_t)stream>>>(K, S, c);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return vpt_fail(VPT_E_HIP, "render_kernel_simple<%d> launch: %s", (int)VPT_HETERO_CHROMATIC, hipGetErrorString(e));
+        return (int)VPT_OK;
+    }, lm, K.counters != nullptr, K.fb == VPT_FB_F32);
+}
+
+/* the persistent-wave kernel: vpt_persistent_launch (vpt_hetero_launch.h) with the coefficients behind the scene */
+template <class Kern>
+static int persistent_launch(Kern kern, int device, const KParams& K, const DevScene* S, const ChromaCoef& c, void* stream)
+{
+    int blocks = 0;
+    hipError_t e = vpt_resident_blocks(kern, 256, device, &blocks);
+    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_chroma_kernel: %s", hipGetErrorString(e));
+    kern<<<dim3((unsigned)vpt_wave_blocks(blocks, K)), dim3(256), 0, (hipStream_t)stream>>>(K, S, c);
+    e = hipGetLastError();
+    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_chroma_kernel launch: %s", hipGetErrorString(e));
+    return (int)VPT_OK;
+}
+
+static int launch(int device, const KParams& K, const DevScene* S, bool lm, const ChromaCoef& c, void* stream)
+{
+    return with_flags([&](auto lmc, auto f32) {
+        return persistent_launch(hetero_chroma_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU>,
+                                 device, K, S, c, stream);
+    }, lm, K.fb == VPT_FB_F32);
+}
+
+/* what the unit exports.  Host pass only: a const object with a constant initialiser is emitted for the device as well,
+ * and these are host functions */
+#if !defined(__HIP_DEVICE_COMPILE__)
+const vpt_hetero_chroma_unit VPT_HX(vpt_int_hetero_chroma_unit) = {launch, simple_launch, trace_launch, grid_chroma_probe_launch};
+#endif

@@ -23,6 +23,7 @@
 #include "vpt_grid.h"
 #include "vpt_grid_eqa.h"
 #include "vpt_grid_mis.h"
+#include "vpt_grid_chroma.h"
 #include "vpt_internal.h"
 #include "vpt_rng.h"
 
@@ -424,6 +425,46 @@ int vpt_grid_mis_probe_host(const vpt_grid_desc* desc, const float* density, int
         if (pe) pe[i] = pq;
         if (T) T[i] = tr;
         if (rho_t) rho_t[i] = rt;
+        if (steps) steps[i] = ns;
+        if (states_out) states_out[i] = X;
+    }
+    return VPT_OK;
+}
+
+int vpt_grid_chroma_probe_host(const vpt_grid_desc* desc, const float* density, int block, int interp, const double sa[3],
+                               const double ss[3], const vpt_ray* rays, const double* tmax, const uint64_t* states, int n,
+                               int32_t* hero, double* t_coll, double* tau, double* w, uint32_t* steps, uint64_t* states_out)
+{
+    const char* who = "vpt_grid_chroma_probe_host";
+    vpt_clear_error();
+    if (!sa || !ss || !rays || !tmax || !states || n < 0) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
+    if (block < 0) return vpt_fail(VPT_E_INVALID, "%s: block %d (0 = the global majorant, else >= 1)", who, block);
+    if (interp != VPT_GRID_NEAREST && interp != VPT_GRID_TRILINEAR)
+        return vpt_fail(VPT_E_INVALID, "%s: interp %d (0 = nearest, 1 = trilinear)", who, interp);
+    double st[3];
+    for (int k = 0; k < 3; ++k) {
+        if (!(sa[k] >= 0.0 && sa[k] - sa[k] == 0.0 && ss[k] >= 0.0 && ss[k] - ss[k] == 0.0))  /* a NaN fails both */
+            return vpt_fail(VPT_E_INVALID, "%s: channel %d: sa %g, ss %g (finite, >= 0)", who, k, sa[k], ss[k]);
+        st[k] = sa[k] + ss[k];
+        if (!(st[k] > 0.0)) return vpt_fail(VPT_E_INVALID, "%s: channel %d has no extinction", who, k);
+    }
+    int rc = vpt_int_grid_check(desc, density, who);
+    if (rc) return rc;
+    vpt_grid_view G;
+    std::vector<float> maj;
+    probe_view(&G, maj, desc, density, block, interp);
+    const size_t nn = (size_t)n;
+    for (int i = 0; i < n; ++i) {
+        uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
+        double tc, ta, wk[3];
+        int h = 0;
+        uint32_t ns = 0;
+        vpt_grid_chroma_one(&G, interp, block != 0, ss, st, rays[i].o, rays[i].d, tmax[i], &X, &h, &tc, &ta, wk, &ns);
+        if (hero) hero[i] = h;
+        if (t_coll) t_coll[i] = tc;
+        if (tau) tau[i] = ta;
+        if (w)
+            for (int k = 0; k < 3; ++k) w[(size_t)k * nn + i] = wk[k];
         if (steps) steps[i] = ns;
         if (states_out) states_out[i] = X;
     }

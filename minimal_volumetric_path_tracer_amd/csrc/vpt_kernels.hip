@@ -20,6 +20,7 @@
 #include "vpt_pool.h"
 #include "vpt_wave.h"
 #include "vpt_hetero_mis.h"
+#include "vpt_hetero_chroma.h"
 #include "vpt_hetero_launch.h"
 
 /* the EST = 1 pool kernel comes from vpt_pool_mis.hip, compiled with flags of its own (VPT_MIS_TU;
@@ -308,6 +309,9 @@ struct vpt_context {
     double* d_emit = nullptr;
     /* estimator 13's track fraction (vpt_set_hetero_mis_fraction): the context's, whatever grid and scene it holds */
     double mis_fraction = 0.5;
+    /* estimator 14's medium colour (vpt_set_medium_colour): the per-channel multipliers of sigma_a and sigma_s; the
+     * context's, like the track fraction */
+    double chroma_a[3] = {1.0, 1.0, 1.0}, chroma_s[3] = {1.0, 1.0, 1.0};
 };
 
 /* The stream's slot, created on first use (or taken over from an idle stream once MAX_STREAM_SLOTS
@@ -373,14 +377,38 @@ static int check_medium(const vpt_medium* m)
     return VPT_OK;
 }
 
+/* the launch constants of estimator 14 from the medium and the context's colour: per unit density ss[k] = sigma_s * cs[k]
+ * and st[k] = sigma_a * ca[k] + ss[k] (vpt_hetero_chroma.h) */
+static ChromaCoef chroma_coef(const vpt_context* ctx, double sigma_a, double sigma_s)
+{
+    ChromaCoef c;
+    for (int k = 0; k < 3; ++k) {
+        const double sa = sigma_a * ctx->chroma_a[k];
+        c.ss[k] = sigma_s * ctx->chroma_s[k];
+        c.st[k] = sa + c.ss[k];
+    }
+    return c;
+}
+
 /* the ray-marching estimators' parameters: march_step (the step of rayMarching3 / rayMarching2, the
  * segment count of rayMarchingGlobal / rayMarching) finite and > 0; march_light (6, 7) a sphere of
  * the scene; rayMarchingGlobal and rayMarching read the hard-coded sphere 5
  * (include/rayMarchingMethods.h:64,153), so the scene needs at least 6 spheres */
 static int check_march(const vpt_context* ctx, const vpt_medium* m)
 {
-    if (m->estimator >= VPT_HETERO_FREE && m->estimator <= VPT_HETERO_MIS) {
+    if (m->estimator >= VPT_HETERO_FREE && m->estimator <= VPT_HETERO_CHROMATIC) {
         if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "estimator %d needs a density grid (vpt_set_density_grid)", m->estimator);
+        if (m->estimator == VPT_HETERO_CHROMATIC) {
+            if (ctx->h_grid.emit)  /* the emitting track's weight under a hero channel is not worked out */
+                return vpt_fail(VPT_E_UNSUPPORTED, "estimator %d does not score an emission grid (estimators 10 and 11 do)",
+                                m->estimator);
+            const ChromaCoef c = chroma_coef(ctx, m->sigma_a, m->sigma_s);
+            for (int k = 0; k < 3; ++k)
+                if (!(c.st[k] > 0))  /* the hero's track and the weights divide by it */
+                    return vpt_fail(VPT_E_INVALID, "estimator %d: channel %d has no extinction (sigma_a * absorb + sigma_s * "
+                                    "scatter == 0; vpt_set_medium_colour)", m->estimator, k);
+            return VPT_OK;
+        }
         /* emission is scored on a delta track, which estimator 12 does not run and estimator 13 runs only in part */
         if ((m->estimator == VPT_HETERO_EQUIANGULAR || m->estimator == VPT_HETERO_MIS) && ctx->h_grid.emit)
             return vpt_fail(VPT_E_UNSUPPORTED, "estimator %d does not score an emission grid (estimators 10 and 11 do)",
@@ -536,9 +564,14 @@ static const vpt_hetero_unit& hetero_unit(bool tl, bool em)
 }
 static const vpt_hetero_eqa_unit& hetero_eqa_unit(bool tl) { return tl ? vpt_int_hetero_eqa_unit_tl : vpt_int_hetero_eqa_unit; }
 static const vpt_hetero_mis_unit& hetero_mis_unit(bool tl) { return tl ? vpt_int_hetero_mis_unit_tl : vpt_int_hetero_mis_unit; }
+static const vpt_hetero_chroma_unit& hetero_chroma_unit(bool tl)
+{
+    return tl ? vpt_int_hetero_chroma_unit_tl : vpt_int_hetero_chroma_unit;
+}
 
 /* estimators 10, 11 (by K.est: hetero_kernel / hetero_ratio_kernel), 12 (hetero_eqa_kernel; the majorant block plays no
- * part) and 13 (hetero_mis_kernel, with the context's track fraction) on the stream's queue word; counting mode and
+ * part), 13 (hetero_mis_kernel, with the context's track fraction) and 14 (hetero_chroma_kernel, with the coefficients
+ * of the context's medium colour) on the stream's queue word; counting mode and
  * VPT_SIMPLE_KERNEL=1: render_kernel_simple<K.est> */
 static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
 {
@@ -547,7 +580,11 @@ static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
     const vpt_hetero_unit& u = hetero_unit(g.interp != 0, g.emit != nullptr);
     const vpt_hetero_eqa_unit& ue = hetero_eqa_unit(g.interp != 0);
     const vpt_hetero_mis_unit& um = hetero_mis_unit(g.interp != 0);
+    const bool chroma = K.est == VPT_HETERO_CHROMATIC;
+    const vpt_hetero_chroma_unit& uc = hetero_chroma_unit(g.interp != 0);
+    const ChromaCoef cc = chroma_coef(ctx, K.sigma_a, K.sigma_s);
     if (K.counters || hetero_simple_kernel()) {
+        if (chroma) return uc.simple_launch(K, ctx->d_scene, lm, cc, stream);
         if (mis) return um.simple_launch(K, ctx->d_scene, lm, ctx->mis_fraction, stream);
         return eqa ? ue.simple_launch(K, ctx->d_scene, stream) : u.simple_launch(K, ctx->d_scene, lm, stream);
     }
@@ -557,7 +594,8 @@ static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
     if (rc) return rc;
     K.queue = sl->d_queue;
     HIP_OK(hipMemsetAsync(K.queue, 0, sizeof(unsigned), stream));
-    if (mis) rc = um.launch(ctx->device, K, ctx->d_scene, lm, ctx->mis_fraction, stream);
+    if (chroma) rc = uc.launch(ctx->device, K, ctx->d_scene, lm, cc, stream);
+    else if (mis) rc = um.launch(ctx->device, K, ctx->d_scene, lm, ctx->mis_fraction, stream);
     else rc = eqa ? ue.launch(ctx->device, K, ctx->d_scene, stream) : u.launch(ctx->device, K, ctx->d_scene, lm, stream);
     if (rc) return rc;
     return slot_done(sl, stream);
@@ -566,7 +604,7 @@ static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
 template <int EST, bool COUNT, int FB>
 static int launch_one(vpt_context* ctx, KParams K, hipStream_t stream)
 {
-    if constexpr (EST >= VPT_HETERO_FREE) {  /* the kernels of 10 and 11 live in vpt_hetero.hip, 12's in vpt_hetero_eqa.hip, 13's in vpt_hetero_mis.hip */
+    if constexpr (EST >= VPT_HETERO_FREE) {  /* the kernels of 10 and 11 live in vpt_hetero.hip, 12's in vpt_hetero_eqa.hip, 13's in vpt_hetero_mis.hip, 14's in vpt_hetero_chroma.hip */
         return launch_hetero(ctx, K, stream);
     } else {
         const DevScene* S = ctx->d_scene;
@@ -771,6 +809,7 @@ static int launch_render(vpt_context* ctx, KParams K, hipStream_t stream)
         VPT_LAUNCH_EST(11)
         VPT_LAUNCH_EST(12)
         VPT_LAUNCH_EST(13)
+        VPT_LAUNCH_EST(14)
     }
 #undef VPT_LAUNCH_EST
     return vpt_fail(VPT_E_INVALID, "unknown estimator %d", K.est);
@@ -1067,6 +1106,21 @@ int vpt_set_hetero_mis_fraction(vpt_context* ctx, double q)
     return VPT_OK;
 }
 
+int vpt_set_medium_colour(vpt_context* ctx, const double absorb[3], const double scatter[3])
+{
+    vpt_clear_error();
+    if (!ctx || !absorb || !scatter) return vpt_fail(VPT_E_INVALID, "vpt_set_medium_colour: NULL argument");
+    for (int k = 0; k < 3; ++k)
+        if (!is_finite(absorb[k]) || !is_finite(scatter[k]) || absorb[k] < 0 || scatter[k] < 0)
+            return vpt_fail(VPT_E_INVALID, "vpt_set_medium_colour: channel %d: absorb %g, scatter %g (finite, >= 0)", k,
+                            absorb[k], scatter[k]);
+    for (int k = 0; k < 3; ++k) {  /* kernel arguments of the next launch: nothing in flight reads them */
+        ctx->chroma_a[k] = absorb[k];
+        ctx->chroma_s[k] = scatter[k];
+    }
+    return VPT_OK;
+}
+
 int vpt_set_grid_interpolation(vpt_context* ctx, int mode)
 {
     vpt_clear_error();
@@ -1248,6 +1302,45 @@ int vpt_grid_mis_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, co
     return st.status("vpt_grid_mis_probe");
 }
 
+int vpt_grid_chroma_probe(vpt_context* ctx, double sigma_a, double sigma_s, const vpt_ray* rays, const double* tmax,
+                          const uint64_t* states, int n, int32_t* hero, double* t_coll, double* tau, double* w, uint32_t* steps,
+                          uint64_t* states_out)
+{
+    vpt_clear_error();
+    if (!ctx || !rays || !tmax || !states || !hero || !t_coll || !tau || !w || !steps || !states_out || n < 0)
+        return vpt_fail(VPT_E_INVALID, "vpt_grid_chroma_probe: bad arguments");
+    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "vpt_grid_chroma_probe: no density grid set (vpt_set_density_grid)");
+    if (!is_finite(sigma_a) || !is_finite(sigma_s) || sigma_a < 0 || sigma_s < 0)
+        return vpt_fail(VPT_E_INVALID, "vpt_grid_chroma_probe: sigma_a/sigma_s must be finite and >= 0");
+    const ChromaCoef cc = chroma_coef(ctx, sigma_a, sigma_s);
+    for (int k = 0; k < 3; ++k)
+        if (!(cc.st[k] > 0)) return vpt_fail(VPT_E_INVALID, "vpt_grid_chroma_probe: channel %d has no extinction", k);
+    if (n == 0) return VPT_OK;
+    HIP_OK(hipSetDevice(ctx->device));
+    Staging st;
+    const size_t nn = (size_t)n;
+    vpt_ray* dr = st.alloc<vpt_ray>(nn);
+    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn);
+    double* dtm = st.alloc<double>(nn);
+    double* dres = st.alloc<double>(5 * nn);  /* t_coll, tau and the three weights, one array behind the other */
+    int32_t* dh = st.alloc<int32_t>(nn);
+    uint32_t* dst = st.alloc<uint32_t>(nn);
+    st.up(dr, rays, nn);
+    st.up(ds, states, nn);
+    st.up(dtm, tmax, nn);
+    st.launch([&] {
+        hetero_chroma_unit(ctx->h_grid.interp != 0).grid_chroma_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, cc, dr, dtm, ds,
+                                                                             n, dres, dh, dst, dso);
+    });
+    st.down(t_coll, dres, nn);
+    st.down(tau, dres + nn, nn);
+    st.down(w, dres + 2 * nn, 3 * nn);  /* w[c * n + i] */
+    st.down(hero, dh, nn);
+    st.down(steps, dst, nn);
+    st.down(states_out, dso, nn);
+    return st.status("vpt_grid_chroma_probe");
+}
+
 int vpt_grid_emission_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
                             int n, double* t_coll, double* esum, uint64_t* states_out, uint32_t* steps)
 {
@@ -1399,6 +1492,10 @@ static int trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* ray
         case VPT_HETERO_MIS:
             hetero_mis_unit(g.interp != 0).trace_launch(dr, ds, n, mm, ctx->d_scene, ctx->d_grid, g.block > 0,
                                                         ctx->mis_fraction, dout, dso);
+            break;
+        case VPT_HETERO_CHROMATIC:
+            hetero_chroma_unit(g.interp != 0).trace_launch(dr, ds, n, mm, ctx->d_scene, ctx->d_grid, g.block > 0,
+                                                           chroma_coef(ctx, m->sigma_a, m->sigma_s), dout, dso);
             break;
         default: trace_batch_kernel<9><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         }

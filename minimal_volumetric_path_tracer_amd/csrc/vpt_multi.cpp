@@ -252,6 +252,17 @@ int vpt_multi_set_hetero_mis_fraction(vpt_multi* m, double q)
     return VPT_OK;
 }
 
+int vpt_multi_set_medium_colour(vpt_multi* m, const double absorb[3], const double scatter[3])
+{
+    vpt_clear_error();
+    if (!m) return vpt_fail(VPT_E_INVALID, "vpt_multi_set_medium_colour: NULL handle");
+    for (int g = 0; g < m->n; ++g) {  /* a refused value is refused by the first context, so all keep theirs */
+        int rc = vpt_set_medium_colour(m->ctx[g], absorb, scatter);
+        if (rc) return rc;
+    }
+    return VPT_OK;
+}
+
 int vpt_multi_set_emission_grid(vpt_multi* m, const float* eps, const double rgb[3])
 {
     vpt_clear_error();

@@ -23,7 +23,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (EXPLICIT_EQUIANGULAR, EXPLICIT_FREE, FB_F32, FB_F64, FREE_FLIGHT, HETERO_EQUIANGULAR, HETERO_FREE, HETERO_MIS, HETERO_RATIO, IMPLICIT_FREE, MIS_EQUIANGULAR,
+from ._lib import (EXPLICIT_EQUIANGULAR, EXPLICIT_FREE, FB_F32, FB_F64, FREE_FLIGHT, HETERO_EQUIANGULAR, HETERO_CHROMATIC, HETERO_FREE, HETERO_MIS, HETERO_RATIO, IMPLICIT_FREE, MIS_EQUIANGULAR,
                    RAY_DTYPE, RAY_MARCHING, RAY_MARCHING_EXPLICIT, RAY_MARCHING_GLOBAL, RAY_MARCHING_SA, SPHERE_DTYPE,
                    SURFACE_PT, check, lib)
 
@@ -33,7 +33,8 @@ ESTIMATORS = {"ff": FREE_FLIGHT, "free_flight": FREE_FLIGHT, "mis": MIS_EQUIANGU
               "ray_marching": RAY_MARCHING, "ray_marching_sa": RAY_MARCHING_SA, "ray_marching_global": RAY_MARCHING_GLOBAL,
               "ray_marching_explicit": RAY_MARCHING_EXPLICIT, "hetero": HETERO_FREE, "hetero_free": HETERO_FREE,
               "hetero_ratio": HETERO_RATIO, "hetero_equiangular": HETERO_EQUIANGULAR, "hetero_eqa": HETERO_EQUIANGULAR,
-              "hetero_mis": HETERO_MIS, "hetero_mis_equiangular": HETERO_MIS}
+              "hetero_mis": HETERO_MIS, "hetero_mis_equiangular": HETERO_MIS,
+              "hetero_chromatic": HETERO_CHROMATIC, "hetero_rgb": HETERO_CHROMATIC}
 
 
 def Sphere(r, p, c=(0, 0, 0), radiance=(0, 0, 0), material=0, eta=(0, 0, 0), kappa=(0, 0, 0), alpha=0.0) -> np.ndarray:
@@ -192,6 +193,45 @@ def grid_mis_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, light, states, 
     check(lib().vpt_grid_mis_probe_host(byref(d), r.ctypes.data, int(majorant_block), mode, float(sigma_t), float(q),
                                         ry.ctypes.data, t.ctypes.data, lp.ctypes.data, s.ctypes.data, len(ry),
                                         *[a.ctypes.data for a in c_order]))
+    return out
+
+
+def _colour_args(absorption, scattering) -> tuple[np.ndarray, np.ndarray]:
+    """the two float64 triples of a medium colour; anything that is not three numbers is VPT_E_INVALID"""
+    out = []
+    for name, v in (("absorption", absorption), ("scattering", scattering)):
+        a = np.ascontiguousarray(v, dtype=np.float64)
+        if a.shape != (3,):
+            raise _lib.VPTError(_lib.VPT_E_INVALID, f"{name}: three numbers (r, g, b), got shape {a.shape}")
+        out.append(a)
+    return out[0], out[1]
+
+
+def _chroma_probe_results(n):
+    """the output arrays of a chromatic probe in the C argument order; w is (3, n), a channel per row"""
+    hero, tc, tau, w = np.zeros(n, dtype=np.int32), np.zeros(n), np.zeros(n), np.zeros((3, n))
+    steps, so = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64)
+    return hero, tc, tau, w, steps, so
+
+
+def grid_chroma_probe_host(rho, lo, hi, sigma_a: float, sigma_s: float, rays, tmax, states, absorption=(1.0, 1.0, 1.0),
+                           scattering=(1.0, 1.0, 1.0), majorant_block: int = 0, interpolation: str = "nearest"):
+    """csrc/vpt_grid_chroma.h on the host (vpt_grid_chroma_probe_host, no GPU): one distance decision of estimator
+    "hetero_chromatic" per ray (unit direction) with surface distance tmax, from `states`, in a medium with
+    sa_c = sigma_a * absorption[c] and ss_c = sigma_s * scattering[c] per unit density.  Returns (hero, t_coll, tau, w,
+    steps, states): the hero channel (one draw; 0 and no draw where the three st_c are equal), the collision distance
+    of the track under st_hero (-1: none, NaN: step cap), the optical depth up to the collision (to tmax at "none"),
+    the per-channel weights as a (3, n) array -- w_c, which stands in the albedo's place, at a collision and ws_c at
+    "none" --, the track's tentative steps and the erand48 states after all draws."""
+    mode = _interp_mode(interpolation)
+    d, r = _grid_args(rho, lo, hi)
+    ry, t, s, _, _, _ = _probe_args(rays, tmax, states)
+    ca, cs = _colour_args(absorption, scattering)
+    sa, ss = float(sigma_a) * ca, float(sigma_s) * cs
+    out = _chroma_probe_results(len(ry))
+    check(lib().vpt_grid_chroma_probe_host(byref(d), r.ctypes.data, int(majorant_block), mode, sa.ctypes.data, ss.ctypes.data,
+                                           ry.ctypes.data, t.ctypes.data, s.ctypes.data, len(ry),
+                                           *[a.ctypes.data for a in out]))
     return out
 
 
@@ -355,6 +395,15 @@ class Tracer:
         the tracer: it survives grid and scene changes.  A value that is refused leaves the setting as it was."""
         check(lib().vpt_set_hetero_mis_fraction(self._ctx, float(q)))
 
+    def set_medium_colour(self, absorption=(1.0, 1.0, 1.0), scattering=(1.0, 1.0, 1.0)) -> None:
+        """The medium colour of estimator "hetero_chromatic": per colour channel the multipliers (r, g, b) of the
+        medium's sigma_a and of its sigma_s, each finite and >= 0 (default 1: a grey medium, estimator "hetero" bit
+        for bit).  Belongs to the tracer: it survives grid and scene changes, and no other estimator reads it.  A
+        value that is refused leaves the setting as it was; a channel whose absorption and scattering are both zero is
+        refused by the render."""
+        ca, cs = _colour_args(absorption, scattering)
+        check(lib().vpt_set_medium_colour(self._ctx, ca.ctypes.data, cs.ctypes.data))
+
     def set_grid_interpolation(self, interpolation: str) -> None:
         """How the density is read between the voxel centres: "nearest" (the default: constant per voxel) or
         "trilinear" (a smooth field, clamped at the border of the box; include/vpt.h vpt_set_grid_interpolation).
@@ -408,6 +457,15 @@ class Tracer:
         c_order, out = _mis_probe_results(len(ry))
         check(lib().vpt_grid_mis_probe(self._ctx, float(sigma_t), ry.ctypes.data, t.ctypes.data, lp.ctypes.data,
                                        s.ctypes.data, len(ry), *[a.ctypes.data for a in c_order]))
+        return out
+
+    def grid_chroma_probe(self, sigma_a: float, sigma_s: float, rays, tmax, states):
+        """grid_chroma_probe_host's quantities for the tracer's grid, majorant block, interpolation and medium colour,
+        computed on the GPU (vpt_grid_chroma_probe)."""
+        ry, t, s, _, _, _ = _probe_args(rays, tmax, states)
+        out = _chroma_probe_results(len(ry))
+        check(lib().vpt_grid_chroma_probe(self._ctx, float(sigma_a), float(sigma_s), ry.ctypes.data, t.ctypes.data,
+                                          s.ctypes.data, len(ry), *[a.ctypes.data for a in out]))
         return out
 
     # ---- main()'s pixel loop (src/rt.cpp:767-805) ----
@@ -674,6 +732,11 @@ class MultiTracer:
     def set_hetero_mis_fraction(self, q: float) -> None:
         """Tracer.set_hetero_mis_fraction on every rank's context."""
         check(lib().vpt_multi_set_hetero_mis_fraction(self._m, float(q)))
+
+    def set_medium_colour(self, absorption=(1.0, 1.0, 1.0), scattering=(1.0, 1.0, 1.0)) -> None:
+        """Tracer.set_medium_colour on every rank's context."""
+        ca, cs = _colour_args(absorption, scattering)
+        check(lib().vpt_multi_set_medium_colour(self._m, ca.ctypes.data, cs.ctypes.data))
 
     def set_majorant_block(self, block: int) -> None:
         """Tracer.set_majorant_block on every rank's context."""
