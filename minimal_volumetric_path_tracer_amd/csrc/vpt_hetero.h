@@ -307,38 +307,69 @@ struct HeteroSteps {
 
 struct KParams;  /* a render's launch parameters (vpt_render_simple.h) */
 
+/* estimator 14's per-channel coefficients per unit density, launch constants (vpt_hetero_chroma.h) */
+struct ChromaCoef {
+    double ss[3], st[3];
+};
+
 }  // namespace vpt
 
-/* What a code object of estimators 10 and 11 exports: its launches.  vpt_hetero.hip defines one table per unit, the four
- * units being the values of (TL, EM) -- nearest or trilinear lookup (the view's interp word), without or with the emission
- * grid -- and the caller picks the table in one place (vpt_kernels.hip hetero_unit).  lm: the grid behind the view has a
- * majorant grid (the kernel's LM instantiation). */
+/* What the estimators' launches differ in on the host, in one argument: each launch reads what its estimator takes */
+struct vpt_hetero_args {
+    bool lm;                    /* the grid behind the view has a majorant grid (the kernel's LM instantiation);
+                                 * estimator 12, where nothing tracks, ignores it */
+    double q;                   /* estimator 13: the context's track fraction */
+    vpt::ChromaCoef c;          /* estimator 14: the launch's coefficients */
+    unsigned long long* stats;  /* estimator 10's per-sample call: vpt_debug_hetero_steps' two counters, else NULL */
+};
+
+/* What a code object of the density-grid estimators exports: its launches.  One table per unit -- vpt_hetero.hip's four
+ * are the values of (TL, EM), nearest or trilinear lookup (the view's interp word) without or with the emission grid;
+ * estimator 12's, 13's and 14's units the two values of TL -- and the caller picks the table in one place (vpt_kernels.hip
+ * hetero_unit).  A probe the unit does not hold is NULL. */
 struct vpt_hetero_unit {
-    /* the persistent-wave render kernel of estimator 10 or 11 (K.est), enqueued on `stream` (the caller owns the queue
-     * word K.queue and has zeroed it in stream order) */
-    int (*launch)(int device, const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
-    /* render_kernel_simple<10 or 11> for the same render; counting iff K.counters (vpt_count_work's device counters) is set */
-    int (*simple_launch)(const vpt::KParams& K, const DevScene* S, bool lm, void* stream);
-    /* the per-sample call (est: 10 or 11) and, below, the probes on device arrays, default stream (the caller reads
-     * hipGetLastError); stats: vpt_debug_hetero_steps' two counters (estimator 10), else NULL; steps: a probe's per-ray
-     * tentative steps, else NULL */
+    /* the persistent-wave render kernel of the unit's estimator (K.est where it holds two), enqueued on `stream` (the
+     * caller owns the queue word K.queue and has zeroed it in stream order) */
+    int (*launch)(int device, const vpt::KParams& K, const DevScene* S, const vpt_hetero_args& a, void* stream);
+    /* render_kernel_simple<K.est> for the same render; counting iff K.counters (vpt_count_work's device counters) is set */
+    int (*simple_launch)(const vpt::KParams& K, const DevScene* S, const vpt_hetero_args& a, void* stream);
+    /* the per-sample call of estimator est and, below, the probes on device arrays, default stream (the caller reads
+     * hipGetLastError); steps: a probe's per-ray tentative steps, else NULL; light: 3 doubles per ray */
     void (*trace_launch)(int est, const vpt_ray* rays, const uint64_t* states, int n, const vpt::Medium& m, const DevScene* S,
-                         const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states, unsigned long long* stats);
-    /* the two grid probes: the EM = false units', NULL in the others */
+                         const vpt_grid_view* grid, const vpt_hetero_args& a, double* out, uint64_t* out_states);
+    /* the two grid probes: vpt_hetero.hip's EM = false units' */
     void (*grid_probe_launch)(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays, const double* tmax,
                               const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out,
                               uint32_t* steps);
     void (*grid_ratio_probe_launch)(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
                                     const double* tmax, const uint64_t* states, int n, double* that, uint64_t* states_out,
                                     uint32_t* steps);
-    /* the emitting track's probe: the EM = true units', NULL in the others */
+    /* the emitting track's probe: vpt_hetero.hip's EM = true units' */
     void (*grid_emission_probe_launch)(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays,
                                        const double* tmax, const uint64_t* states, int n, double* t_coll, double* esum,
                                        uint64_t* states_out, uint32_t* steps);
+    /* estimator 12's */
+    void (*grid_eqa_probe_launch)(const vpt_grid_view* grid, double sigma_t, const vpt_ray* rays, const double* tmax,
+                                  const double* light, const uint64_t* states, int n, double* psurf, double* dist, double* pdf,
+                                  double* T, double* rho_t, uint64_t* states_out);
+    /* estimator 13's; res: six arrays of n doubles, one behind the other (psurf, dist, pdf, pe, T, rho_t) */
+    void (*grid_mis_probe_launch)(const vpt_grid_view* grid, bool lm, double sigma_t, double q, const vpt_ray* rays,
+                                  const double* tmax, const double* light, const uint64_t* states, int n, double* res,
+                                  int32_t* strategy, uint32_t* steps, uint64_t* states_out);
+    /* estimator 14's; res: five arrays of n doubles, one behind the other (t_coll, tau, w[0], w[1], w[2]) */
+    void (*grid_chroma_probe_launch)(const vpt_grid_view* grid, bool lm, const vpt::ChromaCoef& c, const vpt_ray* rays,
+                                     const double* tmax, const uint64_t* states, int n, double* res, int32_t* hero,
+                                     uint32_t* steps, uint64_t* states_out);
 };
-extern const vpt_hetero_unit vpt_int_hetero_unit;        /* vpt_hetero.hip: TL = false, EM = false */
-extern const vpt_hetero_unit vpt_int_hetero_unit_tl;     /* vpt_hetero_tl.hip: TL = true */
-extern const vpt_hetero_unit vpt_int_hetero_unit_em;     /* vpt_hetero_em.hip: EM = true */
-extern const vpt_hetero_unit vpt_int_hetero_unit_em_tl;  /* vpt_hetero_em_tl.hip: both */
+extern const vpt_hetero_unit vpt_int_hetero_unit;            /* vpt_hetero.hip: TL = false, EM = false */
+extern const vpt_hetero_unit vpt_int_hetero_unit_tl;         /* vpt_hetero_tl.hip: TL = true, the view's interp == 1 */
+extern const vpt_hetero_unit vpt_int_hetero_unit_em;         /* vpt_hetero_em.hip: EM = true */
+extern const vpt_hetero_unit vpt_int_hetero_unit_em_tl;      /* vpt_hetero_em_tl.hip: both */
+extern const vpt_hetero_unit vpt_int_hetero_eqa_unit;        /* vpt_hetero_eqa.hip, and _tl: vpt_hetero_eqa_tl.hip */
+extern const vpt_hetero_unit vpt_int_hetero_eqa_unit_tl;
+extern const vpt_hetero_unit vpt_int_hetero_mis_unit;        /* vpt_hetero_mis.hip, vpt_hetero_mis_tl.hip */
+extern const vpt_hetero_unit vpt_int_hetero_mis_unit_tl;
+extern const vpt_hetero_unit vpt_int_hetero_chroma_unit;     /* vpt_hetero_chroma.hip, vpt_hetero_chroma_tl.hip */
+extern const vpt_hetero_unit vpt_int_hetero_chroma_unit_tl;
 
 #endif

@@ -8,7 +8,7 @@
  * hetero_kernel: the persistent-wave loop of vpt_wave.h on estimator 10's steps (HeteroSteps, vpt_hetero.h).  A
  * lane owns one pixel and runs that pixel's samples strictly in order (acc = L + acc, then * (1 / (double)spp)),
  * so the image is render_kernel_simple<10>'s bit for bit.  What the kernel adds to the loop is the prologue
- * that stages the grid in LDS.
+ * that stages the grid in LDS (stage_grid_lds, vpt_hetero_lds.h: one function for every density-grid kernel).
  *
  * Density reads: a grid of at most 64 KiB (16 384 voxels) is staged in LDS once per workgroup
  * (VPT_HETERO_LDS, on by default); a larger one is read from global memory, where the L2 holds the grids of
@@ -34,31 +34,19 @@
 #include <hip/hip_runtime.h>
 
 #include "vpt_wave.h"
+#include "vpt_hetero_lds.h"
 #include "vpt_hetero_launch.h"
 
-#ifndef VPT_HETERO_LDS
-#define VPT_HETERO_LDS 1
-#endif
-#define VPT_HETERO_LDS_BYTES 65536
-#ifndef VPT_HETERO_TL
-#define VPT_HETERO_TL 0
-#endif
 #ifndef VPT_HETERO_EM
 #define VPT_HETERO_EM 0
 #endif
-#if VPT_HETERO_EM && VPT_HETERO_TL
+#if VPT_HETERO_EM  /* the emission units' suffixes: vpt_hetero_lds.h's VPT_HX knows the interpolation alone */
+#undef VPT_HX
+#if VPT_HETERO_TL
 #define VPT_HX(name) name##_em_tl
-#elif VPT_HETERO_EM
-#define VPT_HX(name) name##_em
-#elif VPT_HETERO_TL
-#define VPT_HX(name) name##_tl
 #else
-#define VPT_HX(name) name
+#define VPT_HX(name) name##_em
 #endif
-/* with local majorants: the majorant grid is staged in what the density left of the LDS budget -- all of it
- * where the density does not fit (DESIGN.md section 4 has the timing that decided the default) */
-#ifndef VPT_HETERO_LDS_MAJ
-#define VPT_HETERO_LDS_MAJ 1
 #endif
 
 namespace vpt {
@@ -67,68 +55,21 @@ template <bool COUNT, int FB, bool LM, bool TL, bool EM = false>
 __global__ __launch_bounds__(256, 2) void hetero_kernel(KParams P, const DevScene* __restrict__ S)
 {
     using TP = GridTrT<TL, EM>;
-    /* the view lives in the steps object from the start: the walkers take its address, so a copy made after the
-     * prologue is a second stack object (416 against 288 bytes of scratch, 9 against 4 spilled VGPRs) */
+    /* the view lives in the steps object from the start (vpt_hetero_lds.h says why) */
     HeteroSteps<LM, TL, TP, EM> st{TP::template load<LM>(P.grid)};
-    [[maybe_unused]] auto& G = st.tp.G;
-#if VPT_HETERO_LDS
-    __shared__ float lds_rho[VPT_HETERO_LDS_BYTES / sizeof(float)];
-    {
-        const int64_t nv = (int64_t)G.n[0] * G.n[1] * G.n[2];
-        if (nv <= (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float))) {  /* workgroup-uniform */
-            for (int k = threadIdx.x; k < (int)nv; k += blockDim.x) lds_rho[k] = G.rho[k];
-            __syncthreads();
-            G.rho = lds_rho;
-        }
-#if VPT_HETERO_LDS_MAJ
-        if (LM) {  /* the majorant grid goes into what the density left of the budget */
-            const int64_t cap = (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float));
-            const int64_t used = nv <= cap ? nv : 0;
-            const int64_t nbv = (int64_t)G.nb[0] * G.nb[1] * G.nb[2];
-            if (nbv <= cap - used) {  /* workgroup-uniform */
-                for (int k = threadIdx.x; k < (int)nbv; k += blockDim.x) lds_rho[used + k] = G.maj[k];
-                __syncthreads();
-                G.maj = lds_rho + used;
-            }
-        }
-#endif
-    }
-#endif
+    stage_grid_lds<LM>(st.tp.G);
     wave_render<HeteroSteps<LM, TL, TP, EM>, COUNT, FB>(P, S, st);
 }
 
-/* estimator 11 (VPT_HETERO_RATIO): hetero_kernel on the ratio-tracking policy.  The prologue is restated, not shared:
- * with estimator 10's kernel calling a common body template its code moves (commuted v_mul_f64 operands, swapped
+/* estimator 11 (VPT_HETERO_RATIO): hetero_kernel on the ratio-tracking policy.  A kernel of its own, three lines as it
+ * is: with estimator 10's kernel calling a common body template its code moves (commuted v_mul_f64 operands, swapped
  * v_add_f64 pairs, up to three instructions more or fewer), and that kernel is to stay what it was */
 template <bool COUNT, int FB, bool LM, bool TL, bool EM = false>
 __global__ __launch_bounds__(256, 2) void hetero_ratio_kernel(KParams P, const DevScene* __restrict__ S)
 {
     using TP = GridRatioTr<LM, TL, EM>;
     HeteroSteps<LM, TL, TP, EM> st{TP::template load<LM>(P.grid)};
-    [[maybe_unused]] auto& G = st.tp.G;
-#if VPT_HETERO_LDS
-    __shared__ float lds_rho[VPT_HETERO_LDS_BYTES / sizeof(float)];
-    {
-        const int64_t nv = (int64_t)G.n[0] * G.n[1] * G.n[2];
-        if (nv <= (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float))) {  /* workgroup-uniform */
-            for (int k = threadIdx.x; k < (int)nv; k += blockDim.x) lds_rho[k] = G.rho[k];
-            __syncthreads();
-            G.rho = lds_rho;
-        }
-#if VPT_HETERO_LDS_MAJ
-        if (LM) {  /* the majorant grid goes into what the density left of the budget */
-            const int64_t cap = (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float));
-            const int64_t used = nv <= cap ? nv : 0;
-            const int64_t nbv = (int64_t)G.nb[0] * G.nb[1] * G.nb[2];
-            if (nbv <= cap - used) {  /* workgroup-uniform */
-                for (int k = threadIdx.x; k < (int)nbv; k += blockDim.x) lds_rho[used + k] = G.maj[k];
-                __syncthreads();
-                G.maj = lds_rho + used;
-            }
-        }
-#endif
-    }
-#endif
+    stage_grid_lds<LM>(st.tp.G);
     wave_render<HeteroSteps<LM, TL, TP, EM>, COUNT, FB>(P, S, st);
 }
 
@@ -259,12 +200,13 @@ static int ratio_simple_launch(const KParams& K, const DevScene* S, bool lm, voi
 static int ratio_launch(int device, const KParams& K, const DevScene* S, bool lm, void* stream);
 
 static void trace_launch(int est, const vpt_ray* rays, const uint64_t* states, int n, const Medium& m, const DevScene* S,
-                         const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states, unsigned long long* stats)
+                         const vpt_grid_view* grid, const vpt_hetero_args& a, double* out, uint64_t* out_states)
 {
-    if (est == VPT_HETERO_RATIO) return ratio_trace_launch(rays, states, n, m, S, grid, lm, out, out_states);
+    if (est == VPT_HETERO_RATIO) return ratio_trace_launch(rays, states, n, m, S, grid, a.lm, out, out_states);
     const dim3 g = vpt_ray_grid(n), b(256);
-    if (lm) trace_batch_hetero_kernel<true, TLU, EMU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states, stats);
-    else trace_batch_hetero_kernel<false, TLU, EMU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states, stats);
+    with_flags([&](auto lmc) {
+        trace_batch_hetero_kernel<decltype(lmc)::value, TLU, EMU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states, a.stats);
+    }, a.lm);
 }
 
 #if VPT_HETERO_EM
@@ -273,8 +215,9 @@ static void grid_emission_probe_launch(const vpt_grid_view* grid, bool lm, doubl
                                        uint64_t* states_out, uint32_t* steps)
 {
     const dim3 g = vpt_ray_grid(n), b(256);
-    if (lm) grid_emission_probe_kernel<true, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, t_coll, esum, states_out, steps);
-    else grid_emission_probe_kernel<false, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, t_coll, esum, states_out, steps);
+    with_flags([&](auto lmc) {
+        grid_emission_probe_kernel<decltype(lmc)::value, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, t_coll, esum, states_out, steps);
+    }, lm);
 }
 #else
 static void grid_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_t, const vpt_ray* rays, const double* tmax,
@@ -282,30 +225,34 @@ static void grid_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_t
                               uint32_t* steps)
 {
     const dim3 g = vpt_ray_grid(n), b(256);
-    if (lm) grid_probe_kernel<true, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, steps);
-    else grid_probe_kernel<false, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, steps);
+    with_flags([&](auto lmc) {
+        grid_probe_kernel<decltype(lmc)::value, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, tau, t_coll, states_out, steps);
+    }, lm);
 }
 #endif
 
 template <int EST>
 static int simple_launch_of(const KParams& K, const DevScene* S, bool lm, void* stream)
 {
-    return with_flags([&](auto lmc) { return vpt_simple_launch<EST, decltype(lmc)::value, TLU, EMU>(K, S, stream); }, lm);
+    return with_flags([&](auto lmc, auto count, auto f32) {
+        return vpt_simple_launch(render_kernel_simple<EST, decltype(count)::value, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU, EMU>,
+                                 K, S, stream);
+    }, lm, K.counters != nullptr, K.fb == VPT_FB_F32);
 }
 
-static int simple_launch(const KParams& K, const DevScene* S, bool lm, void* stream)
+static int simple_launch(const KParams& K, const DevScene* S, const vpt_hetero_args& a, void* stream)
 {
-    if (K.est == VPT_HETERO_RATIO) return ratio_simple_launch(K, S, lm, stream);
-    return simple_launch_of<VPT_HETERO_FREE>(K, S, lm, stream);
+    if (K.est == VPT_HETERO_RATIO) return ratio_simple_launch(K, S, a.lm, stream);
+    return simple_launch_of<VPT_HETERO_FREE>(K, S, a.lm, stream);
 }
 
-static int launch(int device, const KParams& K, const DevScene* S, bool lm, void* stream)
+static int launch(int device, const KParams& K, const DevScene* S, const vpt_hetero_args& a, void* stream)
 {
-    if (K.est == VPT_HETERO_RATIO) return ratio_launch(device, K, S, lm, stream);
+    if (K.est == VPT_HETERO_RATIO) return ratio_launch(device, K, S, a.lm, stream);
     return with_flags([&](auto lmc, auto f32) {
         return vpt_persistent_launch(hetero_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU, EMU>,
                                      "hetero_kernel", device, K, S, stream);
-    }, lm, K.fb == VPT_FB_F32);
+    }, a.lm, K.fb == VPT_FB_F32);
 }
 
 /* ---- estimator 11 ---- */
@@ -313,8 +260,9 @@ static void ratio_trace_launch(const vpt_ray* rays, const uint64_t* states, int 
                                const vpt_grid_view* grid, bool lm, double* out, uint64_t* out_states)
 {
     const dim3 g = vpt_ray_grid(n), b(256);
-    if (lm) trace_batch_hetero_ratio_kernel<true, TLU, EMU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states);
-    else trace_batch_hetero_ratio_kernel<false, TLU, EMU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states);
+    with_flags([&](auto lmc) {
+        trace_batch_hetero_ratio_kernel<decltype(lmc)::value, TLU, EMU><<<g, b>>>(rays, states, n, m, S, grid, out, out_states);
+    }, lm);
 }
 
 #if !VPT_HETERO_EM
@@ -323,8 +271,9 @@ static void grid_ratio_probe_launch(const vpt_grid_view* grid, bool lm, double s
                                     uint32_t* steps)
 {
     const dim3 g = vpt_ray_grid(n), b(256);
-    if (lm) grid_ratio_probe_kernel<true, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, that, states_out, steps);
-    else grid_ratio_probe_kernel<false, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, that, states_out, steps);
+    with_flags([&](auto lmc) {
+        grid_ratio_probe_kernel<decltype(lmc)::value, TLU><<<g, b>>>(grid, sigma_t, rays, tmax, states, n, that, states_out, steps);
+    }, lm);
 }
 #endif
 
@@ -341,11 +290,11 @@ static int ratio_launch(int device, const KParams& K, const DevScene* S, bool lm
     }, lm, K.fb == VPT_FB_F32);
 }
 
-/* what the unit exports: its launches by slot; the probes a unit does not hold are NULL.  Host pass only: a const object
- * with a constant initialiser is emitted for the device as well, and these are host functions */
+/* what the unit exports: its launches by slot.  Host pass only: a const object with a constant initialiser is emitted for
+ * the device as well, and these are host functions */
 #if defined(__HIP_DEVICE_COMPILE__)
 #elif VPT_HETERO_EM
 const vpt_hetero_unit VPT_HX(vpt_int_hetero_unit) = {launch, simple_launch, trace_launch, nullptr, nullptr, grid_emission_probe_launch};
 #else
-const vpt_hetero_unit VPT_HX(vpt_int_hetero_unit) = {launch, simple_launch, trace_launch, grid_probe_launch, grid_ratio_probe_launch, nullptr};
+const vpt_hetero_unit VPT_HX(vpt_int_hetero_unit) = {launch, simple_launch, trace_launch, grid_probe_launch, grid_ratio_probe_launch};
 #endif

@@ -32,11 +32,6 @@
 
 namespace vpt {
 
-/* the per-channel coefficients per unit density, launch constants */
-struct ChromaCoef {
-    double ss[3], st[3];
-};
-
 /* the grid's transmittance per channel as the TP policy of mis_v2 / single_scattering: GridTrT with a dv3 in the
  * scalar's place.  The helpers' sigma_t argument is not read: the policy holds the three extinctions */
 template <bool TL>
@@ -218,20 +213,5 @@ struct HeteroChromaSteps {
 };
 
 }  // namespace vpt
-
-/* What a code object of estimator 14 exports, as vpt_hetero_mis_unit is for estimator 13; lm: the grid behind the view has
- * a majorant grid (the kernel's LM instantiation); c: the launch's coefficients.  The probe's result arrays: five doubles
- * per ray in res (t_coll, tau, w[0], w[1], w[2], one array of n behind the other), hero and steps */
-struct vpt_hetero_chroma_unit {
-    int (*launch)(int device, const vpt::KParams& K, const DevScene* S, bool lm, const vpt::ChromaCoef& c, void* stream);
-    int (*simple_launch)(const vpt::KParams& K, const DevScene* S, bool lm, const vpt::ChromaCoef& c, void* stream);
-    void (*trace_launch)(const vpt_ray* rays, const uint64_t* states, int n, const vpt::Medium& m, const DevScene* S,
-                         const vpt_grid_view* grid, bool lm, const vpt::ChromaCoef& c, double* out, uint64_t* out_states);
-    void (*grid_chroma_probe_launch)(const vpt_grid_view* grid, bool lm, const vpt::ChromaCoef& c, const vpt_ray* rays,
-                                     const double* tmax, const uint64_t* states, int n, double* res, int32_t* hero,
-                                     uint32_t* steps, uint64_t* states_out);
-};
-extern const vpt_hetero_chroma_unit vpt_int_hetero_chroma_unit;     /* vpt_hetero_chroma.hip: TL = false */
-extern const vpt_hetero_chroma_unit vpt_int_hetero_chroma_unit_tl;  /* vpt_hetero_chroma_tl.hip: TL = true, the view's interp == 1 */
 
 #endif

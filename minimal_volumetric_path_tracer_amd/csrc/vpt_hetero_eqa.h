@@ -166,19 +166,4 @@ struct HeteroEqaSteps {
 
 }  // namespace vpt
 
-/* What a code object of estimator 12 exports, as vpt_hetero_unit is for estimators 10 and 11: the persistent-wave kernel
- * (the caller owns the queue word K.queue), render_kernel_simple<12> (counting iff K.counters is set), the per-sample
- * call and the probe on device arrays (default stream; the caller reads hipGetLastError).  light: 3 doubles per ray */
-struct vpt_hetero_eqa_unit {
-    int (*launch)(int device, const vpt::KParams& K, const DevScene* S, void* stream);
-    int (*simple_launch)(const vpt::KParams& K, const DevScene* S, void* stream);
-    void (*trace_launch)(const vpt_ray* rays, const uint64_t* states, int n, const vpt::Medium& m, const DevScene* S,
-                         const vpt_grid_view* grid, double* out, uint64_t* out_states);
-    void (*grid_eqa_probe_launch)(const vpt_grid_view* grid, double sigma_t, const vpt_ray* rays, const double* tmax,
-                                  const double* light, const uint64_t* states, int n, double* psurf, double* dist, double* pdf,
-                                  double* T, double* rho_t, uint64_t* states_out);
-};
-extern const vpt_hetero_eqa_unit vpt_int_hetero_eqa_unit;     /* vpt_hetero_eqa.hip: TL = false */
-extern const vpt_hetero_eqa_unit vpt_int_hetero_eqa_unit_tl;  /* vpt_hetero_eqa_tl.hip: TL = true, the view's interp == 1 */
-
 #endif

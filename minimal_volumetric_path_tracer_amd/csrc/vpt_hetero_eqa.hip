@@ -4,31 +4,19 @@
  *
  * hetero_eqa_kernel: the persistent-wave loop of vpt_wave.h on estimator 12's steps (HeteroEqaSteps).  A lane owns one
  * pixel and runs that pixel's samples strictly in order, so the image is render_kernel_simple<12>'s bit for bit.  The
- * prologue that stages a grid of at most 64 KiB in LDS is vpt_hetero.hip's, restated as estimator 11 restated it;
- * there is no majorant grid to stage, because nothing tracks.
+ * prologue that stages a grid of at most 64 KiB in LDS is stage_grid_lds (vpt_hetero_lds.h) with LM = false: there is
+ * no majorant grid to stage, because nothing tracks.
  *
  * Trilinear interpolation: the unit instantiates one value of TL, VPT_HETERO_TL.  Compiled as it stands (0) it holds the
- * nearest-lookup kernels and exports their launches as the table vpt_int_hetero_eqa_unit (vpt_hetero_eqa.h);
+ * nearest-lookup kernels and exports their launches as the table vpt_int_hetero_eqa_unit (vpt_hetero.h);
  * vpt_hetero_eqa_tl.hip includes this file with VPT_HETERO_TL = 1 and exports vpt_int_hetero_eqa_unit_tl.  The launches
  * are static; their host side is vpt_hetero_launch.h's, shared with vpt_hetero.hip.
  */
 #include <hip/hip_runtime.h>
 
 #include "vpt_wave.h"
+#include "vpt_hetero_lds.h"
 #include "vpt_hetero_launch.h"
-
-#ifndef VPT_HETERO_LDS
-#define VPT_HETERO_LDS 1
-#endif
-#define VPT_HETERO_LDS_BYTES 65536
-#ifndef VPT_HETERO_TL
-#define VPT_HETERO_TL 0
-#endif
-#if VPT_HETERO_TL
-#define VPT_HX(name) name##_tl
-#else
-#define VPT_HX(name) name
-#endif
 
 namespace vpt {
 
@@ -36,20 +24,9 @@ template <bool COUNT, int FB, bool TL>
 __global__ __launch_bounds__(256, 2) void hetero_eqa_kernel(KParams P, const DevScene* __restrict__ S)
 {
     using TP = GridTrT<TL>;
-    /* the view lives in the steps object from the start, as in hetero_kernel: the walkers take its address */
+    /* the view lives in the steps object from the start (vpt_hetero_lds.h says why) */
     HeteroEqaSteps<TL> st{TP::template load<false>(P.grid)};
-    [[maybe_unused]] auto& G = st.tp.G;
-#if VPT_HETERO_LDS
-    __shared__ float lds_rho[VPT_HETERO_LDS_BYTES / sizeof(float)];
-    {
-        const int64_t nv = (int64_t)G.n[0] * G.n[1] * G.n[2];
-        if (nv <= (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float))) {  /* workgroup-uniform */
-            for (int k = threadIdx.x; k < (int)nv; k += blockDim.x) lds_rho[k] = G.rho[k];
-            __syncthreads();
-            G.rho = lds_rho;
-        }
-    }
-#endif
+    stage_grid_lds<false>(st.tp.G);
     wave_render<HeteroEqaSteps<TL>, COUNT, FB>(P, S, st);
 }
 
@@ -108,9 +85,9 @@ __global__ __launch_bounds__(256) void grid_eqa_probe_kernel(const vpt_grid_view
 
 }  // namespace
 
-/* the unit's launches, the slots of vpt_hetero_eqa_unit (vpt_hetero_eqa.h) */
-static void trace_launch(const vpt_ray* rays, const uint64_t* states, int n, const Medium& m, const DevScene* S,
-                         const vpt_grid_view* grid, double* out, uint64_t* out_states)
+/* the unit's launches, the slots of vpt_hetero_unit (vpt_hetero.h); estimator 12 takes nothing of vpt_hetero_args */
+static void trace_launch(int, const vpt_ray* rays, const uint64_t* states, int n, const Medium& m, const DevScene* S,
+                         const vpt_grid_view* grid, const vpt_hetero_args&, double* out, uint64_t* out_states)
 {
     trace_batch_hetero_eqa_kernel<TLU><<<vpt_ray_grid(n), dim3(256)>>>(rays, states, n, m, S, grid, out, out_states);
 }
@@ -123,12 +100,15 @@ static void grid_eqa_probe_launch(const vpt_grid_view* grid, double sigma_t, con
                                                                 T, rho_t, states_out);
 }
 
-static int simple_launch(const KParams& K, const DevScene* S, void* stream)
+static int simple_launch(const KParams& K, const DevScene* S, const vpt_hetero_args&, void* stream)
 {
-    return vpt_simple_launch<VPT_HETERO_EQUIANGULAR, false, TLU, false>(K, S, stream);
+    return with_flags([&](auto count, auto f32) {
+        return vpt_simple_launch(render_kernel_simple<VPT_HETERO_EQUIANGULAR, decltype(count)::value, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, false, TLU, false>,
+                                 K, S, stream);
+    }, K.counters != nullptr, K.fb == VPT_FB_F32);
 }
 
-static int launch(int device, const KParams& K, const DevScene* S, void* stream)
+static int launch(int device, const KParams& K, const DevScene* S, const vpt_hetero_args&, void* stream)
 {
     return with_flags([&](auto f32) {
         return vpt_persistent_launch(hetero_eqa_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, TLU>,
@@ -139,5 +119,5 @@ static int launch(int device, const KParams& K, const DevScene* S, void* stream)
 /* what the unit exports.  Host pass only: a const object with a constant initialiser is emitted for the device as well,
  * and these are host functions */
 #if !defined(__HIP_DEVICE_COMPILE__)
-const vpt_hetero_eqa_unit VPT_HX(vpt_int_hetero_eqa_unit) = {launch, simple_launch, trace_launch, grid_eqa_probe_launch};
+const vpt_hetero_unit VPT_HX(vpt_int_hetero_eqa_unit) = {launch, simple_launch, trace_launch, nullptr, nullptr, nullptr, grid_eqa_probe_launch};
 #endif

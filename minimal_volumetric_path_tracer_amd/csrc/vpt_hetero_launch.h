@@ -1,7 +1,8 @@
 /*
- * vpt_hetero_launch.h -- the host side of a launch, shared by the density-grid units (vpt_hetero.hip, vpt_hetero_eqa.hip
- * and the units that include them) and vpt_kernels.hip.  Host code only: it names kernels and launches them, and holds
- * no __global__ or __device__ function, so including it leaves a unit's code object what it was.
+ * vpt_hetero_launch.h -- the host side of a launch, shared by the density-grid units (vpt_hetero.hip, vpt_hetero_eqa.hip,
+ * vpt_hetero_mis.hip, vpt_hetero_chroma.hip and the units that include them) and vpt_kernels.hip.  Host code only: it
+ * names kernels and launches them, and holds no __global__ or __device__ function, so including it leaves a unit's code
+ * object what it was (what the units share on the device is vpt_hetero_lds.h's).
  */
 #ifndef VPT_HETERO_LAUNCH_H
 #define VPT_HETERO_LAUNCH_H
@@ -13,14 +14,14 @@
 #include "vpt_render_simple.h"
 #include "vpt_internal.h"
 
-/* run-time flags as compile-time constants: f(std::bool_constant<flag>{}...) */
+/* run-time flags as compile-time constants: f(std::bool_constant<flag>{}...), whatever f returns */
 template <class F>
-static int with_flags(F f)
+static auto with_flags(F f)
 {
     return f();
 }
 template <class F, class... Bools>
-static int with_flags(F f, bool flag, Bools... rest)
+static auto with_flags(F f, bool flag, Bools... rest)
 {
     if (flag) return with_flags([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
     return with_flags([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
@@ -48,32 +49,32 @@ static inline int vpt_wave_blocks(int blocks, const vpt::KParams& K)
     return blocks < 1 ? 1 : blocks;
 }
 
-/* a persistent-wave kernel on as many workgroups as the device holds, clamped as above; `name` stands in the message */
-static int vpt_persistent_launch(void (*kern)(vpt::KParams, const DevScene*), const char* name, int device,
-                                 const vpt::KParams& K, const DevScene* S, void* stream)
+/* a persistent-wave kernel on as many workgroups as the device holds, clamped as above; `name` stands in the message.
+ * a: the kernel's arguments behind (K, S) -- none, estimator 13's track fraction, estimator 14's coefficients */
+template <class Kern, class... A>
+static int vpt_persistent_launch(Kern kern, const char* name, int device, const vpt::KParams& K, const DevScene* S,
+                                 void* stream, const A&... a)
 {
     int blocks = 0;
     hipError_t e = vpt_resident_blocks(kern, 256, device, &blocks);
     if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "%s: %s", name, hipGetErrorString(e));
-    kern<<<dim3((unsigned)vpt_wave_blocks(blocks, K)), dim3(256), 0, (hipStream_t)stream>>>(K, S);
+    kern<<<dim3((unsigned)vpt_wave_blocks(blocks, K)), dim3(256), 0, (hipStream_t)stream>>>(K, S, a...);
     e = hipGetLastError();
     if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "%s launch: %s", name, hipGetErrorString(e));
     return (int)VPT_OK;
 }
 
-/* render_kernel_simple<EST> (vpt_render_simple.h), one lane per pixel: counting mode (K.counters != NULL) and
- * VPT_SIMPLE_KERNEL=1 */
-template <int EST, bool LM, bool TL, bool EM>
-static int vpt_simple_launch(const vpt::KParams& K, const DevScene* S, void* stream)
+/* kern: the render_kernel_simple<K.est, ...> (vpt_render_simple.h, or a unit's overload of it) of a render, one lane per
+ * pixel: counting mode (K.counters != NULL) and VPT_SIMPLE_KERNEL=1; a: as above, and what picks the overload */
+template <class... A>
+static int vpt_simple_launch(void (*kern)(vpt::KParams, const DevScene*, A...), const vpt::KParams& K, const DevScene* S,
+                             void* stream, const A&... a)
 {
-    return with_flags([&](auto count, auto f32) {
-        constexpr int FB = decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64;
-        dim3 grid((unsigned)((K.w + 15) / 16), (unsigned)((K.shard_rows + 15) / 16));
-        render_kernel_simple<EST, decltype(count)::value, FB, LM, TL, EM><<<grid, dim3(256), 0, (hipStream_t)stream>>>(K, S);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "render_kernel_simple<%d> launch: %s", EST, hipGetErrorString(e));
-        return (int)VPT_OK;
-    }, K.counters != nullptr, K.fb == VPT_FB_F32);
+    dim3 grid((unsigned)((K.w + 15) / 16), (unsigned)((K.shard_rows + 15) / 16));
+    kern<<<grid, dim3(256), 0, (hipStream_t)stream>>>(K, S, a...);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "render_kernel_simple<%d> launch: %s", (int)K.est, hipGetErrorString(e));
+    return (int)VPT_OK;
 }
 
 #endif

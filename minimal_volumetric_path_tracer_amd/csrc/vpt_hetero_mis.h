@@ -145,19 +145,4 @@ struct HeteroMisSteps {
 
 }  // namespace vpt
 
-/* What a code object of estimator 13 exports, as vpt_hetero_eqa_unit is for estimator 12; lm: the grid behind the view has
- * a majorant grid (the kernel's LM instantiation); q: the context's track fraction.  The probe's result arrays: six
- * doubles per ray in res (psurf, dist, pdf, pe, T, rho_t, one array behind the other), strategy and steps */
-struct vpt_hetero_mis_unit {
-    int (*launch)(int device, const vpt::KParams& K, const DevScene* S, bool lm, double q, void* stream);
-    int (*simple_launch)(const vpt::KParams& K, const DevScene* S, bool lm, double q, void* stream);
-    void (*trace_launch)(const vpt_ray* rays, const uint64_t* states, int n, const vpt::Medium& m, const DevScene* S,
-                         const vpt_grid_view* grid, bool lm, double q, double* out, uint64_t* out_states);
-    void (*grid_mis_probe_launch)(const vpt_grid_view* grid, bool lm, double sigma_t, double q, const vpt_ray* rays,
-                                  const double* tmax, const double* light, const uint64_t* states, int n, double* res,
-                                  int32_t* strategy, uint32_t* steps, uint64_t* states_out);
-};
-extern const vpt_hetero_mis_unit vpt_int_hetero_mis_unit;     /* vpt_hetero_mis.hip: TL = false */
-extern const vpt_hetero_mis_unit vpt_int_hetero_mis_unit_tl;  /* vpt_hetero_mis_tl.hip: TL = true, the view's interp == 1 */
-
 #endif

@@ -5,13 +5,13 @@
  * hetero_mis_kernel: the persistent-wave loop of vpt_wave.h on estimator 13's steps (HeteroMisSteps).  A lane owns one
  * pixel and runs that pixel's samples strictly in order, so the image is render_kernel_simple<13>'s bit for bit.  The
  * prologue that stages a grid of at most 64 KiB in LDS, and with local majorants the majorant grid in what the density
- * left of the budget, is vpt_hetero.hip's, restated as estimators 11 and 12 restated it.
+ * left of the budget, is stage_grid_lds (vpt_hetero_lds.h), every density-grid kernel's.
  *
  * The track fraction q is a kernel argument of every kernel here (KParams keeps its layout), so render_kernel_simple<13>
  * is an overload with that argument: vpt_render_simple.h's kernel with trace_hetero_mis in the estimator's place.
  *
  * Trilinear interpolation: the unit instantiates one value of TL, VPT_HETERO_TL.  Compiled as it stands (0) it holds the
- * nearest-lookup kernels and exports their launches as the table vpt_int_hetero_mis_unit (vpt_hetero_mis.h);
+ * nearest-lookup kernels and exports their launches as the table vpt_int_hetero_mis_unit (vpt_hetero.h);
  * vpt_hetero_mis_tl.hip includes this file with VPT_HETERO_TL = 1 and exports vpt_int_hetero_mis_unit_tl.  The launches
  * are static; their host side is vpt_hetero_launch.h's, shared with the other density-grid units.
  */
@@ -19,23 +19,8 @@
 
 #include "vpt_wave.h"
 #include "vpt_hetero_mis.h"
+#include "vpt_hetero_lds.h"
 #include "vpt_hetero_launch.h"
-
-#ifndef VPT_HETERO_LDS
-#define VPT_HETERO_LDS 1
-#endif
-#define VPT_HETERO_LDS_BYTES 65536
-#ifndef VPT_HETERO_TL
-#define VPT_HETERO_TL 0
-#endif
-#if VPT_HETERO_TL
-#define VPT_HX(name) name##_tl
-#else
-#define VPT_HX(name) name
-#endif
-#ifndef VPT_HETERO_LDS_MAJ
-#define VPT_HETERO_LDS_MAJ 1
-#endif
 
 namespace vpt {
 
@@ -43,32 +28,9 @@ template <bool COUNT, int FB, bool LM, bool TL>
 __global__ __launch_bounds__(256, 2) void hetero_mis_kernel(KParams P, const DevScene* __restrict__ S, double q)
 {
     using TP = GridTrT<TL>;
-    /* the view lives in the steps object from the start, as in hetero_kernel: the walkers take its address */
+    /* the view lives in the steps object from the start (vpt_hetero_lds.h says why) */
     HeteroMisSteps<LM, TL> st{TP::template load<LM>(P.grid), q};
-    [[maybe_unused]] auto& G = st.tp.G;
-#if VPT_HETERO_LDS
-    __shared__ float lds_rho[VPT_HETERO_LDS_BYTES / sizeof(float)];
-    {
-        const int64_t nv = (int64_t)G.n[0] * G.n[1] * G.n[2];
-        if (nv <= (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float))) {  /* workgroup-uniform */
-            for (int k = threadIdx.x; k < (int)nv; k += blockDim.x) lds_rho[k] = G.rho[k];
-            __syncthreads();
-            G.rho = lds_rho;
-        }
-#if VPT_HETERO_LDS_MAJ
-        if (LM) {  /* the majorant grid goes into what the density left of the budget */
-            const int64_t cap = (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float));
-            const int64_t used = nv <= cap ? nv : 0;
-            const int64_t nbv = (int64_t)G.nb[0] * G.nb[1] * G.nb[2];
-            if (nbv <= cap - used) {  /* workgroup-uniform */
-                for (int k = threadIdx.x; k < (int)nbv; k += blockDim.x) lds_rho[used + k] = G.maj[k];
-                __syncthreads();
-                G.maj = lds_rho + used;
-            }
-        }
-#endif
-    }
-#endif
+    stage_grid_lds<LM>(st.tp.G);
     wave_render<HeteroMisSteps<LM, TL>, COUNT, FB>(P, S, st);
 }
 
@@ -173,13 +135,14 @@ __global__ __launch_bounds__(256) void grid_mis_probe_kernel(const vpt_grid_view
 
 }  // namespace
 
-/* the unit's launches, the slots of vpt_hetero_mis_unit (vpt_hetero_mis.h) */
-static void trace_launch(const vpt_ray* rays, const uint64_t* states, int n, const Medium& m, const DevScene* S,
-                         const vpt_grid_view* grid, bool lm, double q, double* out, uint64_t* out_states)
+/* the unit's launches, the slots of vpt_hetero_unit (vpt_hetero.h); estimator 13 takes lm and the track fraction */
+static void trace_launch(int, const vpt_ray* rays, const uint64_t* states, int n, const Medium& m, const DevScene* S,
+                         const vpt_grid_view* grid, const vpt_hetero_args& a, double* out, uint64_t* out_states)
 {
     const dim3 g = vpt_ray_grid(n), b(256);
-    if (lm) trace_batch_hetero_mis_kernel<true, TLU><<<g, b>>>(rays, states, n, m, S, grid, q, out, out_states);
-    else trace_batch_hetero_mis_kernel<false, TLU><<<g, b>>>(rays, states, n, m, S, grid, q, out, out_states);
+    with_flags([&](auto lmc) {
+        trace_batch_hetero_mis_kernel<decltype(lmc)::value, TLU><<<g, b>>>(rays, states, n, m, S, grid, a.q, out, out_states);
+    }, a.lm);
 }
 
 static void grid_mis_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_t, double q, const vpt_ray* rays,
@@ -187,48 +150,29 @@ static void grid_mis_probe_launch(const vpt_grid_view* grid, bool lm, double sig
                                   int32_t* strategy, uint32_t* steps, uint64_t* states_out)
 {
     const dim3 g = vpt_ray_grid(n), b(256);
-    if (lm) grid_mis_probe_kernel<true, TLU><<<g, b>>>(grid, sigma_t, q, rays, tmax, light, states, n, res, strategy, steps, states_out);
-    else grid_mis_probe_kernel<false, TLU><<<g, b>>>(grid, sigma_t, q, rays, tmax, light, states, n, res, strategy, steps, states_out);
+    with_flags([&](auto lmc) {
+        grid_mis_probe_kernel<decltype(lmc)::value, TLU><<<g, b>>>(grid, sigma_t, q, rays, tmax, light, states, n, res, strategy, steps, states_out);
+    }, lm);
 }
 
-/* render_kernel_simple<13>: vpt_simple_launch (vpt_hetero_launch.h) with the track fraction behind the scene */
-static int simple_launch(const KParams& K, const DevScene* S, bool lm, double q, void* stream)
+static int simple_launch(const KParams& K, const DevScene* S, const vpt_hetero_args& a, void* stream)
 {
     return with_flags([&](auto lmc, auto count, auto f32) {
-        constexpr int FB = decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64;
-        dim3 grid((unsigned)((K.w + 15) / 16), (unsigned)((K.shard_rows + 15) / 16));
-        render_kernel_simple<VPT_HETERO_MIS, decltype(count)::value, FB, decltype(lmc)::value, TLU>
-            <<<grid, dim3(256), 0, (hipStream_t)stream>>>(K, S, q);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return vpt_fail(VPT_E_HIP, "render_kernel_simple<%d> launch: %s", (int)VPT_HETERO_MIS, hipGetErrorString(e));
-        return (int)VPT_OK;
-    }, lm, K.counters != nullptr, K.fb == VPT_FB_F32);
+        return vpt_simple_launch(render_kernel_simple<VPT_HETERO_MIS, decltype(count)::value, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU>,
+                                 K, S, stream, a.q);
+    }, a.lm, K.counters != nullptr, K.fb == VPT_FB_F32);
 }
 
-/* the persistent-wave kernel: vpt_persistent_launch (vpt_hetero_launch.h) with the track fraction behind the scene */
-template <class Kern>
-static int persistent_launch(Kern kern, int device, const KParams& K, const DevScene* S, double q, void* stream)
-{
-    int blocks = 0;
-    hipError_t e = vpt_resident_blocks(kern, 256, device, &blocks);
-    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_mis_kernel: %s", hipGetErrorString(e));
-    kern<<<dim3((unsigned)vpt_wave_blocks(blocks, K)), dim3(256), 0, (hipStream_t)stream>>>(K, S, q);
-    e = hipGetLastError();
-    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "hetero_mis_kernel launch: %s", hipGetErrorString(e));
-    return (int)VPT_OK;
-}
-
-static int launch(int device, const KParams& K, const DevScene* S, bool lm, double q, void* stream)
+static int launch(int device, const KParams& K, const DevScene* S, const vpt_hetero_args& a, void* stream)
 {
     return with_flags([&](auto lmc, auto f32) {
-        return persistent_launch(hetero_mis_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU>,
-                                 device, K, S, q, stream);
-    }, lm, K.fb == VPT_FB_F32);
+        return vpt_persistent_launch(hetero_mis_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU>,
+                                     "hetero_mis_kernel", device, K, S, stream, a.q);
+    }, a.lm, K.fb == VPT_FB_F32);
 }
 
 /* what the unit exports.  Host pass only: a const object with a constant initialiser is emitted for the device as well,
  * and these are host functions */
 #if !defined(__HIP_DEVICE_COMPILE__)
-const vpt_hetero_mis_unit VPT_HX(vpt_int_hetero_mis_unit) = {launch, simple_launch, trace_launch, grid_mis_probe_launch};
+const vpt_hetero_unit VPT_HX(vpt_int_hetero_mis_unit) = {launch, simple_launch, trace_launch, nullptr, nullptr, nullptr, nullptr, grid_mis_probe_launch};
 #endif

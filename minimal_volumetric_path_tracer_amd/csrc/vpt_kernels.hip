@@ -553,20 +553,31 @@ static bool hetero_simple_kernel()
     return v && *v && atoi(v) != 0;
 }
 
-/* The code object that holds the kernels of estimators 10 and 11 for a lookup (tl: trilinear) and a medium without or
- * with emission (vpt_hetero.h), and estimator 12's and 13's for a lookup (vpt_hetero_eqa.h, vpt_hetero_mis.h).  The one place where the two settings
- * turn into a unit: every launch below goes through the table returned here.  The two grid probes exist in the units
- * without emission only, so their callers pass em = false whatever the context holds. */
-static const vpt_hetero_unit& hetero_unit(bool tl, bool em)
+/* The code object that holds an estimator's kernels for a lookup (tl: trilinear) and, for estimators 10 and 11, a medium
+ * without or with emission (vpt_hetero.h); estimators 12 to 14 take the lookup alone.  The one place where the settings
+ * turn into a unit: every launch below goes through the table returned here.  A probe names its estimator's unit, and
+ * the two grid probes exist in the units without emission only, so their callers pass em = false whatever the context
+ * holds. */
+static const vpt_hetero_unit& hetero_unit(int est, bool tl, bool em)
 {
+    switch (est) {
+    case VPT_HETERO_EQUIANGULAR: return tl ? vpt_int_hetero_eqa_unit_tl : vpt_int_hetero_eqa_unit;
+    case VPT_HETERO_MIS: return tl ? vpt_int_hetero_mis_unit_tl : vpt_int_hetero_mis_unit;
+    case VPT_HETERO_CHROMATIC: return tl ? vpt_int_hetero_chroma_unit_tl : vpt_int_hetero_chroma_unit;
+    default: break;  /* 10 and 11 */
+    }
     if (em) return tl ? vpt_int_hetero_unit_em_tl : vpt_int_hetero_unit_em;
     return tl ? vpt_int_hetero_unit_tl : vpt_int_hetero_unit;
 }
-static const vpt_hetero_eqa_unit& hetero_eqa_unit(bool tl) { return tl ? vpt_int_hetero_eqa_unit_tl : vpt_int_hetero_eqa_unit; }
-static const vpt_hetero_mis_unit& hetero_mis_unit(bool tl) { return tl ? vpt_int_hetero_mis_unit_tl : vpt_int_hetero_mis_unit; }
-static const vpt_hetero_chroma_unit& hetero_chroma_unit(bool tl)
+static const vpt_hetero_unit& hetero_unit(const vpt_context* ctx, int est)
 {
-    return tl ? vpt_int_hetero_chroma_unit_tl : vpt_int_hetero_chroma_unit;
+    return hetero_unit(est, ctx->h_grid.interp != 0, ctx->h_grid.emit != nullptr);
+}
+
+/* what the context and the medium give a launch of these units (vpt_hetero_args); stats: estimator 10's per-sample call */
+static vpt_hetero_args hetero_args(const vpt_context* ctx, double sigma_a, double sigma_s, unsigned long long* stats)
+{
+    return vpt_hetero_args{ctx->h_grid.block > 0, ctx->mis_fraction, chroma_coef(ctx, sigma_a, sigma_s), stats};
 }
 
 /* estimators 10, 11 (by K.est: hetero_kernel / hetero_ratio_kernel), 12 (hetero_eqa_kernel; the majorant block plays no
@@ -575,28 +586,16 @@ static const vpt_hetero_chroma_unit& hetero_chroma_unit(bool tl)
  * VPT_SIMPLE_KERNEL=1: render_kernel_simple<K.est> */
 static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
 {
-    const vpt_grid_view& g = ctx->h_grid;
-    const bool eqa = K.est == VPT_HETERO_EQUIANGULAR, mis = K.est == VPT_HETERO_MIS, lm = g.block > 0;
-    const vpt_hetero_unit& u = hetero_unit(g.interp != 0, g.emit != nullptr);
-    const vpt_hetero_eqa_unit& ue = hetero_eqa_unit(g.interp != 0);
-    const vpt_hetero_mis_unit& um = hetero_mis_unit(g.interp != 0);
-    const bool chroma = K.est == VPT_HETERO_CHROMATIC;
-    const vpt_hetero_chroma_unit& uc = hetero_chroma_unit(g.interp != 0);
-    const ChromaCoef cc = chroma_coef(ctx, K.sigma_a, K.sigma_s);
-    if (K.counters || hetero_simple_kernel()) {
-        if (chroma) return uc.simple_launch(K, ctx->d_scene, lm, cc, stream);
-        if (mis) return um.simple_launch(K, ctx->d_scene, lm, ctx->mis_fraction, stream);
-        return eqa ? ue.simple_launch(K, ctx->d_scene, stream) : u.simple_launch(K, ctx->d_scene, lm, stream);
-    }
+    const vpt_hetero_unit& u = hetero_unit(ctx, K.est);
+    const vpt_hetero_args a = hetero_args(ctx, K.sigma_a, K.sigma_s, nullptr);
+    if (K.counters || hetero_simple_kernel()) return u.simple_launch(K, ctx->d_scene, a, stream);
     std::lock_guard<std::mutex> lock(ctx->mu);
     StreamSlot* sl = nullptr;
     int rc = stream_slot(ctx, stream, 0, &sl);
     if (rc) return rc;
     K.queue = sl->d_queue;
     HIP_OK(hipMemsetAsync(K.queue, 0, sizeof(unsigned), stream));
-    if (chroma) rc = uc.launch(ctx->device, K, ctx->d_scene, lm, cc, stream);
-    else if (mis) rc = um.launch(ctx->device, K, ctx->d_scene, lm, ctx->mis_fraction, stream);
-    else rc = eqa ? ue.launch(ctx->device, K, ctx->d_scene, stream) : u.launch(ctx->device, K, ctx->d_scene, lm, stream);
+    rc = u.launch(ctx->device, K, ctx->d_scene, a, stream);
     if (rc) return rc;
     return slot_done(sl, stream);
 }
@@ -604,7 +603,7 @@ static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
 template <int EST, bool COUNT, int FB>
 static int launch_one(vpt_context* ctx, KParams K, hipStream_t stream)
 {
-    if constexpr (EST >= VPT_HETERO_FREE) {  /* the kernels of 10 and 11 live in vpt_hetero.hip, 12's in vpt_hetero_eqa.hip, 13's in vpt_hetero_mis.hip, 14's in vpt_hetero_chroma.hip */
+    if constexpr (EST >= VPT_HETERO_FREE) {  /* the density-grid units' kernels (hetero_unit) */
         return launch_hetero(ctx, K, stream);
     } else {
         const DevScene* S = ctx->d_scene;
@@ -1187,8 +1186,8 @@ static int grid_probe(vpt_context* ctx, bool lm, double sigma_t, const vpt_ray* 
     st.up(ds, states, nn);
     st.up(dtm, tmax, nn);
     st.launch([&] {
-        hetero_unit(ctx->h_grid.interp != 0, false).grid_probe_launch(dview, lm && ctx->h_grid.block > 0, sigma_t, dr, dtm, ds, n,
-                                                                      dtau, dtc, dso, dst);
+        hetero_unit(VPT_HETERO_FREE, ctx->h_grid.interp != 0, false)
+            .grid_probe_launch(dview, lm && ctx->h_grid.block > 0, sigma_t, dr, dtm, ds, n, dtau, dtc, dso, dst);
     });
     st.down(tau, dtau, nn);
     st.down(t_coll, dtc, nn);
@@ -1228,8 +1227,8 @@ int vpt_grid_ratio_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, 
     st.up(ds, states, nn);
     st.up(dtm, tmax, nn);
     st.launch([&] {
-        hetero_unit(ctx->h_grid.interp != 0, false).grid_ratio_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, sigma_t, dr, dtm, ds,
-                                                                            n, dth, dso, dst);
+        hetero_unit(VPT_HETERO_RATIO, ctx->h_grid.interp != 0, false)
+            .grid_ratio_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, sigma_t, dr, dtm, ds, n, dth, dso, dst);
     });
     st.down(that, dth, nn);
     st.down(states_out, dso, nn);
@@ -1258,8 +1257,9 @@ int vpt_grid_eqa_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, co
     st.up(dtm, tmax, nn);
     st.up(dl, light, 3 * nn);
     st.launch([&] {
-        hetero_eqa_unit(ctx->h_grid.interp != 0).grid_eqa_probe_launch(ctx->d_grid, sigma_t, dr, dtm, dl, ds, n, dres, dres + nn,
-                                                                       dres + 2 * nn, dres + 3 * nn, dres + 4 * nn, dso);
+        hetero_unit(ctx, VPT_HETERO_EQUIANGULAR)
+            .grid_eqa_probe_launch(ctx->d_grid, sigma_t, dr, dtm, dl, ds, n, dres, dres + nn, dres + 2 * nn, dres + 3 * nn,
+                                   dres + 4 * nn, dso);
     });
     double* const res[5] = {psurf, dist, pdf, T, rho_t};
     for (int k = 0; k < 5; ++k) st.down(res[k], dres + (size_t)k * nn, nn);
@@ -1291,8 +1291,9 @@ int vpt_grid_mis_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, co
     st.up(dtm, tmax, nn);
     st.up(dl, light, 3 * nn);
     st.launch([&] {
-        hetero_mis_unit(ctx->h_grid.interp != 0).grid_mis_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, sigma_t,
-                                                                       ctx->mis_fraction, dr, dtm, dl, ds, n, dres, dsg, dst, dso);
+        hetero_unit(ctx, VPT_HETERO_MIS)
+            .grid_mis_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, sigma_t, ctx->mis_fraction, dr, dtm, dl, ds, n, dres,
+                                   dsg, dst, dso);
     });
     double* const res[6] = {psurf, dist, pdf, pe, T, rho_t};
     for (int k = 0; k < 6; ++k) st.down(res[k], dres + (size_t)k * nn, nn);
@@ -1329,8 +1330,8 @@ int vpt_grid_chroma_probe(vpt_context* ctx, double sigma_a, double sigma_s, cons
     st.up(ds, states, nn);
     st.up(dtm, tmax, nn);
     st.launch([&] {
-        hetero_chroma_unit(ctx->h_grid.interp != 0).grid_chroma_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, cc, dr, dtm, ds,
-                                                                             n, dres, dh, dst, dso);
+        hetero_unit(ctx, VPT_HETERO_CHROMATIC)
+            .grid_chroma_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, cc, dr, dtm, ds, n, dres, dh, dst, dso);
     });
     st.down(t_coll, dres, nn);
     st.down(tau, dres + nn, nn);
@@ -1361,8 +1362,8 @@ int vpt_grid_emission_probe(vpt_context* ctx, double sigma_t, const vpt_ray* ray
     st.up(ds, states, nn);
     st.up(dtm, tmax, nn);
     st.launch([&] {
-        hetero_unit(ctx->h_grid.interp != 0, true).grid_emission_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, sigma_t, dr, dtm,
-                                                                              ds, n, dtc, des, dso, dst);
+        hetero_unit(VPT_HETERO_FREE, ctx->h_grid.interp != 0, true)
+            .grid_emission_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, sigma_t, dr, dtm, ds, n, dtc, des, dso, dst);
     });
     st.down(t_coll, dtc, nn);
     st.down(esum, des, nn);
@@ -1470,7 +1471,6 @@ static int trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* ray
     st.launch([&] {
         Medium mm{m->sigma_a, m->sigma_s, m->hg_g, m->max_depth, m->march_step, m->march_light};
         const dim3 grid = vpt_ray_grid(n), block(256);
-        const vpt_grid_view& g = ctx->h_grid;
         switch (m->estimator) {
         case 0: trace_batch_kernel<0><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         case 1: trace_batch_kernel<1><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
@@ -1483,19 +1483,11 @@ static int trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* ray
         case 8: trace_batch_kernel<8><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         case VPT_HETERO_FREE:
         case VPT_HETERO_RATIO:
-            hetero_unit(g.interp != 0, g.emit != nullptr).trace_launch(m->estimator, dr, ds, n, mm, ctx->d_scene, ctx->d_grid,
-                                                                       g.block > 0, dout, dso, stats);
-            break;
         case VPT_HETERO_EQUIANGULAR:
-            hetero_eqa_unit(g.interp != 0).trace_launch(dr, ds, n, mm, ctx->d_scene, ctx->d_grid, dout, dso);
-            break;
         case VPT_HETERO_MIS:
-            hetero_mis_unit(g.interp != 0).trace_launch(dr, ds, n, mm, ctx->d_scene, ctx->d_grid, g.block > 0,
-                                                        ctx->mis_fraction, dout, dso);
-            break;
         case VPT_HETERO_CHROMATIC:
-            hetero_chroma_unit(g.interp != 0).trace_launch(dr, ds, n, mm, ctx->d_scene, ctx->d_grid, g.block > 0,
-                                                           chroma_coef(ctx, m->sigma_a, m->sigma_s), dout, dso);
+            hetero_unit(ctx, m->estimator).trace_launch(m->estimator, dr, ds, n, mm, ctx->d_scene, ctx->d_grid,
+                                                        hetero_args(ctx, m->sigma_a, m->sigma_s, stats), dout, dso);
             break;
         default: trace_batch_kernel<9><<<grid, block>>>(dr, ds, n, mm, m->hg_g, ctx->d_scene, dout, dso); break;
         }

@@ -1,9 +1,12 @@
 /*
  * vpt_render_simple.h -- a render's launch parameters (KParams), the per-pixel helpers every render kernel but
  * the pool kernel uses (row mapping, camera ray, pixel store), and the one-lane-per-pixel render kernel, shared by
- * the translation units that instantiate it: vpt_kernels.hip (estimators 0-9), vpt_hetero.hip (estimators 10 and
- * 11; vpt_hetero_tl.hip compiles that file again for the trilinear field) and vpt_hetero_eqa.hip (estimator 12), so that the code object of
- * vpt_kernels.hip -- the tuned pool kernels and their placement -- stays what it was before estimator 10 existed.  render_kernel_simple replaces main()'s OpenMP pixel loop (src/rt.cpp:767-805):
+ * the translation units that instantiate it: vpt_kernels.hip (estimators 0-9) and the density-grid units -- vpt_hetero.hip
+ * (estimators 10 and 11), vpt_hetero_eqa.hip (12), vpt_hetero_mis.hip (13) and vpt_hetero_chroma.hip (14), each compiled
+ * again by the units that include it (_tl for the trilinear field, _em for the emission grid); the last two overload the
+ * kernel with a third argument.  So the code object of vpt_kernels.hip -- the tuned pool kernels and their placement --
+ * stays what it was before estimator 10 existed.  render_kernel_simple replaces main()'s OpenMP pixel loop
+ * (src/rt.cpp:767-805):
  * one lane owns one pixel and runs its spp camera samples (src/rt.cpp:786-798) through the estimator,
  * accumulating in FP64 in the reference's order, then writes the average (src/rt.cpp:800) once.
  */
@@ -31,7 +34,7 @@ struct KParams {
     int32_t cost_surf, cost_med;   /* event scheduler weights */
     int32_t chunk;                 /* samples per partial sum (pool kernel) */
     int32_t taper;                 /* tapered chunk layout (auto mode, vpt_chunks.h) */
-    const vpt_grid_view* grid;     /* estimators 10, 11, 12: the context's density grid (device), else NULL */
+    const vpt_grid_view* grid;     /* estimators 10 to 14: the context's density grid (device), else NULL */
 };
 
 __host__ __device__ __forceinline__ Medium medium_of(const KParams& P)
@@ -90,7 +93,8 @@ namespace {
 using namespace vpt;
 
 /* LM, TL, EM: estimators 10 and 11 only -- the grid has a majorant grid, the field is trilinear, the context holds an
- * emission grid (vpt_hetero.h); estimator 12 takes TL alone (vpt_hetero_eqa.h) */
+ * emission grid (vpt_hetero.h); estimator 12 takes TL alone (vpt_hetero_eqa.h).  Estimators 13 and 14 have overloads of
+ * their own in their units, with the track fraction and the coefficients behind (P, S) */
 template <int EST, bool COUNT, int FB, bool LM = false, bool TL = false, bool EM = false>
 __global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const DevScene* __restrict__ S)
 {

@@ -1,7 +1,8 @@
 """The host side of the per-ray entry points and of the density-grid launches (csrc/vpt_kernels.hip's staging helper and
 unit selector, csrc/vpt_hetero_launch.h): what a copy of the wrong length, a wrong grid size, a mishandled optional
 output or a wrong slot of a unit's table would change.  One 8^3 grid with majorant block 2 in the default scene;
-257 rays: one full workgroup and one lane."""
+257 rays: one full workgroup and one lane.  And the branches of the kernels' LDS prologue (csrc/vpt_hetero_lds.h), on
+grids at and around the 16 384-float budget."""
 import ctypes
 
 import numpy as np
@@ -194,16 +195,25 @@ def _cfg(est):
     return RenderConfig(width=W, height=H, spp=SPP, estimator=est, sigma_a=T.SA, sigma_s=T.SS, seed=SEED, fp64=True)
 
 
-@pytest.mark.parametrize("est", ["hetero", "hetero_ratio", "hetero_equiangular"])
+NO_EMISSION = ("hetero_equiangular", "hetero_mis", "hetero_chromatic")  # estimators that take no emission grid
+MIS_FRACTION = 0.3  # strictly between 0 (estimator 12's draws) and 1
+COLOUR = ((1.0, 0.7, 0.4), (0.9, 1.0, 0.6))  # absorption, scattering: no two channels alike
+
+
+@pytest.mark.parametrize("est", ["hetero", "hetero_ratio", "hetero_equiangular", "hetero_mis", "hetero_chromatic"])
 def test_every_setting_reaches_its_unit(lt, orc_vm, monkeypatch, est):
-    """Each (interpolation, emission) setting of one context -- estimator 12 takes no emission grid: the interpolation
-    alone -- through the persistent-wave render, render_kernel_simple (VPT_SIMPLE_KERNEL=1) and the in-order sum of the
-    per-sample call: the three are one image bit for bit, and no two settings give the same image"""
+    """Each (interpolation, emission) setting of one context -- estimators 12 to 14 take no emission grid: the
+    interpolation alone -- through the persistent-wave render, render_kernel_simple (VPT_SIMPLE_KERNEL=1) and the in-order
+    sum of the per-sample call: the three are one image bit for bit, and no two settings give the same image.  Estimator
+    13 runs with a track fraction of its own and estimator 14 with unequal channels, so that a launch that dropped either
+    would show"""
     rays, st = T._camera_samples(orc_vm, W, H, SPP, SEED)
     m = _cfg(est).medium()
     imgs = {}
     try:
-        for ip, em in SETTINGS if est != "hetero_equiangular" else [(ip, False) for ip in ("nearest", "trilinear")]:
+        lt.set_hetero_mis_fraction(MIS_FRACTION)
+        lt.set_medium_colour(*COLOUR)
+        for ip, em in SETTINGS if est not in NO_EMISSION else [(ip, False) for ip in ("nearest", "trilinear")]:
             lt.set_grid_interpolation(ip)
             if em:
                 lt.set_emission_grid(EPS, RGB)
@@ -227,3 +237,82 @@ def test_every_setting_reaches_its_unit(lt, orc_vm, monkeypatch, est):
     finally:
         lt.set_grid_interpolation("nearest")
         lt.set_emission_grid(EPS, RGB)
+        lt.set_hetero_mis_fraction(0.5)
+        lt.set_medium_colour()
+
+
+# ---- the LDS prologue's branches (csrc/vpt_hetero_lds.h) ----
+CAP = 16384  # the budget in floats
+# (shape [nz, ny, nx], majorant block): every branch of the prologue by its condition on nv and nbv
+LDS_GRIDS = {
+    "both_staged": ((15, 32, 32), 4),       # nv < cap, nbv = 256 <= cap - nv = 1024: majorants behind the density
+    "maj_global": ((15, 32, 32), 2),        # nv < cap, nbv = 2048 > cap - nv: density staged, majorants global
+    "nv_is_cap": ((16, 32, 32), 2),         # nv == cap: the <= boundary, nothing left for majorants
+    "maj_at_zero": ((17, 32, 32), 2),       # nv > cap, nbv = 2304 <= cap: density global, majorants staged at 0
+    "nothing_staged": ((17, 32, 32), 1),    # nv > cap, nbv = nv > cap
+    "no_majorants": ((17, 32, 32), 0),      # nv > cap, LM = false: density global
+}
+LDS_ESTIMATORS = ["hetero", "hetero_ratio", "hetero_equiangular", "hetero_mis", "hetero_chromatic"]
+EQA_GRIDS = ("both_staged", "nv_is_cap", "no_majorants")  # estimator 12 ignores the majorants: one grid per nv case
+
+
+def _nbv(shape, block):
+    return int(np.prod([-(-n // block) for n in shape])) if block else 0
+
+
+def test_lds_grids_meet_their_conditions():
+    """the grids above are what their names say (no GPU work, but it belongs with them)"""
+    nv = {k: int(np.prod(sh)) for k, (sh, _) in LDS_GRIDS.items()}
+    nbv = {k: _nbv(sh, b) for k, (sh, b) in LDS_GRIDS.items()}
+    assert nv["both_staged"] < CAP and 0 < nbv["both_staged"] <= CAP - nv["both_staged"]
+    assert nv["maj_global"] < CAP and nbv["maj_global"] > CAP - nv["maj_global"]
+    assert nv["nv_is_cap"] == CAP and nbv["nv_is_cap"] > 0
+    assert nv["maj_at_zero"] > CAP and 0 < nbv["maj_at_zero"] <= CAP
+    assert nv["nothing_staged"] > CAP and nbv["nothing_staged"] > CAP
+    assert nv["no_majorants"] > CAP and nbv["no_majorants"] == 0
+    assert {nv[k] for k in EQA_GRIDS} == set(nv.values())
+
+
+def _sparse_field(shape, seed):
+    rho = np.random.default_rng(seed).uniform(0.0, 1.0, shape).astype(np.float32)
+    rho[rho < 0.3] = 0.0  # empty voxels: the majorant blocks differ
+    return rho
+
+
+@pytest.fixture(scope="module")
+def pt():
+    """a tracer of the prologue tests' own: they replace the grid"""
+    t = Tracer(0, default_scene())
+    t.set_hetero_mis_fraction(MIS_FRACTION)
+    t.set_medium_colour(*COLOUR)
+    yield t
+    t.close()
+
+
+def _lds_cases():
+    for k in LDS_GRIDS:
+        for est in LDS_ESTIMATORS:
+            if est != "hetero_equiangular" or k in EQA_GRIDS:
+                yield pytest.param(k, est, "nearest", id=f"{k}-{est}")
+    for est in LDS_ESTIMATORS:
+        yield pytest.param("both_staged", est, "trilinear", id=f"both_staged-{est}-trilinear")
+
+
+@pytest.mark.parametrize("grid,est,ip", list(_lds_cases()))
+def test_lds_prologue_branches(pt, monkeypatch, grid, est, ip):
+    """The persistent-wave render, whose prologue stages the density and the majorants in LDS or leaves either in global
+    memory, equals render_kernel_simple's (VPT_SIMPLE_KERNEL=1), which reads global memory only, bit for bit -- on a grid
+    for every branch of the prologue"""
+    shape, block = LDS_GRIDS[grid]
+    try:
+        pt.set_density_grid(_sparse_field(shape, 43), LO, HI, majorant_block=block, interpolation=ip)
+        img = pt.render(_cfg(est))
+        with monkeypatch.context() as mp:
+            mp.setenv("VPT_SIMPLE_KERNEL", "1")
+            simple = pt.render(_cfg(est))
+        assert np.isfinite(img).all() and (img > 0).any()
+        assert bitwise_equal(img, simple).all(), f"{(~bitwise_equal(img, simple)).sum()} differ"
+    finally:
+        pt.set_majorant_block(0)
+        pt.set_grid_interpolation("nearest")
+        pt.clear_density_grid()
