@@ -97,7 +97,7 @@ class Oracle:
         L.orc_math_n.restype, L.orc_math_n.argtypes = None, [_I, _P, _P, _P, _I]
         L.orc_hg_phase_sample.restype, L.orc_hg_phase_sample.argtypes = _U, [_D, _P, _U, _P]
         L.orc_hg_phase_value.restype, L.orc_hg_phase_value.argtypes = _D, [_D, _P, _P]
-        # the heterogeneous medium (oracle/vpt_oracle_grid.h): estimators 10 and 11
+        # the heterogeneous medium (oracle/vpt_oracle_grid.h): estimators 10 - 14
         L.orc_set_density_grid.restype, L.orc_set_density_grid.argtypes = _I, [_P, _I, _I, _I, _P, _P, _I, _I]
         L.orc_clear_density_grid.restype, L.orc_clear_density_grid.argtypes = None, []
         L.orc_set_emission_grid.restype, L.orc_set_emission_grid.argtypes = _I, [_P, _P]
@@ -106,6 +106,14 @@ class Oracle:
         L.orc_grid_probe.restype, L.orc_grid_probe.argtypes = _I, [_D, _P, _P, _P, _I, _P, _P, _P, _P]
         L.orc_grid_ratio_probe.restype, L.orc_grid_ratio_probe.argtypes = _I, [_D, _P, _P, _P, _I, _P, _P, _P]
         L.orc_grid_emission_probe.restype, L.orc_grid_emission_probe.argtypes = _I, [_D, _P, _P, _P, _I, _P, _P, _P, _P]
+        # estimators 12, 13 and 14: their settings, what the library would answer, their decisions
+        L.orc_set_hetero_mis_fraction.restype, L.orc_set_hetero_mis_fraction.argtypes = _I, [_D]
+        L.orc_set_medium_colour.restype, L.orc_set_medium_colour.argtypes = _I, [_P, _P]
+        L.orc_estimator_status.restype, L.orc_estimator_status.argtypes = _I, [POINTER(Medium)]
+        L.orc_ext_counters.restype, L.orc_ext_counters.argtypes = None, [_P, _I]
+        L.orc_grid_eqa_probe.restype, L.orc_grid_eqa_probe.argtypes = _I, [_D, _P, _P, _P, _P, _I] + [_P] * 6
+        L.orc_grid_mis_probe.restype, L.orc_grid_mis_probe.argtypes = _I, [_D, _D, _P, _P, _P, _P, _I] + [_P] * 9
+        L.orc_grid_chroma_probe.restype, L.orc_grid_chroma_probe.argtypes = _I, [_P, _P, _P, _P, _P, _I] + [_P] * 6
         self.L = L
         self.portable = bool(L.orc_is_portable_math())
         self.prefix = "orc"
@@ -131,8 +139,9 @@ class Oracle:
             pv[i] = self.L.orc_hg_phase_value(g, d.ctypes.data, w[i].ctypes.data)
         return out, st, pv
 
-    # ---- the heterogeneous medium.  The grid, the emission grid and the fault are state of the library, which the
-    # session's fixtures share: whoever sets one resets it in a `finally` (clear_density_grid, set_hetero_fault(0)).
+    # ---- the heterogeneous medium.  The grid, the emission grid, the fault, the track fraction and the medium colour
+    # are state of the library, which the session's fixtures share: whoever sets one resets it in a `finally`
+    # (clear_density_grid, set_hetero_fault(0), set_hetero_mis_fraction(0.5), set_medium_colour()).
     INTERPOLATIONS = {"nearest": 0, "trilinear": 1}
 
     def set_density_grid(self, rho, lo, hi, majorant_block: int = 0, interpolation: str = "nearest", emission=None,
@@ -167,8 +176,34 @@ class Oracle:
         self._grid_shape = None
 
     def set_hetero_fault(self, kind: int) -> None:
-        """test only: the mistake trace_hetero commits on purpose (0: none; oracle/vpt_oracle.c)"""
+        """test only: the mistake the heterogeneous tracers commit on purpose (0: none; oracle/vpt_oracle.c)"""
         self.L.orc_hetero_set_fault(int(kind))
+
+    def set_hetero_mis_fraction(self, q: float) -> None:
+        """Tracer.set_hetero_mis_fraction: estimator 13's track fraction in [0, 1] (default 0.5); state of the library"""
+        if self.L.orc_set_hetero_mis_fraction(float(q)) != 0:
+            raise ValueError("oracle: the track fraction is a number in [0, 1]")
+
+    def set_medium_colour(self, absorption=(1.0, 1.0, 1.0), scattering=(1.0, 1.0, 1.0)) -> None:
+        """Tracer.set_medium_colour: estimator 14's multipliers of sigma_a and sigma_s per channel (default 1); state
+        of the library"""
+        ca, cs = (np.ascontiguousarray(v, dtype=np.float64) for v in (absorption, scattering))
+        if ca.shape != (3,) or cs.shape != (3,) or self.L.orc_set_medium_colour(ca.ctypes.data, cs.ctypes.data) != 0:
+            raise ValueError("oracle: a medium colour is two triples of finite numbers >= 0")
+
+    def ext_counters(self, reset: bool = True) -> dict:
+        """test only: what the trace calls since the last reset did in estimators 12 - 14 -- medium vertices by the
+        strategy that sampled them, estimator 14's decisions by hero channel, its collisions whose three weights differ"""
+        c = np.zeros(6, dtype=np.uint64)
+        self.L.orc_ext_counters(c.ctypes.data, int(reset))
+        c = [int(v) for v in c]
+        return {"equiangular": c[0], "track": c[1], "hero": tuple(c[2:5]), "w_differ": c[5]}
+
+    def _check_estimator(self, m: Medium) -> None:
+        """what the library refuses, the oracle refuses: VPT_E_INVALID (-1), VPT_E_UNSUPPORTED (-4)"""
+        rc = self.L.orc_estimator_status(byref(m))
+        if rc == -4 or (rc != 0 and m.estimator >= 12):
+            raise ValueError(f"oracle: estimator {m.estimator} is refused in this state (library code {rc})")
 
     @staticmethod
     def _probe_args(rays, tmax, states):
@@ -223,11 +258,62 @@ class Oracle:
         assert rc == 0
         return tc, es, so, steps
 
+    def grid_eqa_probe(self, rho, lo, hi, sigma_t, rays, tmax, light, states, interpolation="nearest"):
+        """grid_eqa_probe_host's arguments and results: (psurf, dist, pdf, T, rho_t, states)"""
+        r, t, s, n = self._probe_args(rays, tmax, states)
+        lp = np.ascontiguousarray(np.broadcast_to(np.asarray(light, dtype=np.float64), (n, 3)))
+        res, so = [np.zeros(n) for _ in range(5)], np.zeros(n, dtype=np.uint64)
+        self.set_density_grid(rho, lo, hi, 0, interpolation)
+        try:
+            rc = self.L.orc_grid_eqa_probe(float(sigma_t), r.ctypes.data, t.ctypes.data, lp.ctypes.data, s.ctypes.data, n,
+                                           *[a.ctypes.data for a in res], so.ctypes.data)
+        finally:
+            self.clear_density_grid()
+        assert rc == 0
+        return (*res, so)
+
+    def grid_mis_probe(self, rho, lo, hi, sigma_t, rays, tmax, light, states, q=0.5, majorant_block=0,
+                       interpolation="nearest"):
+        """grid_mis_probe_host's arguments and results: (psurf, strategy, dist, pdf, pe, T, rho_t, steps, states)"""
+        r, t, s, n = self._probe_args(rays, tmax, states)
+        lp = np.ascontiguousarray(np.broadcast_to(np.asarray(light, dtype=np.float64), (n, 3)))
+        f = [np.zeros(n) for _ in range(6)]  # psurf, dist, pdf, pe, T, rho_t
+        strategy, steps, so = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64)
+        self.set_density_grid(rho, lo, hi, majorant_block, interpolation)
+        try:
+            rc = self.L.orc_grid_mis_probe(float(sigma_t), float(q), r.ctypes.data, t.ctypes.data, lp.ctypes.data,
+                                           s.ctypes.data, n, f[0].ctypes.data, strategy.ctypes.data,
+                                           *[a.ctypes.data for a in f[1:]], steps.ctypes.data, so.ctypes.data)
+        finally:
+            self.clear_density_grid()
+        assert rc == 0
+        return f[0], strategy, f[1], f[2], f[3], f[4], f[5], steps, so
+
+    def grid_chroma_probe(self, rho, lo, hi, sigma_a, sigma_s, rays, tmax, states, absorption=(1.0, 1.0, 1.0),
+                          scattering=(1.0, 1.0, 1.0), majorant_block=0, interpolation="nearest"):
+        """grid_chroma_probe_host's arguments and results: (hero, t_coll, tau, w, steps, states), w of shape (3, n)"""
+        r, t, s, n = self._probe_args(rays, tmax, states)
+        sa = float(sigma_a) * np.ascontiguousarray(absorption, dtype=np.float64)
+        ss = float(sigma_s) * np.ascontiguousarray(scattering, dtype=np.float64)
+        hero, tc, tau, w = np.zeros(n, dtype=np.int32), np.zeros(n), np.zeros(n), np.zeros((3, n))
+        steps, so = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64)
+        self.set_density_grid(rho, lo, hi, majorant_block, interpolation)
+        try:
+            rc = self.L.orc_grid_chroma_probe(sa.ctypes.data, ss.ctypes.data, r.ctypes.data, t.ctypes.data, s.ctypes.data, n,
+                                              hero.ctypes.data, tc.ctypes.data, tau.ctypes.data, w.ctypes.data,
+                                              steps.ctypes.data, so.ctypes.data)
+        finally:
+            self.clear_density_grid()
+        assert rc == 0
+        return hero, tc, tau, w, steps, so
+
     def trace(self, estimator: int, rays: np.ndarray, states: np.ndarray, sigma_a=0.001, sigma_s=0.009, hg_g=0.0,
               max_depth=0, counters: bool = False, march_step=0.1, march_light=7):
-        """per-sample radiance and end state of include/vpt.h's estimator number (0-11; 10 and 11 need a density
-        grid: without one the radiance is NaN and the state is the start state)"""
+        """per-sample radiance and end state of include/vpt.h's estimator number (0-14; 10 and 11 need a density
+        grid: without one the radiance is NaN and the state is the start state; 12-14 raise ValueError where the
+        library refuses them: without a grid, with an emission grid, 14 with a channel without extinction)"""
         m = Medium(sigma_a, sigma_s, hg_g, max_depth, estimator, march_step, march_light)
+        self._check_estimator(m)
         if getattr(rays, "dtype", None) is not None and rays.dtype.names:  # records of (o, d), as Tracer.trace takes them
             rays = np.ascontiguousarray(rays).view(np.float64)
         r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
@@ -247,9 +333,10 @@ class Oracle:
         """main()'s pixel loop over camera rows [y0, y1); returns (h, w, 3) float64 in file order.
         chunk: samples per partial sum in uniform chunks (spp = the reference's order); None = the
         GPU's default (vpt_params.chunk_spp == 0): for estimators 0-5 chunks of min(spp, 32), the last 64
-        samples tapered (csrc/vpt_chunks.h); for estimators 6-11, whose kernels ignore chunk_spp (include/vpt.h),
+        samples tapered (csrc/vpt_chunks.h); for estimators 6-14, whose kernels ignore chunk_spp (include/vpt.h),
         the reference's order."""
         m = Medium(sigma_a, sigma_s, hg_g, max_depth, estimator, march_step, march_light)
+        self._check_estimator(m)
         out = np.zeros((h, w, 3))
         c = Counters()
         taper = 0

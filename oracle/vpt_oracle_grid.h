@@ -6,6 +6,7 @@
  * yields a ray's tentative points -- the draws, the step count, the boundary test -- for the global or the local
  * majorant, and ONE consumer applies the rule of the track, of ratio tracking or of the emitting track at each
  * point.  Everything that draws keeps the specification's operation order, FP64 without contraction.
+ * The distance decisions of estimators 12, 13 and 14 follow at the end, on the same pieces.
  *
  * Included by vpt_oracle.c after xi(c), M_EXP, M_LOG and v3 exist; plain C11.
  */
@@ -33,7 +34,7 @@ typedef struct {
 } og_grid;
 
 static og_grid g_grid;
-static int g_hetero_fault = 0;  /* orc_hetero_set_fault: the mistake trace_hetero commits on purpose (tests) */
+static int g_hetero_fault = 0;  /* orc_hetero_set_fault: the mistake a heterogeneous tracer commits on purpose (tests) */
 
 static void og_free(float** p)
 {
@@ -398,6 +399,192 @@ static double og_run(int kind, const double o[3], const double d[3], double tmax
     }
     if (steps) *steps = w.steps;
     return result;
+}
+
+/* ================================================================== estimators 12, 13 and 14
+ * The distance decisions of the three later estimators, written from the specification (the header comments of
+ * csrc/vpt_grid_eqa.h, vpt_grid_mis.h and vpt_grid_chroma.h, DESIGN.md section 4, tests/{eqa,mis,chroma}_model.py) on
+ * the pieces above: og_slab, og_tau, og_field_on_ray, og_run.  The product states each decision as a chain of
+ * functions that hand draws and intermediate values on; here a decision is ONE function that fills one record, the
+ * light's geometry is formed once per decision, and the equi-angular pdf is the oracle's estimator-1 helper
+ * (equiangular_prob, vpt_oracle.c).  FP64 without contraction, the specification's operation order. */
+static double equiangular_prob(double D, double ta, double tb, double s);
+
+/* the settings next to the grid's: estimator 13's track fraction, estimator 14's colour multipliers */
+static double g_mis_q = 0.5;
+static double g_col_a[3] = {1.0, 1.0, 1.0}, g_col_s[3] = {1.0, 1.0, 1.0};
+
+enum { OG_D_SURFACE = 0, OG_D_MEDIUM = 1, OG_D_EMPTY = 2, OG_D_CAP = 3 };
+
+/* what a decision of estimator 12 or 13 found.  Fields a branch does not reach are +0 (the probes' convention):
+ * all but psurf, strategy and steps on the surface and at the cap; T at an empty point */
+typedef struct {
+    int kind;        /* OG_D_SURFACE; OG_D_MEDIUM; OG_D_EMPTY: a distance with rho == 0 there; OG_D_CAP: the step cap */
+    int strategy;    /* 1: the distance decision ran a delta track */
+    uint32_t steps;  /* that track's draws */
+    double psurf;    /* the transmittance over [0, t] */
+    double dist;     /* -1 on the surface, NaN at the cap */
+    double pe;       /* the equi-angular pdf times 1 - psurf at dist */
+    double pdf;      /* estimator 12: pe; estimator 13: the combined pdf */
+    double T;        /* the transmittance over [0, dist] */
+    double rho_t;    /* the density at o + d dist */
+} og_decision;
+
+/* the grid's transmittance over [0, t] of the ray: no draw */
+static double og_transmittance(const double o[3], const double d[3], double t, double sigma_t)
+{
+    return M_EXP(sigma_t * og_tau(o, d, t) * -1.0);
+}
+
+/* the part [a, b] of [0, t] that the box holds; without a slab interval all of [0, t].
+ * Fault 6 (orc_hetero_set_fault): [0, t] whatever the box is -- the reference's interval. */
+static void og_eqa_interval(const double o[3], const double d[3], double t, double* a, double* b)
+{
+    double t0, t1;
+    *a = 0.0;
+    *b = t;
+    if (g_hetero_fault == 6) return;
+    if (!og_slab(o, d, &t0, &t1)) return;
+    if (t0 > 0.0) *a = t0;
+    if (!(t < t1)) *b = t1;
+}
+
+/* the light seen from the ray: its distance D from the ray's line, the foot of the perpendicular proj, and the angles
+ * of the interval's two ends (equiangular_params2's operations with a in 0.0's place and b in tMax's) */
+typedef struct { double D, proj, ta, tb; } og_eqa_light;
+
+static og_eqa_light og_eqa_see(const double o[3], const double d[3], const double lp[3], double a, double b)
+{
+    og_eqa_light g;
+    const v3 dv = vsub(vload(lp), vload(o)), rd = vload(d);
+    const double dvn = sqrt(vdot(dv, dv));
+    g.proj = vdot(dv, rd) / vdot(rd, rd);
+    g.D = sqrt(dvn * dvn - g.proj * g.proj);
+    g.ta = M_ATAN2(a - g.proj, g.D);
+    g.tb = M_ATAN2(b - g.proj, g.D);
+    return g;
+}
+
+/* the density of the distance whose offset from the foot is s, times the medium branch's probability */
+static double og_eqa_density(const og_eqa_light* g, double s, double psurf)
+{
+    return equiangular_prob(g->D, g->ta, g->tb, s) * (1 - psurf);
+}
+
+/* a decision's medium side once the distance is known: the density there, and T where there is medium */
+static void og_decision_point(og_decision* r, const double o[3], const double d[3], double sigma_t)
+{
+    r->rho_t = og_field_on_ray(g_grid.rho, o, d, r->dist);
+    r->kind = r->rho_t == 0.0 ? OG_D_EMPTY : OG_D_MEDIUM;
+    if (r->kind == OG_D_MEDIUM) r->T = og_transmittance(o, d, r->dist, sigma_t);
+}
+
+/* estimator 12: the draw x, then the coin against psurf; the distance is equi-angular in [a, b] toward lp */
+static og_decision og_decide_eqa(orc_ctx* c, const double o[3], const double d[3], double t, const double lp[3], double sigma_t)
+{
+    og_decision r;
+    double a, b;
+    memset(&r, 0, sizeof r);
+    r.dist = -1.0;
+    og_eqa_interval(o, d, t, &a, &b);
+    const double x = xi(c);
+    r.psurf = og_transmittance(o, d, t, sigma_t);
+    if (xi(c) < r.psurf) return r;
+    const og_eqa_light g = og_eqa_see(o, d, lp, a, b);
+    const double s = g.D * M_TAN((1 - x) * g.ta + x * g.tb);
+    r.pe = og_eqa_density(&g, s, r.psurf);
+    r.pdf = r.pe;
+    r.dist = s + g.proj;
+    og_decision_point(&r, o, d, sigma_t);
+    return r;
+}
+
+/* estimator 13: the draw x, the coin, and where the coin is below q a delta track's draws.  The coin less q over
+ * 1 - q is estimator 12's coin.  The pdf of a medium distance combines both strategies' densities there:
+ * q sigma_t rho T + (1 - q) pe.  Fault 7: the track's density without T. */
+static og_decision og_decide_mis(orc_ctx* c, const double o[3], const double d[3], double t, const double lp[3], double sigma_t,
+                                 double q)
+{
+    og_decision r;
+    double a, b;
+    memset(&r, 0, sizeof r);
+    r.dist = -1.0;
+    og_eqa_interval(o, d, t, &a, &b);
+    const double x = xi(c);
+    r.psurf = og_transmittance(o, d, t, sigma_t);
+    const double coin = xi(c);
+    r.strategy = coin < q;
+    if (r.strategy) {
+        const double tc = og_run(OG_TRACK, o, d, t, sigma_t, c, &r.steps, NULL);
+        if (tc != tc) {
+            r.kind = OG_D_CAP;
+            r.dist = tc;
+            return r;
+        }
+        if (tc < 0) return r;
+        const og_eqa_light g = og_eqa_see(o, d, lp, a, b);
+        r.dist = tc;
+        r.pe = og_eqa_density(&g, tc - g.proj, r.psurf);
+    } else {
+        if ((coin - q) / (1 - q) < r.psurf) return r;
+        const og_eqa_light g = og_eqa_see(o, d, lp, a, b);
+        const double s = g.D * M_TAN((1 - x) * g.ta + x * g.tb);
+        r.pe = og_eqa_density(&g, s, r.psurf);
+        r.dist = s + g.proj;
+    }
+    og_decision_point(&r, o, d, sigma_t);
+    const double pff = g_hetero_fault == 7 ? sigma_t * r.rho_t : sigma_t * r.rho_t * r.T;
+    r.pdf = q * pff + (1 - q) * r.pe;
+    return r;
+}
+
+/* ------------------------------------------------------------------ estimator 14: the chromatic medium */
+typedef struct og_chroma_s {
+    double ss[3], st[3];  /* per unit density and channel: scattering, extinction = absorption + scattering */
+    int grey;             /* the three extinctions are one number */
+} og_chroma;
+
+static og_chroma og_chroma_of(const double sa[3], const double ss[3])
+{
+    og_chroma k;
+    for (int i = 0; i < 3; ++i) {
+        k.ss[i] = ss[i];
+        k.st[i] = sa[i] + ss[i];
+    }
+    k.grey = k.st[0] == k.st[1] && k.st[1] == k.st[2];
+    return k;
+}
+
+/* the hero channel: uniform from one draw, channel 0 without a draw under grey extinction */
+static int og_chroma_hero(const og_chroma* k, orc_ctx* c)
+{
+    if (k->grey) return 0;
+    const int h = (int)(xi(c) * 3);
+    return h > 2 ? 2 : h;
+}
+
+/* the balance heuristic over the three hero choices behind the optical depth tau, from e_k = exp(-(st_k tau - min)):
+ * collision != 0: w_k = ss_k e_k over the mean of st_j e_j (under grey extinction that mean is st itself, exactly);
+ * else ws_k = e_k over the mean of e_j */
+static v3 og_chroma_weight(const og_chroma* k, double tau, int collision)
+{
+    double xk[3], e[3];
+    for (int i = 0; i < 3; ++i) xk[i] = k->st[i] * tau;
+    double mn = xk[0] < xk[1] ? xk[0] : xk[1];
+    mn = mn < xk[2] ? mn : xk[2];
+    for (int i = 0; i < 3; ++i) e[i] = M_EXP((xk[i] - mn) * -1.0);
+    if (!collision) {
+        const double den = ((e[0] + e[1]) + e[2]) / 3.0;
+        return V3(e[0] / den, e[1] / den, e[2] / den);
+    }
+    const double den = k->grey ? k->st[0] : ((k->st[0] * e[0] + k->st[1] * e[1]) + k->st[2] * e[2]) / 3.0;
+    return V3((k->ss[0] * e[0]) / den, (k->ss[1] * e[1]) / den, (k->ss[2] * e[2]) / den);
+}
+
+/* every channel's transmittance over a segment of optical depth tau */
+static v3 og_chroma_T(const og_chroma* k, double tau)
+{
+    return V3(M_EXP(k->st[0] * tau * -1.0), M_EXP(k->st[1] * tau * -1.0), M_EXP(k->st[2] * tau * -1.0));
 }
 
 #endif

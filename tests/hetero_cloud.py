@@ -35,3 +35,44 @@ def set_cloud(owner, block, interp, emit):
     owner.set_density_grid(rho, ROOM_LO, ROOM_HI, majorant_block=block, interpolation=interp)
     if emit:
         owner.set_emission_grid(eps, RGB)
+
+
+# ---- estimators 12, 13 and 14 (tests/test_oracle_hetero_ext.py, tests/test_gpu_hetero_ext_oracle.py): the same cloud,
+# no emission grid (the library refuses these estimators with one).
+#
+# Why another box.  In ROOM_LO .. ROOM_HI the camera and every wall lie inside the grid, so the equi-angular interval
+# [a, b] is [0, t] on all but the rays that hit nothing, and a kernel that sampled [0, t] would differ on 42 of 4096
+# samples.  In EXT_LO .. EXT_HI the camera stands outside the box (a > 0 on every camera ray) and the walls lie
+# outside it (b < t on most later rays): that mistake moves more than 1000 samples.  The three lights are inside.
+#
+# Why these coefficients.  The smaller box holds less medium; at (0.0026, 0.0234) the 2048 samples of the GPU tests
+# have at least 27 % surface events, 25 % medium events and 50 % lit samples under each of the three estimators on
+# each of the four grid configurations, and each of the oracle's deliberate mistakes 5-10 (orc_hetero_set_fault)
+# changes more than 1000 of 4096 samples (tests/test_oracle_hetero_ext.py asserts both).
+EXT_LO, EXT_HI = (-40.0, -35.0, -70.0), (40.0, 38.0, 120.0)
+EXT_SA, EXT_SS = 0.0026, 0.0234
+Q = 0.5  # estimator 13's track fraction
+# estimator 14's colour: three different extinctions and three different albedos
+COLOUR = ((1.0, 0.6, 0.3), (0.7, 1.0, 1.4))
+# one pair of equal extinctions (channels 0 and 1 take the same multipliers, so the pair is equal bit for bit) and a
+# third that differs: two of three hero choices run the same track, and the weights' mean has two equal terms
+COLOUR_PAIR = ((1.0, 1.0, 0.3), (1.0, 1.0, 1.4))
+GREY = ((1.0, 1.0, 1.0), (1.0, 1.0, 1.0))
+EXT_CONFIGS = [(block, interp) for block in (0, 2) for interp in ("nearest", "trilinear")]
+EXT_MAIN = (2, "trilinear")
+ESTIMATORS.update({"hetero_equiangular": 12, "hetero_mis": 13, "hetero_chromatic": 14})
+EXT_ESTIMATORS = ("hetero_equiangular", "hetero_mis", "hetero_chromatic")
+
+
+def set_ext_cloud(owner, block, interp, q=Q, colour=COLOUR):
+    """the cloud in EXT_LO .. EXT_HI, the track fraction and the medium colour on a Tracer or an Oracle"""
+    owner.set_density_grid(cloud()[0], EXT_LO, EXT_HI, majorant_block=block, interpolation=interp)
+    owner.set_hetero_mis_fraction(q)
+    owner.set_medium_colour(*colour)
+
+
+def reset_ext(owner):
+    """the defaults of what set_ext_cloud set, and no grid"""
+    owner.clear_density_grid()
+    owner.set_hetero_mis_fraction(0.5)
+    owner.set_medium_colour(*GREY)
