@@ -116,7 +116,7 @@ typedef enum {
                                     * expectation as estimators 10 and 12; q = 0 is estimator 12 bit for bit, q = 1
                                     * samples every distance by tracking; with an emission grid and in the accumulator
                                     * VPT_E_UNSUPPORTED; csrc/vpt_grid_mis.h, csrc/vpt_hetero_mis.h */
-    VPT_HETERO_CHROMATIC = 14      /* extension: VPT_HETERO_FREE in a chromatic medium -- the context's medium colour
+    VPT_HETERO_CHROMATIC = 14,     /* extension: VPT_HETERO_FREE in a chromatic medium -- the context's medium colour
                                     * (vpt_set_medium_colour) multiplies sigma_a and sigma_s per colour channel.  One
                                     * draw per decision picks a hero channel whose extinction drives the delta track
                                     * (the majorant block is honoured), and collisions, surfaces and every
@@ -128,8 +128,19 @@ typedef enum {
                                     * 10's bit for bit.  A channel without extinction is VPT_E_INVALID; with an
                                     * emission grid and in the accumulator VPT_E_UNSUPPORTED; csrc/vpt_grid_chroma.h,
                                     * csrc/vpt_hetero_chroma.h */
+    VPT_HETERO_RESIDUAL = 15       /* extension: VPT_HETERO_RATIO statement for statement, with every transmittance
+                                    * factor a residual ratio-tracking estimate: per super-voxel of the majorant block
+                                    * the minimum density is a control under the field, its part exp(-sigma_t mn len) of
+                                    * the transmittance is taken analytically, and only rho - mn is tracked against the
+                                    * residual majorant mu - mn -- fewer draws, weights nearer 1, zero variance where a
+                                    * block is uniform; the same expectation as estimators 10 and 11.  With an all-zero
+                                    * control grid it is estimator 11 bit for bit.  Needs a majorant block
+                                    * (vpt_set_grid_majorant_block; block 0 -> VPT_E_INVALID; a block >= the largest
+                                    * dimension is the global control); nearest and trilinear fields; with an emission
+                                    * grid and in the accumulator VPT_E_UNSUPPORTED; csrc/vpt_grid.h,
+                                    * csrc/vpt_hetero_residual.h */
 } vpt_estimator;
-#define VPT_NUM_ESTIMATORS 15
+#define VPT_NUM_ESTIMATORS 16
 
 typedef enum {
     VPT_FB_F32 = 0,            /* framebuffer: 3 x float per pixel */
@@ -203,7 +214,7 @@ typedef struct vpt_grid_desc {
  * or more than 2^27 voxels -> VPT_E_INVALID (the previous grid stays). */
 int vpt_set_density_grid(vpt_context* ctx, const vpt_grid_desc* desc, const float* density);
 /* Local majorants for the delta tracking of estimators VPT_HETERO_FREE and VPT_HETERO_RATIO (and the ratio tracking
- * of the latter; csrc/vpt_grid.h): the voxels are grouped
+ * of the latter; csrc/vpt_grid.h; VPT_HETERO_RESIDUAL needs them, and reads the block minima built beside them): the voxels are grouped
  * into cubic super-voxels of `block` voxels per axis, each with the maximum density of its voxels, and a track
  * steps with the majorant of the super-voxel it is in (empty ones are skipped).  Fewer null collisions on sparse
  * fields; the same estimator in distribution, other draws.  block 0 (the default) turns it off: the single
@@ -413,6 +424,18 @@ int vpt_grid_probe_host_ex(const vpt_grid_desc* desc, const float* density, int 
 int vpt_grid_ratio_probe_host_ex(const vpt_grid_desc* desc, const float* density, int block, int interp, double sigma_t,
                                  const vpt_ray* rays, const double* tmax, const uint64_t* states, int n, double* that,
                                  uint64_t* states_out, uint32_t* steps);
+/* Residual ratio-tracking probe (csrc/vpt_grid.h: vpt_grid_residual_lm_m; estimator VPT_HETERO_RESIDUAL's transmittance):
+ * that[i] = the estimate of exp(-sigma_t tau) over t in [0, tmax[i]] from states[i] (in [0, exp(-sigma_t tauc[i])]; NaN:
+ * the 2^22-step cap), tauc[i] = the control optical depth the walk took analytically (the block minima integrated over
+ * the part of the segment inside the box; up to the tentative point where that[i] is +0), states_out[i] = the state after
+ * it, steps[i] (may be NULL) = its draws.  The GPU probe reads the context's grid, majorant block and interpolation:
+ * without a grid or with block 0 -> VPT_E_INVALID.  The host probe takes them as arguments: block < 1, a bad grid or a bad
+ * mode -> VPT_E_INVALID.  Host arrays, synchronous. */
+int vpt_grid_residual_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
+                            int n, double* that, double* tauc, uint64_t* states_out, uint32_t* steps);
+int vpt_grid_residual_probe_host(const vpt_grid_desc* desc, const float* density, int block, int interp, double sigma_t,
+                                 const vpt_ray* rays, const double* tmax, const uint64_t* states, int n, double* that,
+                                 double* tauc, uint64_t* states_out, uint32_t* steps);
 
 /* Emission probe (csrc/vpt_grid.h: vpt_grid_track_em_m, vpt_grid_track_lm_em_m): the delta track of vpt_grid_probe_lm from
  * states[i] over t in [0, tmax[i]] with the collision estimator of the emission grid: t_coll[i], states_out[i] and steps[i]

@@ -28,6 +28,7 @@ HETERO_RATIO = 11
 HETERO_EQUIANGULAR = 12
 HETERO_MIS = 13
 HETERO_CHROMATIC = 14
+HETERO_RESIDUAL = 15
 FB_F32, FB_F64 = 0, 1
 GRID_NEAREST, GRID_TRILINEAR = 0, 1  # vpt_grid_interp
 
@@ -163,6 +164,10 @@ PROTOTYPES = [
                                        c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vpt_grid_ratio_probe_host_ex", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_int, c_double, c_void_p, c_void_p,
                                              c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    ("vpt_grid_residual_probe", c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
+    ("vpt_grid_residual_probe_host", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_int, c_double, c_void_p, c_void_p,
+                                             c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vpt_grid_eqa_probe", c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vpt_grid_eqa_probe_host", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p,

@@ -109,6 +109,34 @@
  * the product is exact, and with mu == rho the score is eps bit for bit.  E[esum] = sigma_t * integral of
  * T(t) rho(t) eps(t) dt over the tracked segment, T = exp(-sigma_t tau): a tentative point falls into dt with probability
  * density T_mu(t) mu sigma_t summed over the null-collision histories, which is sigma_t mu T(t) once the nulls are weighed.
+ *
+ * Residual ratio tracking (Novak et al. 2014, section 5.1; vpt_grid_residual_lm_m; estimator 15, vpt_hetero_residual.h): ratio
+ * tracking with local majorants over a control density under the field.  Beside the block maxima the host builds the block
+ * minima ctl[bz][by][bx], the float32 minimum of rho over the super-voxel (vpt_grid_control_build; under the trilinear field
+ * over the block dilated by one voxel on every side, vpt_grid_control_build_tl, as the maxima are); they lie directly behind
+ * the nbv = nb[0] nb[1] nb[2] maxima of the majorant allocation, ctl = maj + nbv, and the walker takes the pointer as an
+ * argument of its own (vpt_grid_fields is what it was).  In a block with minimum mn and majorant mu the part
+ * exp(-sigma_t mn len) of the transmittance is taken analytically and only the residual rho - mn is tracked, against the
+ * residual majorant mr = mu - mn.  The walk is vpt_grid_ratio_lm_m's statement for statement -- the entry tests (1.0 with no
+ * draw, *tauc = +0.0), the DDA, the eager draw rem = -log(1 - xi) at the head of each tentative step, the caps -- with:
+ *   per super-voxel entered (te > t): mn = (double)ctl[idx] beside mu; mr = mu - mn; !(mr > 0.0): skipped -- no candidate,
+ *        rem untouched; else s = mr * sigma_t, tc = t + (rem / s), tested and rem reduced as before
+ *   the control optical depth tauc, from +0.0, takes tauc = tauc + mn * (e - t) for every stretch [t, e] the walk passes in a
+ *        block, in traversal order: up to a block's exit plane (e = min(te, tend), tend = min(tmax, t1), only where e > t, before
+ *        t = te); up to a tentative point that passed the boundary test (e = tc, after the test, before the lookup); and where
+ *        the boundary test rejects the tentative point, up to tend (only where tend > t).  So at every "none" exit tauc is mn
+ *        integrated over [t0, tend], skipped and uniform blocks included; at the +0.0 exit it is the integral up to the
+ *        tentative point; a walk that runs into the crossing cap returns what it has
+ *   at a tentative point with density rho: rho >= mu returns +0.0; else if (rho > mn) That = That * (1.0 - (rho - mn) / mr)
+ *        (a trilinear lookup may fall an ulp below the smallest of its corners as it may rise above the largest: hence the
+ *        test, not an unconditional multiply, and the weight stays in [0, 1]); t = tc and the walk goes on.  No second draw:
+ *        `steps` is the number of draws
+ *   every "none" exit returns That * exp(sigma_t * tauc * -1.0) (vpt_grid_transmittance's operand order); a capped walk NaN.
+ * Two identities follow.  (i) With ctl == 0 in every block the value, the end state and the step count are
+ * vpt_grid_ratio_lm_m's bit for bit: mu - 0.0 == mu, (rho - 0.0) / mu == rho / mu, the multiply by 1.0 that is skipped at
+ * rho == 0 changes no bit, and That * exp(-0) == That.  (ii) Where every super-voxel is uniform (mn == mu) no block has a
+ * candidate: the walk takes exactly one draw and returns exp(-sigma_t tauc), the exact transmittance up to the order of the
+ * sum, with zero variance -- at B = 1 under the nearest lookup on every field.  The estimate lies in [0, exp(-sigma_t tauc)].
  */
 #ifndef VPT_GRID_H
 #define VPT_GRID_H
@@ -243,6 +271,66 @@ static inline void vpt_grid_majorant_build_tl(const int32_t n[3], int32_t B, con
                     }
             }
         }
+    }
+}
+
+/* host: the block minima of `density` into out, the layout and the blocks of vpt_grid_majorant_build: the control grid of
+ * residual ratio tracking (header comment).  Every block holds a voxel, so every minimum is a voxel's value */
+static inline void vpt_grid_control_build(const int32_t n[3], int32_t B, const float* density, float* out)
+{
+    int32_t nb[3];
+    vpt_grid_majorant_counts(n, B, nb);
+    const int64_t nbv = (int64_t)nb[0] * nb[1] * nb[2];
+    for (int64_t i = 0; i < nbv; ++i) out[i] = INFINITY;
+    for (int32_t z = 0; z < n[2]; ++z)
+        for (int32_t y = 0; y < n[1]; ++y) {
+            const float* row = density + ((int64_t)z * n[1] + y) * n[0];
+            float* orow = out + ((int64_t)(z / B) * nb[1] + y / B) * nb[0];
+            for (int32_t x = 0; x < n[0]; ++x)
+                if (row[x] < orow[x / B]) orow[x / B] = row[x];
+        }
+}
+
+/* the same for the trilinear field: every block's minimum over its voxels dilated by one voxel on every side, as
+ * vpt_grid_majorant_build_tl dilates the maximum */
+static inline void vpt_grid_control_build_tl(const int32_t n[3], int32_t B, const float* density, float* out)
+{
+    int32_t nb[3];
+    vpt_grid_majorant_counts(n, B, nb);
+    const int64_t nbv = (int64_t)nb[0] * nb[1] * nb[2];
+    for (int64_t i = 0; i < nbv; ++i) out[i] = INFINITY;
+    for (int32_t z = 0; z < n[2]; ++z) {
+        const int32_t bz0 = (z > 0 ? z - 1 : 0) / B, bz1 = (z + 1 < n[2] ? z + 1 : n[2] - 1) / B;
+        for (int32_t y = 0; y < n[1]; ++y) {
+            const int32_t by0 = (y > 0 ? y - 1 : 0) / B, by1 = (y + 1 < n[1] ? y + 1 : n[1] - 1) / B;
+            const float* row = density + ((int64_t)z * n[1] + y) * n[0];
+            for (int32_t x = 0; x < n[0]; ++x) {
+                const int32_t bx0 = (x > 0 ? x - 1 : 0) / B, bx1 = (x + 1 < n[0] ? x + 1 : n[0] - 1) / B;
+                for (int32_t bz = bz0; bz <= bz1; ++bz)
+                    for (int32_t by = by0; by <= by1; ++by) {
+                        float* orow = out + ((int64_t)bz * nb[1] + by) * nb[0];
+                        for (int32_t bx = bx0; bx <= bx1; ++bx)
+                            if (row[x] < orow[bx]) orow[bx] = row[x];
+                    }
+            }
+        }
+    }
+}
+
+/* host: the majorant allocation of block size B >= 1 as the context and the host probes keep it -- the nbv block maxima and
+ * directly behind them the nbv block minima (out: 2 nbv floats), for the nearest (tl == 0) or the trilinear field.  The
+ * view's maj points at the first half; the residual walker's ctl is vpt_grid_control_of */
+static inline void vpt_grid_majorant_control_build(const int32_t n[3], int32_t B, int tl, const float* density, float* out)
+{
+    int32_t nb[3];
+    vpt_grid_majorant_counts(n, B, nb);
+    const int64_t nbv = (int64_t)nb[0] * nb[1] * nb[2];
+    if (tl) {
+        vpt_grid_majorant_build_tl(n, B, density, out);
+        vpt_grid_control_build_tl(n, B, density, out + nbv);
+    } else {
+        vpt_grid_majorant_build(n, B, density, out);
+        vpt_grid_control_build(n, B, density, out + nbv);
     }
 }
 
@@ -596,6 +684,101 @@ VPT_GR double vpt_grid_ratio_lm_m(const vpt_grid_fields* G, const int tl, const 
         That = That * (1.0 - rho / mu);
         t = tc;
     }
+    return (double)NAN;
+}
+
+/* the control grid behind the majorants of a view with a majorant grid (header comment): ctl = maj + nbv */
+VPT_GR const float* vpt_grid_control_of(const vpt_grid_fields* G)
+{
+    return G->maj + (int64_t)G->nb[0] * G->nb[1] * G->nb[2];
+}
+
+/* residual ratio tracking over the block minima ctl (header comment; G->block >= 1): vpt_grid_ratio_lm_m's arguments and
+ * results, and the control optical depth in *tauc_out.  The walk is that walker's, restated */
+VPT_GR double vpt_grid_residual_lm_m(const vpt_grid_fields* G, const float* ctl, const int tl, const double o[3], const double d[3],
+                                   double tmax, double sigma_t, uint64_t* X, uint32_t* steps, double* tauc_out)
+{
+    double t0, t1;
+    if (steps) *steps = 0;
+    *tauc_out = 0.0;
+    if (!(G->rho_max > 0.0)) return 1.0;
+    if (!vpt_grid_slab(G, o, d, &t0, &t1)) return 1.0;
+    const double tend = t1 < tmax ? t1 : tmax;
+    int i[3], step[3];
+    double tn[3], inv[3];
+    for (int a = 0; a < 3; ++a) {
+        i[a] = vpt_grid_axis_index(G, a, o[a] + d[a] * t0) / G->block;
+        step[a] = d[a] > 0.0 ? 1 : (d[a] < 0.0 ? -1 : 0);
+        inv[a] = step[a] ? 1.0 / d[a] : 0.0;
+        tn[a] = step[a] ? (vpt_grid_block_plane(G, a, i[a] + (step[a] > 0)) - o[a]) * inv[a] : VPT_GRID_BIG;
+    }
+    const int max_cross = G->nb[0] + G->nb[1] + G->nb[2] + 4;
+    double t = t0, That = 1.0, tauc = 0.0;
+    int a = tn[0] <= tn[1] ? (tn[0] <= tn[2] ? 0 : 2) : (tn[1] <= tn[2] ? 1 : 2);
+    double te = tn[a];
+    double mu = 0.0, mn = 0.0;
+    if (te > t) {
+        const int64_t idx = ((int64_t)i[2] * G->nb[1] + i[1]) * G->nb[0] + i[0];
+        mu = (double)G->maj[idx];
+        mn = (double)ctl[idx];
+    }
+    for (int k = 0; k < VPT_GRID_MAX_TRACK_STEPS; ++k) {
+        double rem = -VPT_GRID_LOG(1 - vpt_erand48(X));
+        if (steps) *steps = (uint32_t)(k + 1);
+        double tc = 0.0;
+        int c = 0;
+        for (; c < max_cross; ++c) {
+            if (te > t) {
+                const double mr = mu - mn;
+                if (mr > 0.0) {
+                    const double s = mr * sigma_t;
+                    tc = t + (rem / s);
+                    if (tc < te) break;  /* a tentative collision */
+                    rem = rem - s * (te - t);
+                }
+                const double e = te < tend ? te : tend;
+                if (e > t) tauc = tauc + mn * (e - t);
+                t = te;
+            }
+            if (!(te < t1) || te > tmax) {
+                *tauc_out = tauc;
+                return That * VPT_GRID_EXP(sigma_t * tauc * -1.0);
+            }
+            i[a] += step[a];
+            if (i[a] < 0 || i[a] >= G->nb[a]) {
+                *tauc_out = tauc;
+                return That * VPT_GRID_EXP(sigma_t * tauc * -1.0);
+            }
+            tn[a] = (vpt_grid_block_plane(G, a, i[a] + (step[a] > 0)) - o[a]) * inv[a];
+            a = tn[0] <= tn[1] ? (tn[0] <= tn[2] ? 0 : 2) : (tn[1] <= tn[2] ? 1 : 2);
+            te = tn[a];
+            mu = 0.0;
+            mn = 0.0;
+            if (te > t) {
+                const int64_t idx = ((int64_t)i[2] * G->nb[1] + i[1]) * G->nb[0] + i[0];
+                mu = (double)G->maj[idx];
+                mn = (double)ctl[idx];
+            }
+        }
+        if (c == max_cross) {
+            *tauc_out = tauc;
+            return That * VPT_GRID_EXP(sigma_t * tauc * -1.0);
+        }
+        if (tc > tmax || tc >= t1) {
+            if (tend > t) tauc = tauc + mn * (tend - t);
+            *tauc_out = tauc;
+            return That * VPT_GRID_EXP(sigma_t * tauc * -1.0);
+        }
+        tauc = tauc + mn * (tc - t);
+        const double rho = vpt_grid_lookup(G, tl, o[0] + d[0] * tc, o[1] + d[1] * tc, o[2] + d[2] * tc);
+        if (rho >= mu) {
+            *tauc_out = tauc;
+            return 0.0;
+        }
+        if (rho > mn) That = That * (1.0 - (rho - mn) / (mu - mn));
+        t = tc;
+    }
+    *tauc_out = tauc;
     return (double)NAN;
 }
 

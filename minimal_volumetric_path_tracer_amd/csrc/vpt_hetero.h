@@ -325,7 +325,7 @@ struct vpt_hetero_args {
 
 /* What a code object of the density-grid estimators exports: its launches.  One table per unit -- vpt_hetero.hip's four
  * are the values of (TL, EM), nearest or trilinear lookup (the view's interp word) without or with the emission grid;
- * estimator 12's, 13's and 14's units the two values of TL -- and the caller picks the table in one place (vpt_kernels.hip
+ * estimator 12's, 13's, 14's and 15's units the two values of TL -- and the caller picks the table in one place (vpt_kernels.hip
  * hetero_unit).  A probe the unit does not hold is NULL. */
 struct vpt_hetero_unit {
     /* the persistent-wave render kernel of the unit's estimator (K.est where it holds two), enqueued on `stream` (the
@@ -360,6 +360,10 @@ struct vpt_hetero_unit {
     void (*grid_chroma_probe_launch)(const vpt_grid_view* grid, bool lm, const vpt::ChromaCoef& c, const vpt_ray* rays,
                                      const double* tmax, const uint64_t* states, int n, double* res, int32_t* hero,
                                      uint32_t* steps, uint64_t* states_out);
+    /* estimator 15's (vpt_grid.h: vpt_grid_residual_lm_m); the view holds a majorant grid */
+    void (*grid_residual_probe_launch)(const vpt_grid_view* grid, double sigma_t, const vpt_ray* rays, const double* tmax,
+                                       const uint64_t* states, int n, double* that, double* tauc, uint64_t* states_out,
+                                       uint32_t* steps);
 };
 extern const vpt_hetero_unit vpt_int_hetero_unit;            /* vpt_hetero.hip: TL = false, EM = false */
 extern const vpt_hetero_unit vpt_int_hetero_unit_tl;         /* vpt_hetero_tl.hip: TL = true, the view's interp == 1 */
@@ -371,5 +375,7 @@ extern const vpt_hetero_unit vpt_int_hetero_mis_unit;        /* vpt_hetero_mis.h
 extern const vpt_hetero_unit vpt_int_hetero_mis_unit_tl;
 extern const vpt_hetero_unit vpt_int_hetero_chroma_unit;     /* vpt_hetero_chroma.hip, vpt_hetero_chroma_tl.hip */
 extern const vpt_hetero_unit vpt_int_hetero_chroma_unit_tl;
+extern const vpt_hetero_unit vpt_int_hetero_residual_unit;   /* vpt_hetero_residual.hip, vpt_hetero_residual_tl.hip */
+extern const vpt_hetero_unit vpt_int_hetero_residual_unit_tl;
 
 #endif

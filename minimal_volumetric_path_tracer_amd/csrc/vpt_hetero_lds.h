@@ -65,6 +65,38 @@ __device__ __forceinline__ void stage_grid_lds(GV& G)
 #endif
 }
 
+/* The prologue of estimator 15's kernels (vpt_hetero_residual.hip), in stage_grid_lds's place: the same budget, with the
+ * control grid beside the majorants.  ctl is the policy's own pointer to the block minima, taken from the view before
+ * this runs (in global memory they lie directly behind the nbv majorants, vpt_grid.h, so the two arrays are one copy).
+ * The density is staged where it fits, as above; the majorants and the minima go into what it left when that holds
+ * both; else the majorants alone where they fit, as above, and the minima are read from global memory */
+template <class GV>
+__device__ __forceinline__ void stage_grid_control_lds(GV& G, const float*& ctl)
+{
+#if VPT_HETERO_LDS
+    __shared__ float lds_rho[VPT_HETERO_LDS_BYTES / sizeof(float)];
+    const int64_t cap = (int64_t)(VPT_HETERO_LDS_BYTES / sizeof(float));
+    const int64_t nv = (int64_t)G.n[0] * G.n[1] * G.n[2];
+    const int64_t used = nv <= cap ? nv : 0;
+    if (used) {  /* workgroup-uniform, like every test below */
+        for (int k = threadIdx.x; k < (int)nv; k += blockDim.x) lds_rho[k] = G.rho[k];
+        G.rho = lds_rho;
+    }
+#if VPT_HETERO_LDS_MAJ
+    const int64_t nbv = (int64_t)G.nb[0] * G.nb[1] * G.nb[2];
+    if (2 * nbv <= cap - used) {
+        for (int k = threadIdx.x; k < (int)(2 * nbv); k += blockDim.x) lds_rho[used + k] = G.maj[k];
+        G.maj = lds_rho + used;
+        ctl = lds_rho + used + nbv;
+    } else if (nbv <= cap - used) {
+        for (int k = threadIdx.x; k < (int)nbv; k += blockDim.x) lds_rho[used + k] = G.maj[k];
+        G.maj = lds_rho + used;
+    }
+#endif
+    __syncthreads();
+#endif
+}
+
 }  // namespace vpt
 
 #endif

@@ -326,6 +326,42 @@ static int grid_ratio_probe_host(const char* who, const vpt_grid_desc* desc, con
     return VPT_OK;
 }
 
+int vpt_grid_residual_probe_host(const vpt_grid_desc* desc, const float* density, int block, int interp, double sigma_t,
+                                 const vpt_ray* rays, const double* tmax, const uint64_t* states, int n, double* that,
+                                 double* tauc, uint64_t* states_out, uint32_t* steps)
+{
+    const char* who = "vpt_grid_residual_probe_host";
+    vpt_clear_error();
+    if (!rays || !tmax || !states || n < 0) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
+    if (block < 1) return vpt_fail(VPT_E_INVALID, "%s: block %d (>= 1: the control grid is per super-voxel)", who, block);
+    if (interp != VPT_GRID_NEAREST && interp != VPT_GRID_TRILINEAR)
+        return vpt_fail(VPT_E_INVALID, "%s: interp %d (0 = nearest, 1 = trilinear)", who, interp);
+    int rc = vpt_int_grid_check(desc, density, who);
+    if (rc) return rc;
+    /* the view with the majorant allocation as the context keeps it: the maxima, and behind them the minima */
+    const int32_t dims[3] = {desc->nx, desc->ny, desc->nz};
+    vpt_grid_view G;
+    vpt_grid_view_init(&G, dims, desc->lo, desc->hi, density, density);
+    G.interp = interp;
+    int32_t nb[3];
+    vpt_grid_majorant_counts(dims, block, nb);
+    std::vector<float> maj(2 * (size_t)nb[0] * (size_t)nb[1] * (size_t)nb[2]);
+    vpt_grid_majorant_control_build(dims, block, interp, density, maj.data());
+    vpt_grid_view_set_majorant(&G, block, maj.data());
+    const float* ctl = vpt_grid_control_of(&G);
+    for (int i = 0; i < n; ++i) {
+        uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
+        uint32_t ns = 0;
+        double tc = 0.0;
+        const double T = vpt_grid_residual_lm_m(&G, ctl, interp, rays[i].o, rays[i].d, tmax[i], sigma_t, &X, &ns, &tc);
+        if (that) that[i] = T;
+        if (tauc) tauc[i] = tc;
+        if (states_out) states_out[i] = X;
+        if (steps) steps[i] = ns;
+    }
+    return VPT_OK;
+}
+
 int vpt_grid_probe_host(const vpt_grid_desc* desc, const float* density, double sigma_t, const vpt_ray* rays,
                         const double* tmax, const uint64_t* states, int n, double* tau, double* t_coll,
                         uint64_t* states_out)

@@ -396,7 +396,7 @@ static ChromaCoef chroma_coef(const vpt_context* ctx, double sigma_a, double sig
  * (include/rayMarchingMethods.h:64,153), so the scene needs at least 6 spheres */
 static int check_march(const vpt_context* ctx, const vpt_medium* m)
 {
-    if (m->estimator >= VPT_HETERO_FREE && m->estimator <= VPT_HETERO_CHROMATIC) {
+    if (m->estimator >= VPT_HETERO_FREE && m->estimator <= VPT_HETERO_RESIDUAL) {
         if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "estimator %d needs a density grid (vpt_set_density_grid)", m->estimator);
         if (m->estimator == VPT_HETERO_CHROMATIC) {
             if (ctx->h_grid.emit)  /* the emitting track's weight under a hero channel is not worked out */
@@ -410,9 +410,13 @@ static int check_march(const vpt_context* ctx, const vpt_medium* m)
             return VPT_OK;
         }
         /* emission is scored on a delta track, which estimator 12 does not run and estimator 13 runs only in part */
-        if ((m->estimator == VPT_HETERO_EQUIANGULAR || m->estimator == VPT_HETERO_MIS) && ctx->h_grid.emit)
+        if ((m->estimator == VPT_HETERO_EQUIANGULAR || m->estimator == VPT_HETERO_MIS || m->estimator == VPT_HETERO_RESIDUAL) &&
+            ctx->h_grid.emit)
             return vpt_fail(VPT_E_UNSUPPORTED, "estimator %d does not score an emission grid (estimators 10 and 11 do)",
                             m->estimator);
+        if (m->estimator == VPT_HETERO_RESIDUAL && ctx->h_grid.block < 1)  /* the control grid lies behind the majorants */
+            return vpt_fail(VPT_E_INVALID, "estimator %d needs a majorant block (vpt_set_grid_majorant_block; a block >= the "
+                            "grid's largest dimension is the global control)", m->estimator);
         return VPT_OK;
     }
     if (m->estimator < VPT_RAY_MARCHING) return VPT_OK;
@@ -554,7 +558,7 @@ static bool hetero_simple_kernel()
 }
 
 /* The code object that holds an estimator's kernels for a lookup (tl: trilinear) and, for estimators 10 and 11, a medium
- * without or with emission (vpt_hetero.h); estimators 12 to 14 take the lookup alone.  The one place where the settings
+ * without or with emission (vpt_hetero.h); estimators 12 to 15 take the lookup alone.  The one place where the settings
  * turn into a unit: every launch below goes through the table returned here.  A probe names its estimator's unit, and
  * the two grid probes exist in the units without emission only, so their callers pass em = false whatever the context
  * holds. */
@@ -564,6 +568,7 @@ static const vpt_hetero_unit& hetero_unit(int est, bool tl, bool em)
     case VPT_HETERO_EQUIANGULAR: return tl ? vpt_int_hetero_eqa_unit_tl : vpt_int_hetero_eqa_unit;
     case VPT_HETERO_MIS: return tl ? vpt_int_hetero_mis_unit_tl : vpt_int_hetero_mis_unit;
     case VPT_HETERO_CHROMATIC: return tl ? vpt_int_hetero_chroma_unit_tl : vpt_int_hetero_chroma_unit;
+    case VPT_HETERO_RESIDUAL: return tl ? vpt_int_hetero_residual_unit_tl : vpt_int_hetero_residual_unit;
     default: break;  /* 10 and 11 */
     }
     if (em) return tl ? vpt_int_hetero_unit_em_tl : vpt_int_hetero_unit_em;
@@ -581,8 +586,8 @@ static vpt_hetero_args hetero_args(const vpt_context* ctx, double sigma_a, doubl
 }
 
 /* estimators 10, 11 (by K.est: hetero_kernel / hetero_ratio_kernel), 12 (hetero_eqa_kernel; the majorant block plays no
- * part), 13 (hetero_mis_kernel, with the context's track fraction) and 14 (hetero_chroma_kernel, with the coefficients
- * of the context's medium colour) on the stream's queue word; counting mode and
+ * part), 13 (hetero_mis_kernel, with the context's track fraction), 14 (hetero_chroma_kernel, with the coefficients
+ * of the context's medium colour) and 15 (hetero_residual_kernel) on the stream's queue word; counting mode and
  * VPT_SIMPLE_KERNEL=1: render_kernel_simple<K.est> */
 static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
 {
@@ -809,6 +814,7 @@ static int launch_render(vpt_context* ctx, KParams K, hipStream_t stream)
         VPT_LAUNCH_EST(12)
         VPT_LAUNCH_EST(13)
         VPT_LAUNCH_EST(14)
+        VPT_LAUNCH_EST(15)
     }
 #undef VPT_LAUNCH_EST
     return vpt_fail(VPT_E_INVALID, "unknown estimator %d", K.est);
@@ -962,14 +968,14 @@ int vpt_set_scene(vpt_context* ctx, const vpt_sphere* s, int n)
 }
 
 /* the block maxima of `density` (host) for block size B >= 1 on the device (*d_maj, the caller frees) and in
- * the view; the dilated maxima where the view's field is trilinear (vpt_grid.h) */
+ * the view; the dilated maxima where the view's field is trilinear (vpt_grid.h).  Directly behind them, in the same
+ * allocation, the block minima: estimator 15's control grid (vpt_grid_control_of), built whenever the maxima are */
 static hipError_t majorant_upload(vpt_grid_view* G, int B, const float* density, float** d_maj)
 {
     int32_t nb[3];
     vpt_grid_majorant_counts(G->n, B, nb);
-    std::vector<float> maj((size_t)nb[0] * (size_t)nb[1] * (size_t)nb[2]);
-    if (G->interp) vpt_grid_majorant_build_tl(G->n, B, density, maj.data());
-    else vpt_grid_majorant_build(G->n, B, density, maj.data());
+    std::vector<float> maj(2 * (size_t)nb[0] * (size_t)nb[1] * (size_t)nb[2]);
+    vpt_grid_majorant_control_build(G->n, B, G->interp, density, maj.data());
     hipError_t e = hipMalloc((void**)d_maj, maj.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(*d_maj, maj.data(), maj.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) vpt_grid_view_set_majorant(G, B, *d_maj);
@@ -1342,6 +1348,36 @@ int vpt_grid_chroma_probe(vpt_context* ctx, double sigma_a, double sigma_s, cons
     return st.status("vpt_grid_chroma_probe");
 }
 
+int vpt_grid_residual_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
+                            int n, double* that, double* tauc, uint64_t* states_out, uint32_t* steps)
+{
+    vpt_clear_error();
+    if (!ctx || !rays || !tmax || !states || !that || !tauc || !states_out || n < 0)
+        return vpt_fail(VPT_E_INVALID, "vpt_grid_residual_probe: bad arguments");
+    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "vpt_grid_residual_probe: no density grid set (vpt_set_density_grid)");
+    if (ctx->h_grid.block < 1)
+        return vpt_fail(VPT_E_INVALID, "vpt_grid_residual_probe: no majorant block set (vpt_set_grid_majorant_block)");
+    if (n == 0) return VPT_OK;
+    HIP_OK(hipSetDevice(ctx->device));
+    Staging st;
+    const size_t nn = (size_t)n;
+    vpt_ray* dr = st.alloc<vpt_ray>(nn);
+    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn);
+    double *dtm = st.alloc<double>(nn), *dth = st.alloc<double>(nn), *dtc = st.alloc<double>(nn);
+    uint32_t* dst = st.alloc_if(steps, nn);
+    st.up(dr, rays, nn);
+    st.up(ds, states, nn);
+    st.up(dtm, tmax, nn);
+    st.launch([&] {
+        hetero_unit(ctx, VPT_HETERO_RESIDUAL).grid_residual_probe_launch(ctx->d_grid, sigma_t, dr, dtm, ds, n, dth, dtc, dso, dst);
+    });
+    st.down(that, dth, nn);
+    st.down(tauc, dtc, nn);
+    st.down(states_out, dso, nn);
+    st.down(steps, dst, nn);
+    return st.status("vpt_grid_residual_probe");
+}
+
 int vpt_grid_emission_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
                             int n, double* t_coll, double* esum, uint64_t* states_out, uint32_t* steps)
 {
@@ -1486,6 +1522,7 @@ static int trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* ray
         case VPT_HETERO_EQUIANGULAR:
         case VPT_HETERO_MIS:
         case VPT_HETERO_CHROMATIC:
+        case VPT_HETERO_RESIDUAL:
             hetero_unit(ctx, m->estimator).trace_launch(m->estimator, dr, ds, n, mm, ctx->d_scene, ctx->d_grid,
                                                         hetero_args(ctx, m->sigma_a, m->sigma_s, stats), dout, dso);
             break;

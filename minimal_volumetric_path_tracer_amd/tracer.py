@@ -23,7 +23,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (EXPLICIT_EQUIANGULAR, EXPLICIT_FREE, FB_F32, FB_F64, FREE_FLIGHT, HETERO_EQUIANGULAR, HETERO_CHROMATIC, HETERO_FREE, HETERO_MIS, HETERO_RATIO, IMPLICIT_FREE, MIS_EQUIANGULAR,
+from ._lib import (EXPLICIT_EQUIANGULAR, EXPLICIT_FREE, FB_F32, FB_F64, FREE_FLIGHT, HETERO_EQUIANGULAR, HETERO_CHROMATIC, HETERO_FREE, HETERO_MIS, HETERO_RATIO, HETERO_RESIDUAL, IMPLICIT_FREE, MIS_EQUIANGULAR,
                    RAY_DTYPE, RAY_MARCHING, RAY_MARCHING_EXPLICIT, RAY_MARCHING_GLOBAL, RAY_MARCHING_SA, SPHERE_DTYPE,
                    SURFACE_PT, check, lib)
 
@@ -34,7 +34,8 @@ ESTIMATORS = {"ff": FREE_FLIGHT, "free_flight": FREE_FLIGHT, "mis": MIS_EQUIANGU
               "ray_marching_explicit": RAY_MARCHING_EXPLICIT, "hetero": HETERO_FREE, "hetero_free": HETERO_FREE,
               "hetero_ratio": HETERO_RATIO, "hetero_equiangular": HETERO_EQUIANGULAR, "hetero_eqa": HETERO_EQUIANGULAR,
               "hetero_mis": HETERO_MIS, "hetero_mis_equiangular": HETERO_MIS,
-              "hetero_chromatic": HETERO_CHROMATIC, "hetero_rgb": HETERO_CHROMATIC}
+              "hetero_chromatic": HETERO_CHROMATIC, "hetero_rgb": HETERO_CHROMATIC,
+              "hetero_residual": HETERO_RESIDUAL, "hetero_residual_ratio": HETERO_RESIDUAL}
 
 
 def Sphere(r, p, c=(0, 0, 0), radiance=(0, 0, 0), material=0, eta=(0, 0, 0), kappa=(0, 0, 0), alpha=0.0) -> np.ndarray:
@@ -145,6 +146,22 @@ def grid_ratio_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, states, major
                                           t.ctypes.data, s.ctypes.data, len(ry), that.ctypes.data, so.ctypes.data,
                                           steps.ctypes.data))
     return that, so, steps
+
+
+def grid_residual_probe_host(rho, lo, hi, sigma_t: float, rays, tmax, states, majorant_block: int = 0,
+                             interpolation: str = "nearest"):
+    """csrc/vpt_grid.h's residual ratio tracking on the host (vpt_grid_residual_probe_host, no GPU): per ray (unit
+    direction) the estimate That of exp(-sigma_t tau) over t in [0, tmax] from `states` (NaN: step cap), the control
+    optical depth tauc taken analytically, the erand48 states after the walk and its draws.  majorant_block >= 1 is
+    required (the control is the minimum of each super-voxel); interpolation "trilinear" reads the field trilinearly."""
+    mode = _interp_mode(interpolation)
+    d, r = _grid_args(rho, lo, hi)
+    ry, t, s, that, tauc, so = _probe_args(rays, tmax, states)
+    steps = np.zeros(len(ry), dtype=np.uint32)
+    check(lib().vpt_grid_residual_probe_host(byref(d), r.ctypes.data, int(majorant_block), mode, float(sigma_t),
+                                             ry.ctypes.data, t.ctypes.data, s.ctypes.data, len(ry), that.ctypes.data,
+                                             tauc.ctypes.data, so.ctypes.data, steps.ctypes.data))
+    return that, tauc, so, steps
 
 
 def _eqa_probe_args(rays, tmax, light, states):
@@ -441,6 +458,15 @@ class Tracer:
         check(lib().vpt_grid_ratio_probe(self._ctx, float(sigma_t), ry.ctypes.data, t.ctypes.data, s.ctypes.data, len(ry),
                                          that.ctypes.data, so.ctypes.data, steps.ctypes.data))
         return that, so, steps
+
+    def grid_residual_probe(self, sigma_t: float, rays, tmax, states):
+        """grid_residual_probe_host's quantities for the tracer's grid, majorant block and interpolation, computed on
+        the GPU (vpt_grid_residual_probe): (That, tauc, states, steps)."""
+        ry, t, s, that, tauc, so = _probe_args(rays, tmax, states)
+        steps = np.zeros(len(ry), dtype=np.uint32)
+        check(lib().vpt_grid_residual_probe(self._ctx, float(sigma_t), ry.ctypes.data, t.ctypes.data, s.ctypes.data, len(ry),
+                                            that.ctypes.data, tauc.ctypes.data, so.ctypes.data, steps.ctypes.data))
+        return that, tauc, so, steps
 
     def grid_eqa_probe(self, sigma_t: float, rays, tmax, light, states):
         """grid_eqa_probe_host's quantities for the tracer's grid and interpolation, computed on the GPU
