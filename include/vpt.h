@@ -128,7 +128,7 @@ typedef enum {
                                     * 10's bit for bit.  A channel without extinction is VPT_E_INVALID; with an
                                     * emission grid and in the accumulator VPT_E_UNSUPPORTED; csrc/vpt_grid_chroma.h,
                                     * csrc/vpt_hetero_chroma.h */
-    VPT_HETERO_RESIDUAL = 15       /* extension: VPT_HETERO_RATIO statement for statement, with every transmittance
+    VPT_HETERO_RESIDUAL = 15,      /* extension: VPT_HETERO_RATIO statement for statement, with every transmittance
                                     * factor a residual ratio-tracking estimate: per super-voxel of the majorant block
                                     * the minimum density is a control under the field, its part exp(-sigma_t mn len) of
                                     * the transmittance is taken analytically, and only rho - mn is tracked against the
@@ -139,8 +139,21 @@ typedef enum {
                                     * dimension is the global control); nearest and trilinear fields; with an emission
                                     * grid and in the accumulator VPT_E_UNSUPPORTED; csrc/vpt_grid.h,
                                     * csrc/vpt_hetero_residual.h */
+    VPT_HETERO_SPECTRAL = 16       /* extension: VPT_HETERO_RATIO in the chromatic medium of VPT_HETERO_CHROMATIC (the
+                                    * context's medium colour, vpt_set_medium_colour) by spectral tracking: every
+                                    * decision tracks once under the largest channel's extinction and carries a weight
+                                    * per channel (the history-aware average variant: the weights of a path that
+                                    * carries (1, 1, 1) sum to 3 and none exceeds 3), and every transmittance factor is
+                                    * a chromatic ratio-tracking estimate, three products from one walk.  No walk of the
+                                    * grid's optical depth is left, so the cost follows the majorant optical depth and
+                                    * not the resolution.  The same expectation per channel as estimator 14.  With
+                                    * equal extinctions in the three channels (the default colour among them) it is
+                                    * estimator 11 bit for bit.  The majorant block is honoured; nearest and trilinear
+                                    * fields.  A channel without extinction is VPT_E_INVALID; with an emission grid and
+                                    * in the accumulator VPT_E_UNSUPPORTED; csrc/vpt_grid_spectral.h,
+                                    * csrc/vpt_hetero_spectral.h */
 } vpt_estimator;
-#define VPT_NUM_ESTIMATORS 16
+#define VPT_NUM_ESTIMATORS 17
 
 typedef enum {
     VPT_FB_F32 = 0,            /* framebuffer: 3 x float per pixel */
@@ -493,12 +506,12 @@ int vpt_grid_mis_probe_host(const vpt_grid_desc* desc, const float* density, int
                             double* psurf, int32_t* strategy, double* dist, double* pdf, double* pe, double* T, double* rho_t,
                             uint32_t* steps, uint64_t* states_out);
 
-/* The medium colour of estimator VPT_HETERO_CHROMATIC: per colour channel c the multipliers absorb[c] of the medium's
+/* The medium colour of estimators VPT_HETERO_CHROMATIC and VPT_HETERO_SPECTRAL: per colour channel c the multipliers absorb[c] of the medium's
  * sigma_a and scatter[c] of its sigma_s, so that per unit density sa_c = sigma_a * absorb[c], ss_c = sigma_s * scatter[c]
  * and st_c = sa_c + ss_c.  Every value finite and >= 0, else VPT_E_INVALID and the previous values stay; the default is
  * (1, 1, 1) for both.  Belongs to the context, like the track fraction: it needs no grid and survives grid and scene
- * changes.  Takes effect with the next render or trace; other estimators do not read it.  A render or trace of estimator
- * VPT_HETERO_CHROMATIC with some st_c == 0 is VPT_E_INVALID. */
+ * changes.  Takes effect with the next render or trace; other estimators do not read it.  A render or trace of either
+ * estimator with some st_c == 0 is VPT_E_INVALID. */
 int vpt_set_medium_colour(vpt_context* ctx, const double absorb[3], const double scatter[3]);
 int vpt_multi_set_medium_colour(vpt_multi* m, const double absorb[3], const double scatter[3]);
 
@@ -521,6 +534,26 @@ int vpt_grid_chroma_probe(vpt_context* ctx, double sigma_a, double sigma_s, cons
 int vpt_grid_chroma_probe_host(const vpt_grid_desc* desc, const float* density, int block, int interp, const double sa[3],
                                const double ss[3], const vpt_ray* rays, const double* tmax, const uint64_t* states, int n,
                                int32_t* hero, double* t_coll, double* tau, double* w, uint32_t* steps, uint64_t* states_out);
+
+/* Spectral-tracking probe (csrc/vpt_grid_spectral.h: vpt_grid_spectral_one; the two walkers of estimator
+ * VPT_HETERO_SPECTRAL), each from states[i].  The spectral delta track over [0, tmax[i]] of a path that carries the
+ * throughput beta[3 i .. 3 i + 2] (beta may be NULL: ones): t_coll[i] = the collision distance, -1 for "none", NaN at the
+ * step cap; w = the track's weight per channel -- at "none" the surface's weight W, at a collision W times the albedo
+ * ss_c / st_c, +0 at the cap -- channel c of ray i at w[c * n + i]; steps[i] = its tentative steps, states_out[i] = the
+ * state after it.  Chromatic ratio tracking over [0, tmax[i]]: T[c * n + i] = channel c's estimate of exp(-st_c tau) (NaN:
+ * the step cap), ratio_steps[i] = its draws, ratio_states_out[i] = the state after it.  Every output array may be NULL in
+ * the host probe and none in the GPU probe.  The GPU probe reads the context's grid, majorant block, interpolation and
+ * medium colour (VPT_E_INVALID without a grid) and takes the medium's sigma_a and sigma_s; the host probe takes the
+ * density, the block size (0: the global majorant), the mode and the six coefficients sa[3], ss[3] per unit density
+ * themselves (st_c = sa[c] + ss[c]).  A coefficient that is not finite or negative, or some st_c == 0, is VPT_E_INVALID.
+ * Host arrays, synchronous. */
+int vpt_grid_spectral_probe(vpt_context* ctx, double sigma_a, double sigma_s, const vpt_ray* rays, const double* tmax,
+                            const double* beta, const uint64_t* states, int n, double* t_coll, double* w, uint32_t* steps,
+                            uint64_t* states_out, double* T, uint32_t* ratio_steps, uint64_t* ratio_states_out);
+int vpt_grid_spectral_probe_host(const vpt_grid_desc* desc, const float* density, int block, int interp, const double sa[3],
+                                 const double ss[3], const vpt_ray* rays, const double* tmax, const double* beta,
+                                 const uint64_t* states, int n, double* t_coll, double* w, uint32_t* steps,
+                                 uint64_t* states_out, double* T, uint32_t* ratio_steps, uint64_t* ratio_states_out);
 
 /* PPM writer of main() (src/rt.cpp:812-820): clamp to [0,1] (src/rt.cpp:803), gamma 1/2.2,
  * int(v*255 + .5) (include/mathUtilities.h:43-45), "P3\n%d %d\n255\n" then "%d %d %d " per

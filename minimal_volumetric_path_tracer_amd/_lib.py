@@ -29,6 +29,7 @@ HETERO_EQUIANGULAR = 12
 HETERO_MIS = 13
 HETERO_CHROMATIC = 14
 HETERO_RESIDUAL = 15
+HETERO_SPECTRAL = 16
 FB_F32, FB_F64 = 0, 1
 GRID_NEAREST, GRID_TRILINEAR = 0, 1  # vpt_grid_interp
 
@@ -182,6 +183,11 @@ PROTOTYPES = [
     ("vpt_grid_chroma_probe_host", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p]),
+    ("vpt_grid_spectral_probe", c_int, [c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vpt_grid_spectral_probe_host", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p]),
     ("vpt_write_ppm", c_int, [c_char_p, c_void_p, c_int, c_int, c_int]),
     ("vpt_encode_ppm", c_int64, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64]),
     ("vpt_last_error", c_char_p, []),

@@ -556,7 +556,8 @@ VPT_DEV double transmitance(dv3 a, dv3 b, double sigma_t)
  * 11's ratio tracking): the draws are taken where the factor is evaluated.  A policy that declares vec == true returns
  * one factor per colour channel, a dv3, and the helpers multiply by it componentwise (estimator 14's chromatic medium,
  * vpt_hetero_chroma.h); a policy without the member is scalar, so the policies above and their instantiations stay as
- * they were. */
+ * they were.  A policy that is both (estimator 16's spectral tracking, vpt_hetero_spectral.h) takes the sampler first and
+ * returns a dv3. */
 struct TrHom {
     static constexpr bool hom = true;
     static constexpr bool draws = false;
@@ -957,6 +958,8 @@ VPT_DEV dv3 mis_v2(const DevScene* __restrict__ S, Sampler<COUNT>& smp, int obj,
         dv3 f = light_sample_sa(S, smp, light, x, obj, omat, n, wray, wiLight, cmax, alpha);
         if constexpr (TP::hom) {
             if (TR) f = scl(f, transmitance(x, sph_p(S, light), sigma_t));
+        } else if constexpr (TP::draws && tp_vec<TP>::value) {
+            if (TR) f = mul(f, tp.between(smp, x, sph_p(S, light), sigma_t));
         } else if constexpr (TP::draws) {
             if (TR) f = scl(f, tp.between(smp, x, sph_p(S, light), sigma_t));
         } else if constexpr (tp_vec<TP>::value) {
@@ -1448,6 +1451,7 @@ VPT_DEV dv3 point_shadow_value(const DevScene* __restrict__ S, Sampler<COUNT>& s
     double ph = smp.g == 0.0 ? 1 / (4 * VPT_PI) : phase_value(smp.g, din, VPT_PL_REUSE ? wl : nrm(sub(lp, xt)));
     dv3 Ls;
     if constexpr (TP::hom) Ls = scl(scl(Le, VPT_PL_REUSE ? lm_exp(sigma_t * mag * -1.0) : transmitance(xt, lp, sigma_t)), ph);
+    else if constexpr (TP::draws && tp_vec<TP>::value) Ls = scl(mul(Le, tp.between(smp, xt, lp, sigma_t)), ph);
     else if constexpr (TP::draws) Ls = scl(scl(Le, tp.between(smp, xt, lp, sigma_t)), ph);
     else if constexpr (tp_vec<TP>::value) Ls = scl(mul(Le, tp.between(xt, lp, sigma_t)), ph);
     else Ls = scl(scl(Le, tp.between(xt, lp, sigma_t)), ph);

@@ -307,7 +307,7 @@ struct HeteroSteps {
 
 struct KParams;  /* a render's launch parameters (vpt_render_simple.h) */
 
-/* estimator 14's per-channel coefficients per unit density, launch constants (vpt_hetero_chroma.h) */
+/* estimator 14's and 16's per-channel coefficients per unit density, launch constants (vpt_hetero_chroma.h) */
 struct ChromaCoef {
     double ss[3], st[3];
 };
@@ -319,13 +319,13 @@ struct vpt_hetero_args {
     bool lm;                    /* the grid behind the view has a majorant grid (the kernel's LM instantiation);
                                  * estimator 12, where nothing tracks, ignores it */
     double q;                   /* estimator 13: the context's track fraction */
-    vpt::ChromaCoef c;          /* estimator 14: the launch's coefficients */
+    vpt::ChromaCoef c;          /* estimators 14 and 16: the launch's coefficients */
     unsigned long long* stats;  /* estimator 10's per-sample call: vpt_debug_hetero_steps' two counters, else NULL */
 };
 
 /* What a code object of the density-grid estimators exports: its launches.  One table per unit -- vpt_hetero.hip's four
  * are the values of (TL, EM), nearest or trilinear lookup (the view's interp word) without or with the emission grid;
- * estimator 12's, 13's, 14's and 15's units the two values of TL -- and the caller picks the table in one place (vpt_kernels.hip
+ * estimator 12's to 16's units the two values of TL -- and the caller picks the table in one place (vpt_kernels.hip
  * hetero_unit).  A probe the unit does not hold is NULL. */
 struct vpt_hetero_unit {
     /* the persistent-wave render kernel of the unit's estimator (K.est where it holds two), enqueued on `stream` (the
@@ -364,6 +364,14 @@ struct vpt_hetero_unit {
     void (*grid_residual_probe_launch)(const vpt_grid_view* grid, double sigma_t, const vpt_ray* rays, const double* tmax,
                                        const uint64_t* states, int n, double* that, double* tauc, uint64_t* states_out,
                                        uint32_t* steps);
+    /* estimator 16's two walkers (vpt_grid_spectral.h); beta: 3 doubles per ray or NULL; res: four arrays of n doubles, one
+     * behind the other (t_coll, w[0], w[1], w[2]); T: three arrays of n doubles */
+    void (*grid_spectral_track_probe_launch)(const vpt_grid_view* grid, bool lm, const vpt::ChromaCoef& c, const vpt_ray* rays,
+                                             const double* tmax, const double* beta, const uint64_t* states, int n, double* res,
+                                             uint32_t* steps, uint64_t* states_out);
+    void (*grid_spectral_ratio_probe_launch)(const vpt_grid_view* grid, bool lm, const vpt::ChromaCoef& c, const vpt_ray* rays,
+                                             const double* tmax, const uint64_t* states, int n, double* T, uint32_t* steps,
+                                             uint64_t* states_out);
 };
 extern const vpt_hetero_unit vpt_int_hetero_unit;            /* vpt_hetero.hip: TL = false, EM = false */
 extern const vpt_hetero_unit vpt_int_hetero_unit_tl;         /* vpt_hetero_tl.hip: TL = true, the view's interp == 1 */
@@ -377,5 +385,7 @@ extern const vpt_hetero_unit vpt_int_hetero_chroma_unit;     /* vpt_hetero_chrom
 extern const vpt_hetero_unit vpt_int_hetero_chroma_unit_tl;
 extern const vpt_hetero_unit vpt_int_hetero_residual_unit;   /* vpt_hetero_residual.hip, vpt_hetero_residual_tl.hip */
 extern const vpt_hetero_unit vpt_int_hetero_residual_unit_tl;
+extern const vpt_hetero_unit vpt_int_hetero_spectral_unit;   /* vpt_hetero_spectral.hip, vpt_hetero_spectral_tl.hip */
+extern const vpt_hetero_unit vpt_int_hetero_spectral_unit_tl;
 
 #endif

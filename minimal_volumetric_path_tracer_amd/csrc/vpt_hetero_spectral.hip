@@ -1,0 +1,217 @@
+/*
+ * vpt_hetero_spectral.hip -- the kernels of estimator 16 (VPT_HETERO_SPECTRAL, vpt_hetero_spectral.h) in a translation unit
+ * of their own, as vpt_hetero_chroma.hip is for estimator 14: the code objects of the other estimators stay what they were.
+ *
+ * hetero_spectral_kernel: the persistent-wave loop of vpt_wave.h on estimator 16's steps (HeteroSpectralSteps).  A lane owns
+ * one pixel and runs that pixel's samples strictly in order, so the image is render_kernel_simple<16>'s bit for bit.  The
+ * prologue that stages a grid of at most 64 KiB in LDS, and with local majorants the majorant grid in what the density
+ * left of the budget, is stage_grid_lds (vpt_hetero_lds.h), every density-grid kernel's.
+ *
+ * The six per-channel coefficients (ChromaCoef) are a kernel argument of every kernel here (KParams keeps its layout),
+ * so render_kernel_simple<16> is an overload with that argument: vpt_render_simple.h's kernel with trace_hetero_spectral
+ * in the estimator's place.
+ *
+ * Trilinear interpolation: the unit instantiates one value of TL, VPT_HETERO_TL.  Compiled as it stands (0) it holds the
+ * nearest-lookup kernels and exports their launches as the table vpt_int_hetero_spectral_unit (vpt_hetero.h);
+ * vpt_hetero_spectral_tl.hip includes this file with VPT_HETERO_TL = 1 and exports vpt_int_hetero_spectral_unit_tl.  The
+ * launches are static; their host side is vpt_hetero_launch.h's, shared with the other density-grid units.
+ */
+#include <hip/hip_runtime.h>
+
+#include "vpt_wave.h"
+#include "vpt_hetero_spectral.h"
+#include "vpt_hetero_lds.h"
+#include "vpt_hetero_launch.h"
+
+namespace vpt {
+
+template <bool COUNT, int FB, bool LM, bool TL>
+__global__ __launch_bounds__(256, 2) void hetero_spectral_kernel(KParams P, const DevScene* __restrict__ S, ChromaCoef c)
+{
+    using TP = GridSpectralTr<LM, TL>;
+    /* the view lives in the steps object from the start (vpt_hetero_lds.h says why) */
+    HeteroSpectralSteps<LM, TL> st{TP::template load<LM>(P.grid, c)};
+    stage_grid_lds<LM>(st.tp.G);
+    wave_render<HeteroSpectralSteps<LM, TL>, COUNT, FB>(P, S, st);
+}
+
+}  // namespace vpt
+
+using namespace vpt;
+
+namespace {
+
+constexpr bool TLU = VPT_HETERO_TL != 0;  /* the unit's value of TL */
+
+/* render_kernel_simple (vpt_render_simple.h) for estimator 16: one lane per pixel, the samples in sequence; c holds the
+ * per-channel coefficients */
+template <int EST, bool COUNT, int FB, bool LM, bool TL>
+__global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const DevScene* __restrict__ S, ChromaCoef c)
+{
+    static_assert(EST == VPT_HETERO_SPECTRAL, "the overload with per-channel coefficients is estimator 16's here");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
+    const int lr = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    if (x >= P.w || lr >= P.shard_rows) return;
+    const PixelRow row = pixel_row(P, x, lr);
+    const Medium m = medium_of(P);
+    const dv3 o = mk(P.o[0], P.o[1], P.o[2]);
+    const GridSpectralTr<LM, TL> tp = GridSpectralTr<LM, TL>::template load<LM>(P.grid, c);
+    dv3 acc = mk(0, 0, 0);
+    uint64_t tests = 0, iters = 0, mism = 0;
+    for (int i = 0; i < P.spp; ++i) {
+        Sampler<COUNT> smp;
+        smp.X = vpt_stream_start(P.seed, row.idx, (uint64_t)i);
+        smp.g = P.g;
+        smp.cnt.tests = 0;
+        smp.cnt.iterations = 0;
+        smp.cnt.draw_mismatch = 0;
+        const dv3 dir = camera_dir(P, smp, x, row.y);
+        const dv3 L = trace_hetero_spectral<COUNT, LM, TL>(S, tp, smp, o, dir, m);
+        acc = add(L, acc);
+        if (COUNT) {
+            tests += smp.cnt.tests;
+            iters += smp.cnt.iterations;
+            mism += smp.cnt.draw_mismatch;
+        }
+    }
+    store_pixel<FB>(P, x, lr, acc);
+    if (COUNT) {
+        atomicAdd(&P.counters[0], (unsigned long long)tests);
+        atomicAdd(&P.counters[1], (unsigned long long)iters);
+        if (mism) atomicAdd(&P.counters[2], (unsigned long long)mism);
+    }
+}
+
+/* estimator 16's per-sample call (vpt_hetero_spectral.h) */
+template <bool LM, bool TL>
+__global__ __launch_bounds__(256) void trace_batch_hetero_spectral_kernel(const vpt_ray* __restrict__ rays,
+                                                                          const uint64_t* __restrict__ states, int n, Medium m,
+                                                                          const DevScene* __restrict__ S,
+                                                                          const vpt_grid_view* __restrict__ grid, ChromaCoef c,
+                                                                          double* out, uint64_t* out_states)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Sampler<false> smp;
+    smp.X = states[i] & 0xFFFFFFFFFFFFull;
+    smp.g = m.g;
+    dv3 L = trace_hetero_spectral<false, LM, TL>(S, GridSpectralTr<LM, TL>::template load<LM>(grid, c), smp, ld3(rays[i].o),
+                                                 ld3(rays[i].d), m);
+    out[3 * i] = L.x;
+    out[3 * i + 1] = L.y;
+    out[3 * i + 2] = L.z;
+    out_states[i] = smp.X;
+}
+
+/* the spectral delta track, one ray per lane (vpt_grid_spectral.h; vpt_grid_spectral_probe).  beta: 3 doubles per ray, or
+ * NULL for ones.  res: four arrays of n doubles, one behind the other (t_coll, w[0], w[1], w[2]) */
+template <bool LM, bool TL>
+__global__ __launch_bounds__(256) void grid_spectral_track_probe_kernel(const vpt_grid_view* __restrict__ grid, ChromaCoef c,
+                                                                        const vpt_ray* __restrict__ rays,
+                                                                        const double* __restrict__ tmax,
+                                                                        const double* __restrict__ beta,
+                                                                        const uint64_t* __restrict__ states, int n, double* res,
+                                                                        uint32_t* steps, uint64_t* states_out)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const vpt_grid_fields G = *grid;
+    const vpt_spectral_consts k = vpt_grid_spectral_consts(c.ss, c.st);
+    const double o[3] = {rays[i].o[0], rays[i].o[1], rays[i].o[2]}, d[3] = {rays[i].d[0], rays[i].d[1], rays[i].d[2]};
+    const double b[3] = {beta ? beta[3 * i] : 1.0, beta ? beta[3 * i + 1] : 1.0, beta ? beta[3 * i + 2] : 1.0};
+    uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
+    uint32_t ns = 0;
+    double W[3];
+    const double tc = vpt_grid_spectral_track(&G, TL, LM, &k, b, o, d, tmax[i], &X, &ns, W);
+    const bool cap = tc != tc, coll = tc >= 0;
+    const size_t nn = (size_t)n;
+    res[i] = tc;
+    res[nn + i] = cap ? 0.0 : (coll ? W[0] * k.alb[0] : W[0]);
+    res[2 * nn + i] = cap ? 0.0 : (coll ? W[1] * k.alb[1] : W[1]);
+    res[3 * nn + i] = cap ? 0.0 : (coll ? W[2] * k.alb[2] : W[2]);
+    steps[i] = ns;
+    states_out[i] = X;
+}
+
+/* chromatic ratio tracking over [0, tmax], one ray per lane.  T: three arrays of n doubles, one behind the other */
+template <bool LM, bool TL>
+__global__ __launch_bounds__(256) void grid_spectral_ratio_probe_kernel(const vpt_grid_view* __restrict__ grid, ChromaCoef c,
+                                                                        const vpt_ray* __restrict__ rays,
+                                                                        const double* __restrict__ tmax,
+                                                                        const uint64_t* __restrict__ states, int n, double* T,
+                                                                        uint32_t* steps, uint64_t* states_out)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const vpt_grid_fields G = *grid;
+    const vpt_spectral_consts k = vpt_grid_spectral_consts(c.ss, c.st);
+    const double o[3] = {rays[i].o[0], rays[i].o[1], rays[i].o[2]}, d[3] = {rays[i].d[0], rays[i].d[1], rays[i].d[2]};
+    uint64_t X = states[i] & 0xFFFFFFFFFFFFull;
+    uint32_t ns = 0;
+    double Tk[3];
+    vpt_grid_spectral_ratio(&G, TL, LM, &k, o, d, tmax[i], &X, &ns, Tk);
+    const size_t nn = (size_t)n;
+    T[i] = Tk[0];
+    T[nn + i] = Tk[1];
+    T[2 * nn + i] = Tk[2];
+    steps[i] = ns;
+    states_out[i] = X;
+}
+
+}  // namespace
+
+/* the unit's launches, the slots of vpt_hetero_unit (vpt_hetero.h); estimator 16 takes lm and the coefficients */
+static void trace_launch(int, const vpt_ray* rays, const uint64_t* states, int n, const Medium& m, const DevScene* S,
+                         const vpt_grid_view* grid, const vpt_hetero_args& a, double* out, uint64_t* out_states)
+{
+    const dim3 g = vpt_ray_grid(n), b(256);
+    with_flags([&](auto lmc) {
+        trace_batch_hetero_spectral_kernel<decltype(lmc)::value, TLU><<<g, b>>>(rays, states, n, m, S, grid, a.c, out, out_states);
+    }, a.lm);
+}
+
+static void grid_spectral_track_probe_launch(const vpt_grid_view* grid, bool lm, const ChromaCoef& c, const vpt_ray* rays,
+                                             const double* tmax, const double* beta, const uint64_t* states, int n, double* res,
+                                             uint32_t* steps, uint64_t* states_out)
+{
+    const dim3 g = vpt_ray_grid(n), b(256);
+    with_flags([&](auto lmc) {
+        grid_spectral_track_probe_kernel<decltype(lmc)::value, TLU><<<g, b>>>(grid, c, rays, tmax, beta, states, n, res, steps,
+                                                                               states_out);
+    }, lm);
+}
+
+static void grid_spectral_ratio_probe_launch(const vpt_grid_view* grid, bool lm, const ChromaCoef& c, const vpt_ray* rays,
+                                             const double* tmax, const uint64_t* states, int n, double* T, uint32_t* steps,
+                                             uint64_t* states_out)
+{
+    const dim3 g = vpt_ray_grid(n), b(256);
+    with_flags([&](auto lmc) {
+        grid_spectral_ratio_probe_kernel<decltype(lmc)::value, TLU><<<g, b>>>(grid, c, rays, tmax, states, n, T, steps, states_out);
+    }, lm);
+}
+
+static int simple_launch(const KParams& K, const DevScene* S, const vpt_hetero_args& a, void* stream)
+{
+    return with_flags([&](auto lmc, auto count, auto f32) {
+        return vpt_simple_launch(render_kernel_simple<VPT_HETERO_SPECTRAL, decltype(count)::value, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU>,
+                                 K, S, stream, a.c);
+    }, a.lm, K.counters != nullptr, K.fb == VPT_FB_F32);
+}
+
+static int launch(int device, const KParams& K, const DevScene* S, const vpt_hetero_args& a, void* stream)
+{
+    return with_flags([&](auto lmc, auto f32) {
+        return vpt_persistent_launch(hetero_spectral_kernel<false, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU>,
+                                     "hetero_spectral_kernel", device, K, S, stream, a.c);
+    }, a.lm, K.fb == VPT_FB_F32);
+}
+
+/* what the unit exports.  Host pass only: a const object with a constant initialiser is emitted for the device as well,
+ * and these are host functions */
+#if !defined(__HIP_DEVICE_COMPILE__)
+const vpt_hetero_unit VPT_HX(vpt_int_hetero_spectral_unit) = {launch,  simple_launch, trace_launch, nullptr, nullptr, nullptr,
+                                                              nullptr, nullptr,       nullptr,      nullptr,
+                                                              grid_spectral_track_probe_launch, grid_spectral_ratio_probe_launch};
+#endif

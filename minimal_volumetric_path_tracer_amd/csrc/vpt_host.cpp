@@ -24,6 +24,7 @@
 #include "vpt_grid_eqa.h"
 #include "vpt_grid_mis.h"
 #include "vpt_grid_chroma.h"
+#include "vpt_grid_spectral.h"
 #include "vpt_internal.h"
 #include "vpt_rng.h"
 
@@ -503,6 +504,51 @@ int vpt_grid_chroma_probe_host(const vpt_grid_desc* desc, const float* density, 
             for (int k = 0; k < 3; ++k) w[(size_t)k * nn + i] = wk[k];
         if (steps) steps[i] = ns;
         if (states_out) states_out[i] = X;
+    }
+    return VPT_OK;
+}
+
+int vpt_grid_spectral_probe_host(const vpt_grid_desc* desc, const float* density, int block, int interp, const double sa[3],
+                                 const double ss[3], const vpt_ray* rays, const double* tmax, const double* beta,
+                                 const uint64_t* states, int n, double* t_coll, double* w, uint32_t* steps,
+                                 uint64_t* states_out, double* T, uint32_t* ratio_steps, uint64_t* ratio_states_out)
+{
+    const char* who = "vpt_grid_spectral_probe_host";
+    vpt_clear_error();
+    if (!sa || !ss || !rays || !tmax || !states || n < 0) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
+    if (block < 0) return vpt_fail(VPT_E_INVALID, "%s: block %d (0 = the global majorant, else >= 1)", who, block);
+    if (interp != VPT_GRID_NEAREST && interp != VPT_GRID_TRILINEAR)
+        return vpt_fail(VPT_E_INVALID, "%s: interp %d (0 = nearest, 1 = trilinear)", who, interp);
+    double st[3];
+    for (int k = 0; k < 3; ++k) {
+        if (!(sa[k] >= 0.0 && sa[k] - sa[k] == 0.0 && ss[k] >= 0.0 && ss[k] - ss[k] == 0.0))  /* a NaN fails both */
+            return vpt_fail(VPT_E_INVALID, "%s: channel %d: sa %g, ss %g (finite, >= 0)", who, k, sa[k], ss[k]);
+        st[k] = sa[k] + ss[k];
+        if (!(st[k] > 0.0)) return vpt_fail(VPT_E_INVALID, "%s: channel %d has no extinction", who, k);
+    }
+    int rc = vpt_int_grid_check(desc, density, who);
+    if (rc) return rc;
+    vpt_grid_view G;
+    std::vector<float> maj;
+    probe_view(&G, maj, desc, density, block, interp);
+    const vpt_spectral_consts kc = vpt_grid_spectral_consts(ss, st);
+    const double ones[3] = {1.0, 1.0, 1.0};
+    const size_t nn = (size_t)n;
+    for (int i = 0; i < n; ++i) {
+        double tc, wk[3], Tk[3];
+        uint32_t ns = 0, nr = 0;
+        uint64_t Xt = 0, Xr = 0;
+        vpt_grid_spectral_one(&G, interp, block != 0, &kc, beta ? beta + 3 * (size_t)i : ones, rays[i].o, rays[i].d, tmax[i],
+                              states[i] & 0xFFFFFFFFFFFFull, &tc, wk, &ns, &Xt, Tk, &nr, &Xr);
+        if (t_coll) t_coll[i] = tc;
+        if (w)
+            for (int k = 0; k < 3; ++k) w[(size_t)k * nn + i] = wk[k];
+        if (steps) steps[i] = ns;
+        if (states_out) states_out[i] = Xt;
+        if (T)
+            for (int k = 0; k < 3; ++k) T[(size_t)k * nn + i] = Tk[k];
+        if (ratio_steps) ratio_steps[i] = nr;
+        if (ratio_states_out) ratio_states_out[i] = Xr;
     }
     return VPT_OK;
 }

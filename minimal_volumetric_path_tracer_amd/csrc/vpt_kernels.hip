@@ -377,7 +377,7 @@ static int check_medium(const vpt_medium* m)
     return VPT_OK;
 }
 
-/* the launch constants of estimator 14 from the medium and the context's colour: per unit density ss[k] = sigma_s * cs[k]
+/* the launch constants of estimators 14 and 16 from the medium and the context's colour: per unit density ss[k] = sigma_s * cs[k]
  * and st[k] = sigma_a * ca[k] + ss[k] (vpt_hetero_chroma.h) */
 static ChromaCoef chroma_coef(const vpt_context* ctx, double sigma_a, double sigma_s)
 {
@@ -396,15 +396,15 @@ static ChromaCoef chroma_coef(const vpt_context* ctx, double sigma_a, double sig
  * (include/rayMarchingMethods.h:64,153), so the scene needs at least 6 spheres */
 static int check_march(const vpt_context* ctx, const vpt_medium* m)
 {
-    if (m->estimator >= VPT_HETERO_FREE && m->estimator <= VPT_HETERO_RESIDUAL) {
+    if (m->estimator >= VPT_HETERO_FREE && m->estimator <= VPT_HETERO_SPECTRAL) {
         if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "estimator %d needs a density grid (vpt_set_density_grid)", m->estimator);
-        if (m->estimator == VPT_HETERO_CHROMATIC) {
-            if (ctx->h_grid.emit)  /* the emitting track's weight under a hero channel is not worked out */
+        if (m->estimator == VPT_HETERO_CHROMATIC || m->estimator == VPT_HETERO_SPECTRAL) {
+            if (ctx->h_grid.emit)  /* the emitting track's weight under a hero channel, or under spectral weights, is not worked out */
                 return vpt_fail(VPT_E_UNSUPPORTED, "estimator %d does not score an emission grid (estimators 10 and 11 do)",
                                 m->estimator);
             const ChromaCoef c = chroma_coef(ctx, m->sigma_a, m->sigma_s);
             for (int k = 0; k < 3; ++k)
-                if (!(c.st[k] > 0))  /* the hero's track and the weights divide by it */
+                if (!(c.st[k] > 0))  /* the hero's track, the weights and the albedo divide by it */
                     return vpt_fail(VPT_E_INVALID, "estimator %d: channel %d has no extinction (sigma_a * absorb + sigma_s * "
                                     "scatter == 0; vpt_set_medium_colour)", m->estimator, k);
             return VPT_OK;
@@ -558,7 +558,7 @@ static bool hetero_simple_kernel()
 }
 
 /* The code object that holds an estimator's kernels for a lookup (tl: trilinear) and, for estimators 10 and 11, a medium
- * without or with emission (vpt_hetero.h); estimators 12 to 15 take the lookup alone.  The one place where the settings
+ * without or with emission (vpt_hetero.h); estimators 12 to 16 take the lookup alone.  The one place where the settings
  * turn into a unit: every launch below goes through the table returned here.  A probe names its estimator's unit, and
  * the two grid probes exist in the units without emission only, so their callers pass em = false whatever the context
  * holds. */
@@ -569,6 +569,7 @@ static const vpt_hetero_unit& hetero_unit(int est, bool tl, bool em)
     case VPT_HETERO_MIS: return tl ? vpt_int_hetero_mis_unit_tl : vpt_int_hetero_mis_unit;
     case VPT_HETERO_CHROMATIC: return tl ? vpt_int_hetero_chroma_unit_tl : vpt_int_hetero_chroma_unit;
     case VPT_HETERO_RESIDUAL: return tl ? vpt_int_hetero_residual_unit_tl : vpt_int_hetero_residual_unit;
+    case VPT_HETERO_SPECTRAL: return tl ? vpt_int_hetero_spectral_unit_tl : vpt_int_hetero_spectral_unit;
     default: break;  /* 10 and 11 */
     }
     if (em) return tl ? vpt_int_hetero_unit_em_tl : vpt_int_hetero_unit_em;
@@ -587,7 +588,8 @@ static vpt_hetero_args hetero_args(const vpt_context* ctx, double sigma_a, doubl
 
 /* estimators 10, 11 (by K.est: hetero_kernel / hetero_ratio_kernel), 12 (hetero_eqa_kernel; the majorant block plays no
  * part), 13 (hetero_mis_kernel, with the context's track fraction), 14 (hetero_chroma_kernel, with the coefficients
- * of the context's medium colour) and 15 (hetero_residual_kernel) on the stream's queue word; counting mode and
+ * of the context's medium colour), 15 (hetero_residual_kernel) and 16 (hetero_spectral_kernel, with the same coefficients)
+ * on the stream's queue word; counting mode and
  * VPT_SIMPLE_KERNEL=1: render_kernel_simple<K.est> */
 static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
 {
@@ -815,6 +817,7 @@ static int launch_render(vpt_context* ctx, KParams K, hipStream_t stream)
         VPT_LAUNCH_EST(13)
         VPT_LAUNCH_EST(14)
         VPT_LAUNCH_EST(15)
+        VPT_LAUNCH_EST(16)
     }
 #undef VPT_LAUNCH_EST
     return vpt_fail(VPT_E_INVALID, "unknown estimator %d", K.est);
@@ -1348,6 +1351,50 @@ int vpt_grid_chroma_probe(vpt_context* ctx, double sigma_a, double sigma_s, cons
     return st.status("vpt_grid_chroma_probe");
 }
 
+int vpt_grid_spectral_probe(vpt_context* ctx, double sigma_a, double sigma_s, const vpt_ray* rays, const double* tmax,
+                            const double* beta, const uint64_t* states, int n, double* t_coll, double* w, uint32_t* steps,
+                            uint64_t* states_out, double* T, uint32_t* ratio_steps, uint64_t* ratio_states_out)
+{
+    vpt_clear_error();
+    if (!ctx || !rays || !tmax || !states || !t_coll || !w || !steps || !states_out || !T || !ratio_steps || !ratio_states_out ||
+        n < 0)
+        return vpt_fail(VPT_E_INVALID, "vpt_grid_spectral_probe: bad arguments");
+    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "vpt_grid_spectral_probe: no density grid set (vpt_set_density_grid)");
+    if (!is_finite(sigma_a) || !is_finite(sigma_s) || sigma_a < 0 || sigma_s < 0)
+        return vpt_fail(VPT_E_INVALID, "vpt_grid_spectral_probe: sigma_a/sigma_s must be finite and >= 0");
+    const ChromaCoef cc = chroma_coef(ctx, sigma_a, sigma_s);
+    for (int k = 0; k < 3; ++k)
+        if (!(cc.st[k] > 0)) return vpt_fail(VPT_E_INVALID, "vpt_grid_spectral_probe: channel %d has no extinction", k);
+    if (n == 0) return VPT_OK;
+    HIP_OK(hipSetDevice(ctx->device));
+    Staging st;
+    const size_t nn = (size_t)n;
+    vpt_ray* dr = st.alloc<vpt_ray>(nn);
+    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn), *dro = st.alloc<uint64_t>(nn);
+    double* dtm = st.alloc<double>(nn);
+    double* db = beta ? st.alloc<double>(3 * nn) : nullptr;
+    double* dres = st.alloc<double>(4 * nn);  /* t_coll and the three weights, one array behind the other */
+    double* dT = st.alloc<double>(3 * nn);
+    uint32_t *dst = st.alloc<uint32_t>(nn), *drs = st.alloc<uint32_t>(nn);
+    st.up(dr, rays, nn);
+    st.up(ds, states, nn);
+    st.up(dtm, tmax, nn);
+    if (beta) st.up(db, beta, 3 * nn);
+    st.launch([&] {
+        const vpt_hetero_unit& u = hetero_unit(ctx, VPT_HETERO_SPECTRAL);
+        u.grid_spectral_track_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, cc, dr, dtm, db, ds, n, dres, dst, dso);
+        u.grid_spectral_ratio_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, cc, dr, dtm, ds, n, dT, drs, dro);
+    });
+    st.down(t_coll, dres, nn);
+    st.down(w, dres + nn, 3 * nn);  /* w[c * n + i] */
+    st.down(steps, dst, nn);
+    st.down(states_out, dso, nn);
+    st.down(T, dT, 3 * nn);  /* T[c * n + i] */
+    st.down(ratio_steps, drs, nn);
+    st.down(ratio_states_out, dro, nn);
+    return st.status("vpt_grid_spectral_probe");
+}
+
 int vpt_grid_residual_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
                             int n, double* that, double* tauc, uint64_t* states_out, uint32_t* steps)
 {
@@ -1523,6 +1570,7 @@ static int trace_batch(vpt_context* ctx, const vpt_medium* m, const vpt_ray* ray
         case VPT_HETERO_MIS:
         case VPT_HETERO_CHROMATIC:
         case VPT_HETERO_RESIDUAL:
+        case VPT_HETERO_SPECTRAL:
             hetero_unit(ctx, m->estimator).trace_launch(m->estimator, dr, ds, n, mm, ctx->d_scene, ctx->d_grid,
                                                         hetero_args(ctx, m->sigma_a, m->sigma_s, stats), dout, dso);
             break;

@@ -23,7 +23,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (EXPLICIT_EQUIANGULAR, EXPLICIT_FREE, FB_F32, FB_F64, FREE_FLIGHT, HETERO_EQUIANGULAR, HETERO_CHROMATIC, HETERO_FREE, HETERO_MIS, HETERO_RATIO, HETERO_RESIDUAL, IMPLICIT_FREE, MIS_EQUIANGULAR,
+from ._lib import (EXPLICIT_EQUIANGULAR, EXPLICIT_FREE, FB_F32, FB_F64, FREE_FLIGHT, HETERO_EQUIANGULAR, HETERO_CHROMATIC, HETERO_FREE, HETERO_MIS, HETERO_RATIO, HETERO_RESIDUAL, HETERO_SPECTRAL, IMPLICIT_FREE, MIS_EQUIANGULAR,
                    RAY_DTYPE, RAY_MARCHING, RAY_MARCHING_EXPLICIT, RAY_MARCHING_GLOBAL, RAY_MARCHING_SA, SPHERE_DTYPE,
                    SURFACE_PT, check, lib)
 
@@ -35,7 +35,8 @@ ESTIMATORS = {"ff": FREE_FLIGHT, "free_flight": FREE_FLIGHT, "mis": MIS_EQUIANGU
               "hetero_ratio": HETERO_RATIO, "hetero_equiangular": HETERO_EQUIANGULAR, "hetero_eqa": HETERO_EQUIANGULAR,
               "hetero_mis": HETERO_MIS, "hetero_mis_equiangular": HETERO_MIS,
               "hetero_chromatic": HETERO_CHROMATIC, "hetero_rgb": HETERO_CHROMATIC,
-              "hetero_residual": HETERO_RESIDUAL, "hetero_residual_ratio": HETERO_RESIDUAL}
+              "hetero_residual": HETERO_RESIDUAL, "hetero_residual_ratio": HETERO_RESIDUAL,
+              "hetero_spectral": HETERO_SPECTRAL, "hetero_spectral_tracking": HETERO_SPECTRAL}
 
 
 def Sphere(r, p, c=(0, 0, 0), radiance=(0, 0, 0), material=0, eta=(0, 0, 0), kappa=(0, 0, 0), alpha=0.0) -> np.ndarray:
@@ -252,6 +253,38 @@ def grid_chroma_probe_host(rho, lo, hi, sigma_a: float, sigma_s: float, rays, tm
     return out
 
 
+def _spectral_probe_args(n, beta):
+    """(beta as (n, 3) float64 or None, the output arrays of a spectral probe in the C argument order); w and T are (3, n),
+    a channel per row"""
+    b = None
+    if beta is not None:
+        b = np.ascontiguousarray(np.broadcast_to(np.asarray(beta, dtype=np.float64), (n, 3)))
+    out = (np.zeros(n), np.zeros((3, n)), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64), np.zeros((3, n)),
+           np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64))
+    return b, out
+
+
+def grid_spectral_probe_host(rho, lo, hi, sigma_a: float, sigma_s: float, rays, tmax, states, absorption=(1.0, 1.0, 1.0),
+                             scattering=(1.0, 1.0, 1.0), majorant_block: int = 0, interpolation: str = "nearest", beta=None):
+    """csrc/vpt_grid_spectral.h on the host (vpt_grid_spectral_probe_host, no GPU): the two walkers of estimator
+    "hetero_spectral" per ray (unit direction), each from `states`, in a medium with sa_c = sigma_a * absorption[c] and
+    ss_c = sigma_s * scattering[c] per unit density.  beta: the throughput the path carries, three numbers or (n, 3)
+    (default ones).  Returns (t_coll, w, steps, states, T, ratio_steps, ratio_states): the spectral delta track over
+    [0, tmax] -- the collision distance (-1: none, NaN: step cap), the per-channel weight as a (3, n) array (W at "none",
+    W times the albedo ss_c / st_c at a collision), its tentative steps and end states -- and chromatic ratio tracking over
+    [0, tmax]: the three estimates of exp(-st_c tau) as a (3, n) array, its draws and end states."""
+    mode = _interp_mode(interpolation)
+    d, r = _grid_args(rho, lo, hi)
+    ry, t, s, _, _, _ = _probe_args(rays, tmax, states)
+    ca, cs = _colour_args(absorption, scattering)
+    sa, ss = float(sigma_a) * ca, float(sigma_s) * cs
+    b, out = _spectral_probe_args(len(ry), beta)
+    check(lib().vpt_grid_spectral_probe_host(byref(d), r.ctypes.data, int(majorant_block), mode, sa.ctypes.data, ss.ctypes.data,
+                                             ry.ctypes.data, t.ctypes.data, None if b is None else b.ctypes.data,
+                                             s.ctypes.data, len(ry), *[a.ctypes.data for a in out]))
+    return out
+
+
 def _emission_args(eps, rgb, shape) -> tuple[np.ndarray, np.ndarray]:
     """(float32 voxels, float64 colour) of an emission grid for a density grid of `shape` (None: not known here, the
     library says what is missing); another shape or a colour that is not three numbers is VPT_E_INVALID"""
@@ -413,11 +446,11 @@ class Tracer:
         check(lib().vpt_set_hetero_mis_fraction(self._ctx, float(q)))
 
     def set_medium_colour(self, absorption=(1.0, 1.0, 1.0), scattering=(1.0, 1.0, 1.0)) -> None:
-        """The medium colour of estimator "hetero_chromatic": per colour channel the multipliers (r, g, b) of the
-        medium's sigma_a and of its sigma_s, each finite and >= 0 (default 1: a grey medium, estimator "hetero" bit
-        for bit).  Belongs to the tracer: it survives grid and scene changes, and no other estimator reads it.  A
-        value that is refused leaves the setting as it was; a channel whose absorption and scattering are both zero is
-        refused by the render."""
+        """The medium colour of estimators "hetero_chromatic" and "hetero_spectral": per colour channel the multipliers
+        (r, g, b) of the medium's sigma_a and of its sigma_s, each finite and >= 0 (default 1: a grey medium, estimators
+        "hetero" and "hetero_ratio" bit for bit).  Belongs to the tracer: it survives grid and scene changes, and no
+        other estimator reads it.  A value that is refused leaves the setting as it was; a channel whose absorption and
+        scattering are both zero is refused by the render."""
         ca, cs = _colour_args(absorption, scattering)
         check(lib().vpt_set_medium_colour(self._ctx, ca.ctypes.data, cs.ctypes.data))
 
@@ -492,6 +525,16 @@ class Tracer:
         out = _chroma_probe_results(len(ry))
         check(lib().vpt_grid_chroma_probe(self._ctx, float(sigma_a), float(sigma_s), ry.ctypes.data, t.ctypes.data,
                                           s.ctypes.data, len(ry), *[a.ctypes.data for a in out]))
+        return out
+
+    def grid_spectral_probe(self, sigma_a: float, sigma_s: float, rays, tmax, states, beta=None):
+        """grid_spectral_probe_host's quantities for the tracer's grid, majorant block, interpolation and medium colour,
+        computed on the GPU (vpt_grid_spectral_probe)."""
+        ry, t, s, _, _, _ = _probe_args(rays, tmax, states)
+        b, out = _spectral_probe_args(len(ry), beta)
+        check(lib().vpt_grid_spectral_probe(self._ctx, float(sigma_a), float(sigma_s), ry.ctypes.data, t.ctypes.data,
+                                            None if b is None else b.ctypes.data, s.ctypes.data, len(ry),
+                                            *[a.ctypes.data for a in out]))
         return out
 
     # ---- main()'s pixel loop (src/rt.cpp:767-805) ----
