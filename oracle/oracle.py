@@ -97,7 +97,7 @@ class Oracle:
         L.orc_math_n.restype, L.orc_math_n.argtypes = None, [_I, _P, _P, _P, _I]
         L.orc_hg_phase_sample.restype, L.orc_hg_phase_sample.argtypes = _U, [_D, _P, _U, _P]
         L.orc_hg_phase_value.restype, L.orc_hg_phase_value.argtypes = _D, [_D, _P, _P]
-        # the heterogeneous medium (oracle/vpt_oracle_grid.h): estimators 10 - 14
+        # the heterogeneous medium (oracle/vpt_oracle_grid.h): estimators 10 - 16
         L.orc_set_density_grid.restype, L.orc_set_density_grid.argtypes = _I, [_P, _I, _I, _I, _P, _P, _I, _I]
         L.orc_clear_density_grid.restype, L.orc_clear_density_grid.argtypes = None, []
         L.orc_set_emission_grid.restype, L.orc_set_emission_grid.argtypes = _I, [_P, _P]
@@ -111,9 +111,13 @@ class Oracle:
         L.orc_set_medium_colour.restype, L.orc_set_medium_colour.argtypes = _I, [_P, _P]
         L.orc_estimator_status.restype, L.orc_estimator_status.argtypes = _I, [POINTER(Medium)]
         L.orc_ext_counters.restype, L.orc_ext_counters.argtypes = None, [_P, _I]
+        L.orc_ext_counters_15_16.restype, L.orc_ext_counters_15_16.argtypes = None, [_P, _I]
         L.orc_grid_eqa_probe.restype, L.orc_grid_eqa_probe.argtypes = _I, [_D, _P, _P, _P, _P, _I] + [_P] * 6
         L.orc_grid_mis_probe.restype, L.orc_grid_mis_probe.argtypes = _I, [_D, _D, _P, _P, _P, _P, _I] + [_P] * 9
         L.orc_grid_chroma_probe.restype, L.orc_grid_chroma_probe.argtypes = _I, [_P, _P, _P, _P, _P, _I] + [_P] * 6
+        # estimators 15 and 16: the residual walk, the two spectral walkers
+        L.orc_grid_residual_probe.restype, L.orc_grid_residual_probe.argtypes = _I, [_D, _P, _P, _P, _I] + [_P] * 4
+        L.orc_grid_spectral_probe.restype, L.orc_grid_spectral_probe.argtypes = _I, [_P, _P, _P, _P, _P, _P, _I] + [_P] * 7
         self.L = L
         self.portable = bool(L.orc_is_portable_math())
         self.prefix = "orc"
@@ -192,12 +196,19 @@ class Oracle:
             raise ValueError("oracle: a medium colour is two triples of finite numbers >= 0")
 
     def ext_counters(self, reset: bool = True) -> dict:
-        """test only: what the trace calls since the last reset did in estimators 12 - 14 -- medium vertices by the
-        strategy that sampled them, estimator 14's decisions by hero channel, its collisions whose three weights differ"""
-        c = np.zeros(6, dtype=np.uint64)
+        """test only: what the trace calls since the last reset did in estimators 12 - 16 -- medium vertices by the
+        strategy that sampled them, estimator 14's decisions by hero channel, its collisions whose three weights differ;
+        estimator 15's residual walks that ended as "none" with tauc > 0 and a product of weights other than 1, and those
+        that passed a block with a control and no residual (mn > 0, mr == 0); estimator 16's decisions whose three W differ
+        (at a collision, on a surface), its ratio walks that went on past a rho >= mu point, its track's real collisions
+        taken without a draw, and its collisions that entered with three different beta"""
+        c, c2 = np.zeros(6, dtype=np.uint64), np.zeros(7, dtype=np.uint64)  # ORC_EXT_COUNTERS, ORC_EXT_COUNTERS_15_16
         self.L.orc_ext_counters(c.ctypes.data, int(reset))
-        c = [int(v) for v in c]
-        return {"equiangular": c[0], "track": c[1], "hero": tuple(c[2:5]), "w_differ": c[5]}
+        self.L.orc_ext_counters_15_16(c2.ctypes.data, int(reset))
+        c = [int(v) for v in c] + [int(v) for v in c2]
+        return {"equiangular": c[0], "track": c[1], "hero": tuple(c[2:5]), "w_differ": c[5], "residual_both": c[6],
+                "residual_flat_block": c[7], "W_differ_collision": c[8], "W_differ_surface": c[9], "ratio_went_on": c[10],
+                "no_draw_collision": c[11], "beta_differ_collision": c[12]}
 
     def _check_estimator(self, m: Medium) -> None:
         """what the library refuses, the oracle refuses: VPT_E_INVALID (-1), VPT_E_UNSUPPORTED (-4)"""
@@ -307,11 +318,47 @@ class Oracle:
         assert rc == 0
         return hero, tc, tau, w, steps, so
 
+    def grid_residual_probe(self, rho, lo, hi, sigma_t, rays, tmax, states, majorant_block=0, interpolation="nearest"):
+        """grid_residual_probe_host's arguments and results: (That, tauc, states, steps); majorant_block >= 1"""
+        r, t, s, n = self._probe_args(rays, tmax, states)
+        that, tauc, so, steps = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32)
+        self.set_density_grid(rho, lo, hi, majorant_block, interpolation)
+        try:
+            rc = self.L.orc_grid_residual_probe(float(sigma_t), r.ctypes.data, t.ctypes.data, s.ctypes.data, n,
+                                                that.ctypes.data, tauc.ctypes.data, so.ctypes.data, steps.ctypes.data)
+        finally:
+            self.clear_density_grid()
+        if rc != 0:
+            raise ValueError("oracle: the residual walk needs a majorant block >= 1")
+        return that, tauc, so, steps
+
+    def grid_spectral_probe(self, rho, lo, hi, sigma_a, sigma_s, rays, tmax, states, absorption=(1.0, 1.0, 1.0),
+                            scattering=(1.0, 1.0, 1.0), majorant_block=0, interpolation="nearest", beta=None):
+        """grid_spectral_probe_host's arguments and results: (t_coll, w, steps, states, T, ratio_steps, ratio_states), w
+        and T of shape (3, n); beta: three numbers or (n, 3), default ones"""
+        r, t, s, n = self._probe_args(rays, tmax, states)
+        sa = float(sigma_a) * np.ascontiguousarray(absorption, dtype=np.float64)
+        ss = float(sigma_s) * np.ascontiguousarray(scattering, dtype=np.float64)
+        b = None if beta is None else np.ascontiguousarray(np.broadcast_to(np.asarray(beta, dtype=np.float64), (n, 3)))
+        out = (np.zeros(n), np.zeros((3, n)), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64), np.zeros((3, n)),
+               np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64))
+        self.set_density_grid(rho, lo, hi, majorant_block, interpolation)
+        try:
+            rc = self.L.orc_grid_spectral_probe(sa.ctypes.data, ss.ctypes.data, r.ctypes.data, t.ctypes.data,
+                                                None if b is None else b.ctypes.data, s.ctypes.data, n,
+                                                *[a.ctypes.data for a in out])
+        finally:
+            self.clear_density_grid()
+        if rc != 0:
+            raise ValueError("oracle: a channel without extinction")
+        return out
+
     def trace(self, estimator: int, rays: np.ndarray, states: np.ndarray, sigma_a=0.001, sigma_s=0.009, hg_g=0.0,
               max_depth=0, counters: bool = False, march_step=0.1, march_light=7):
-        """per-sample radiance and end state of include/vpt.h's estimator number (0-14; 10 and 11 need a density
-        grid: without one the radiance is NaN and the state is the start state; 12-14 raise ValueError where the
-        library refuses them: without a grid, with an emission grid, 14 with a channel without extinction)"""
+        """per-sample radiance and end state of include/vpt.h's estimator number (0-16; 10 and 11 need a density
+        grid: without one the radiance is NaN and the state is the start state; 12-16 raise ValueError where the
+        library refuses them: without a grid, with an emission grid, 14 and 16 with a channel without extinction, 15
+        without a majorant block)"""
         m = Medium(sigma_a, sigma_s, hg_g, max_depth, estimator, march_step, march_light)
         self._check_estimator(m)
         if getattr(rays, "dtype", None) is not None and rays.dtype.names:  # records of (o, d), as Tracer.trace takes them
@@ -333,7 +380,7 @@ class Oracle:
         """main()'s pixel loop over camera rows [y0, y1); returns (h, w, 3) float64 in file order.
         chunk: samples per partial sum in uniform chunks (spp = the reference's order); None = the
         GPU's default (vpt_params.chunk_spp == 0): for estimators 0-5 chunks of min(spp, 32), the last 64
-        samples tapered (csrc/vpt_chunks.h); for estimators 6-14, whose kernels ignore chunk_spp (include/vpt.h),
+        samples tapered (csrc/vpt_chunks.h); for estimators 6-16, whose kernels ignore chunk_spp (include/vpt.h),
         the reference's order."""
         m = Medium(sigma_a, sigma_s, hg_g, max_depth, estimator, march_step, march_light)
         self._check_estimator(m)

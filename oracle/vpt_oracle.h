@@ -28,7 +28,7 @@ typedef struct {
     double sigma_a, sigma_s;  /* src/rt.cpp:794 */
     double hg_g;              /* extension: 0 = reference isotropic phase */
     int32_t max_depth;        /* extension: 0 = unbounded (reference) */
-    int32_t estimator;        /* include/vpt.h vpt_estimator: 0 iterativeVPTracerFree, 1 MISVPTTracerRecursive, ..., 5 iterativePathTracer, 6 rayMarching3, 7 rayMarching2, 8 rayMarchingGlobal, 9 rayMarching, 10 the heterogeneous free-flight estimator (delta tracking on orc_set_density_grid's grid), 11 the same with ratio-tracking transmittance, 12 equi-angular sampling in the grid, 13 the one-sample combination of a delta track and equi-angular sampling (orc_set_hetero_mis_fraction), 14 estimator 10 in a chromatic medium (orc_set_medium_colour) */
+    int32_t estimator;        /* include/vpt.h vpt_estimator: 0 iterativeVPTracerFree, 1 MISVPTTracerRecursive, ..., 5 iterativePathTracer, 6 rayMarching3, 7 rayMarching2, 8 rayMarchingGlobal, 9 rayMarching, 10 the heterogeneous free-flight estimator (delta tracking on orc_set_density_grid's grid), 11 the same with ratio-tracking transmittance, 12 equi-angular sampling in the grid, 13 the one-sample combination of a delta track and equi-angular sampling (orc_set_hetero_mis_fraction), 14 estimator 10 in a chromatic medium (orc_set_medium_colour), 15 estimator 11 with residual ratio tracking over the block minima (needs a majorant block), 16 estimator 11 in the chromatic medium by spectral tracking */
     double march_step;        /* rayMarching3 / rayMarching2: step; rayMarchingGlobal: segments; rayMarching: steps */
     int32_t march_light;      /* rayMarching3 / rayMarching2: idsource */
     int32_t reserved_;

@@ -6,7 +6,8 @@
  * yields a ray's tentative points -- the draws, the step count, the boundary test -- for the global or the local
  * majorant, and ONE consumer applies the rule of the track, of ratio tracking or of the emitting track at each
  * point.  Everything that draws keeps the specification's operation order, FP64 without contraction.
- * The distance decisions of estimators 12, 13 and 14 follow at the end, on the same pieces.
+ * The distance decisions of estimators 12, 13 and 14 follow at the end, on the same pieces, and behind them the walkers
+ * of estimators 15 and 16: the residual ratio walk over the block minima, chromatic ratio tracking and the spectral track.
  *
  * Included by vpt_oracle.c after xi(c), M_EXP, M_LOG and v3 exist; plain C11.
  */
@@ -29,6 +30,7 @@ typedef struct {
     double rho_max;
     float* rho;            /* [nz][ny][nx] */
     float* maj;            /* [nbz][nby][nbx], B >= 1 */
+    float* ctl;            /* the control grid of estimator 15: the block minima, maj's layout and blocks */
     float* eps;            /* emission grid, rho's layout; NULL: none */
     double rgb[3];
 } og_grid;
@@ -46,6 +48,7 @@ static void og_clear(void)
 {
     og_free(&g_grid.rho);
     og_free(&g_grid.maj);
+    og_free(&g_grid.ctl);
     og_free(&g_grid.eps);
     memset(&g_grid, 0, sizeof g_grid);
 }
@@ -53,13 +56,15 @@ static void og_clear(void)
 static inline size_t og_at(int ix, int iy, int iz) { return ((size_t)iz * (size_t)g_grid.n[1] + (size_t)iy) * (size_t)g_grid.n[0] + (size_t)ix; }
 
 /* super-voxel majorants: the float32 maximum over the block's voxels; under trilinear the block is dilated by one
- * voxel on every side (held to the grid), since a point of the block reads the voxels next to it too */
+ * voxel on every side (held to the grid), since a point of the block reads the voxels next to it too.  Beside them the
+ * control grid: the float32 minimum over the same voxels (every block holds one) */
 static void og_build_majorants(void)
 {
     og_grid* G = &g_grid;
     const int B = G->B, dil = G->interp ? 1 : 0;
     for (int a = 0; a < 3; ++a) G->nb[a] = (G->n[a] + B - 1) / B;
     G->maj = (float*)malloc(sizeof(float) * (size_t)G->nb[0] * (size_t)G->nb[1] * (size_t)G->nb[2]);
+    G->ctl = (float*)malloc(sizeof(float) * (size_t)G->nb[0] * (size_t)G->nb[1] * (size_t)G->nb[2]);
     for (int bz = 0; bz < G->nb[2]; ++bz)
         for (int by = 0; by < G->nb[1]; ++by)
             for (int bx = 0; bx < G->nb[0]; ++bx) {
@@ -71,12 +76,15 @@ static void og_build_majorants(void)
                     if (first[a] < 0) first[a] = 0;
                     if (last[a] > G->n[a] - 1) last[a] = G->n[a] - 1;
                 }
-                float mx = 0.0f;
+                float mx = 0.0f, mn = INFINITY;
                 for (int z = first[2]; z <= last[2]; ++z)
                     for (int y = first[1]; y <= last[1]; ++y)
-                        for (int x = first[0]; x <= last[0]; ++x)
+                        for (int x = first[0]; x <= last[0]; ++x) {
                             if (G->rho[og_at(x, y, z)] > mx) mx = G->rho[og_at(x, y, z)];
+                            if (G->rho[og_at(x, y, z)] < mn) mn = G->rho[og_at(x, y, z)];
+                        }
                 G->maj[((size_t)bz * (size_t)G->nb[1] + (size_t)by) * (size_t)G->nb[0] + (size_t)bx] = mx;
+                G->ctl[((size_t)bz * (size_t)G->nb[1] + (size_t)by) * (size_t)G->nb[0] + (size_t)bx] = mn;
             }
 }
 
@@ -278,12 +286,24 @@ typedef struct {
     double next[3], inv[3];
     int ax;
     double te, mu;
+    /* the residual walk (estimator 15; resid != 0): the current super-voxel's minimum, the candidates' majorant is
+     * mu - mn, and the control optical depth of what the walk has passed */
+    int resid;
+    double mn, tauc, tend;
+    int flat;              /* the walk passed a block with a control and no residual (mn > 0, mr == 0) */
 } og_walk;
 
 static double og_block_mu(const og_walk* w)
 {
     if (!(w->te > w->t)) return 0.0;  /* no length: passed over */
     return (double)g_grid.maj[((size_t)w->ib[2] * (size_t)g_grid.nb[1] + (size_t)w->ib[1]) * (size_t)g_grid.nb[0] + (size_t)w->ib[0]];
+}
+
+/* the block's minimum, read where og_block_mu reads the majorant */
+static double og_block_mn(const og_walk* w)
+{
+    if (!(w->te > w->t)) return 0.0;
+    return (double)g_grid.ctl[((size_t)w->ib[2] * (size_t)g_grid.nb[1] + (size_t)w->ib[1]) * (size_t)g_grid.nb[0] + (size_t)w->ib[0]];
 }
 
 /* 0: the walk draws nothing and ends as "none" (rho_max == 0, or no slab interval) */
@@ -295,9 +315,13 @@ static int og_walk_begin(og_walk* w, const double o[3], const double d[3], doubl
     w->tmax = tmax;
     w->sigma_t = sigma_t;
     w->steps = 0;
+    w->resid = 0;
+    w->flat = 0;
+    w->tauc = 0.0;
     if (!(g_grid.rho_max > 0.0)) return 0;
     if (!og_slab(o, d, &t0, &w->t1)) return 0;
     w->t = t0;
+    w->tend = w->t1 < tmax ? w->t1 : tmax;
     if (g_grid.B >= 1) {
         for (int a = 0; a < 3; ++a) {
             w->ib[a] = og_voxel(a, o[a] + d[a] * t0) / g_grid.B;
@@ -308,11 +332,17 @@ static int og_walk_begin(og_walk* w, const double o[3], const double d[3], doubl
         w->ax = og_argmin3(w->next);
         w->te = w->next[w->ax];
         w->mu = og_block_mu(w);
+        w->mn = og_block_mn(w);
     }
     return 1;
 }
 
-/* the next tentative point: one draw, one step counted.  1 with the point's distance and majorant, 0 for "none" */
+/* the next tentative point: one draw, one step counted.  1 with the point's distance and majorant, 0 for "none".
+ * The residual walk (w->resid, local majorants only) takes its candidates against mr = mu - mn -- a block where
+ * !(mr > 0) has none and leaves rem untouched -- and adds to w->tauc the three pieces of the control optical depth in
+ * traversal order: mn times the stretch up to a block's exit plane held to tend (where it has length); up to a tentative
+ * point that passed the boundary test; and up to tend where the boundary test rejects the point (where tend > t).
+ * Fault 11 (orc_hetero_set_fault): the last piece is left out. */
 static int og_walk_next(og_walk* w, orc_ctx* c, double* tc_out, double* mu_out)
 {
     const og_grid* G = &g_grid;
@@ -329,16 +359,27 @@ static int og_walk_next(og_walk* w, orc_ctx* c, double* tc_out, double* mu_out)
     const int max_cross = G->nb[0] + G->nb[1] + G->nb[2] + 4;
     for (int k = 0; k < max_cross; ++k) {
         if (w->te > w->t) {
-            if (w->mu > 0.0) {  /* an empty super-voxel is skipped: rem untouched */
-                const double s = w->mu * w->sigma_t;
+            const double m = w->resid ? w->mu - w->mn : w->mu;
+            if (m > 0.0) {  /* an empty super-voxel is skipped: rem untouched */
+                const double s = m * w->sigma_t;
                 const double tc = w->t + (rem / s);
                 if (tc < w->te) {
-                    if (tc > w->tmax || tc >= w->t1) return 0;
+                    if (tc > w->tmax || tc >= w->t1) {
+                        if (w->resid && g_hetero_fault != 11 && w->tend > w->t) w->tauc = w->tauc + w->mn * (w->tend - w->t);
+                        return 0;
+                    }
+                    if (w->resid) w->tauc = w->tauc + w->mn * (tc - w->t);
                     *tc_out = tc;
                     *mu_out = w->mu;
                     return 1;
                 }
                 rem = rem - s * (w->te - w->t);
+            } else if (w->resid && w->mn > 0.0) {
+                w->flat = 1;
+            }
+            if (w->resid) {
+                const double e = w->te < w->tend ? w->te : w->tend;
+                if (e > w->t) w->tauc = w->tauc + w->mn * (e - w->t);
             }
             w->t = w->te;
         }
@@ -349,6 +390,7 @@ static int og_walk_next(og_walk* w, orc_ctx* c, double* tc_out, double* mu_out)
         w->ax = og_argmin3(w->next);
         w->te = w->next[w->ax];
         w->mu = og_block_mu(w);
+        w->mn = og_block_mn(w);
     }
     return 0;  /* the crossing cap */
 }
@@ -585,6 +627,159 @@ static v3 og_chroma_weight(const og_chroma* k, double tau, int collision)
 static v3 og_chroma_T(const og_chroma* k, double tau)
 {
     return V3(M_EXP(k->st[0] * tau * -1.0), M_EXP(k->st[1] * tau * -1.0), M_EXP(k->st[2] * tau * -1.0));
+}
+
+/* ================================================================== estimators 15 and 16
+ * Their walkers, written from the specification (the header comments of csrc/vpt_grid.h, "Residual ratio tracking", and of
+ * csrc/vpt_grid_spectral.h) on the pieces above.  The product restates the local-majorant DDA in
+ * every walker; here all three consume the tentative points of og_walk_begin / og_walk_next, the residual walk through
+ * that generator's resid mode, the two spectral walkers under the bounding extinction in sigma_t's place. */
+
+/* residual ratio tracking over [0, tmax] (local majorants: g_grid.B >= 1): the estimate of the transmittance, the control
+ * optical depth in *tauc and the draws in *steps (optional).  Without a slab interval, or on an empty grid, 1.0 with no
+ * draw and tauc = +0.  At a tentative point: rho >= mu returns +0.0; else the weight 1 - (rho - mn) / mr is multiplied in
+ * only where rho > mn.  "None" returns That * exp(-sigma_t tauc), a capped walk NaN.
+ * Fault 12 (orc_hetero_set_fault): the weight is taken against mu, 1 - (rho - mn) / mu. */
+static double og_residual(const double o[3], const double d[3], double tmax, double sigma_t, orc_ctx* c, uint32_t* steps,
+                          double* tauc)
+{
+    og_walk w;
+    double That = 1.0;
+    if (steps) *steps = 0;
+    *tauc = 0.0;
+    if (!og_walk_begin(&w, o, d, tmax, sigma_t)) return 1.0;
+    w.resid = 1;
+    double result = (double)NAN;
+    for (int k = 0; k < OG_MAX_STEPS; ++k) {
+        double tc, mu;
+        if (!og_walk_next(&w, c, &tc, &mu)) {
+            result = That * M_EXP(sigma_t * w.tauc * -1.0);
+            if (w.tauc > 0.0 && That != 1.0) c->ext[ORC_EXT_RESID_BOTH]++;
+            break;
+        }
+        const double rho = og_field_on_ray(g_grid.rho, o, d, tc);
+        if (rho >= mu) {
+            result = 0.0;
+            break;
+        }
+        if (rho > w.mn) That = That * (1.0 - (rho - w.mn) / (g_hetero_fault == 12 ? mu : mu - w.mn));
+        w.t = tc;
+    }
+    if (w.flat) c->ext[ORC_EXT_RESID_FLAT]++;
+    if (steps) *steps = w.steps;
+    *tauc = w.tauc;
+    return result;
+}
+
+/* estimator 16's launch constants beside the medium's coefficients: the bounding extinction sb (the largest channel's),
+ * f_k = st_k / sb (the largest channel's is x / x == 1.0), the collision's albedo alb_k = ss_k / st_k */
+typedef struct og_spectral_s {
+    og_chroma m;
+    double sb, f[3], alb[3];
+} og_spectral;
+
+static og_spectral og_spectral_of(const og_chroma* m)
+{
+    og_spectral k;
+    k.m = *m;
+    k.sb = m->st[0] > m->st[1] ? m->st[0] : m->st[1];
+    k.sb = k.sb > m->st[2] ? k.sb : m->st[2];
+    for (int i = 0; i < 3; ++i) {
+        k.f[i] = m->st[i] / k.sb;
+        k.alb[i] = m->ss[i] / m->st[i];
+    }
+    return k;
+}
+
+/* chromatic ratio tracking over [0, tmax]: ratio tracking's walk under sb with a T per channel, from (1, 1, 1).  At a
+ * tentative point with rho >= mu every T_k takes 1 - f_k and the walk ends only if all three are 0.0 (the largest channel is
+ * from there on; under grey extinction all are, at once); else T_k takes 1 - f_k (rho / mu).  "None" returns T as it stands,
+ * the cap NaN in every channel.
+ * Fault 18 (orc_hetero_set_fault): (0, 0, 0) at the first rho >= mu, as the scalar walker returns. */
+static v3 og_spectral_ratio(const og_spectral* k, const double o[3], const double d[3], double tmax, orc_ctx* c, uint32_t* steps)
+{
+    og_walk w;
+    double T[3] = {1.0, 1.0, 1.0};
+    int went_on = 0;
+    if (steps) *steps = 0;
+    if (!og_walk_begin(&w, o, d, tmax, k->sb)) return V3(1.0, 1.0, 1.0);
+    int capped = 1;
+    for (int n = 0; n < OG_MAX_STEPS; ++n) {
+        double tc, mu;
+        if (!og_walk_next(&w, c, &tc, &mu)) {
+            capped = 0;
+            break;
+        }
+        const double rho = og_field_on_ray(g_grid.rho, o, d, tc);
+        if (rho >= mu) {
+            if (g_hetero_fault == 18) T[0] = T[1] = T[2] = 0.0;
+            for (int i = 0; i < 3; ++i) T[i] = T[i] * (1.0 - k->f[i]);
+            if (T[0] == 0.0 && T[1] == 0.0 && T[2] == 0.0) {
+                capped = 0;
+                break;
+            }
+            went_on = 1;
+        } else {
+            const double q = rho / mu;
+            for (int i = 0; i < 3; ++i) T[i] = T[i] * (1.0 - k->f[i] * q);
+        }
+        w.t = tc;
+    }
+    if (went_on) c->ext[ORC_EXT_RATIO_WENT_ON]++;
+    if (steps) *steps = w.steps;
+    if (capped) return V3((double)NAN, (double)NAN, (double)NAN);
+    return V3(T[0], T[1], T[2]);
+}
+
+/* the spectral track over [0, tmax] for a path that carries beta: the delta track's walk under sb with a weight W per
+ * channel, from (1, 1, 1).  At a tentative point the channels' real and null fractions r_k = f_k q and n_k = 1 - r_k
+ * (q = rho / mu, 1.0 at rho >= mu) are averaged with the weights h_k = |beta_k| W_k -- (1, 1, 1) where their sum is not
+ * finite or not positive -- into a_r and a_n; a_n == 0.0 is a real collision without a draw, else one draw decides, real
+ * iff xi (a_r + a_n) < a_r; W_k takes r_k (c / a_r) or n_k (c / a_n).  The distance, -1 for "none" (W is then the
+ * surface's weight), NaN for a capped track.  Under grey extinction the scalar track under st[0], W = (1, 1, 1).
+ * Fault 17 (orc_hetero_set_fault): h_k = W_k, without |beta_k|. */
+static double og_spectral_track(const og_spectral* k, const double beta[3], const double o[3], const double d[3], double tmax,
+                                orc_ctx* c, uint32_t* steps, double W[3])
+{
+    og_walk w;
+    W[0] = W[1] = W[2] = 1.0;
+    if (k->m.grey) return og_run(OG_TRACK, o, d, tmax, k->m.st[0], c, steps, NULL);
+    if (steps) *steps = 0;
+    if (!og_walk_begin(&w, o, d, tmax, k->sb)) return -1.0;
+    double result = (double)NAN;
+    for (int n = 0; n < OG_MAX_STEPS; ++n) {
+        double tc, mu, r[3], nn[3], h[3];
+        if (!og_walk_next(&w, c, &tc, &mu)) {
+            result = -1.0;
+            break;
+        }
+        const double rho = og_field_on_ray(g_grid.rho, o, d, tc);
+        const double q = rho >= mu ? 1.0 : rho / mu;
+        for (int i = 0; i < 3; ++i) {
+            r[i] = k->f[i] * q;
+            nn[i] = 1.0 - r[i];
+            h[i] = g_hetero_fault == 17 ? W[i] : fabs(beta[i]) * W[i];
+        }
+        const double hs = (h[0] + h[1]) + h[2];
+        if (!(hs > 0.0) || !isfinite(hs)) h[0] = h[1] = h[2] = 1.0;
+        const double a_r = (h[0] * r[0] + h[1] * r[1]) + h[2] * r[2];
+        const double a_n = (h[0] * nn[0] + h[1] * nn[1]) + h[2] * nn[2];
+        const double cc = a_r + a_n;
+        int real = 1;
+        if (a_n == 0.0) c->ext[ORC_EXT_NO_DRAW]++;
+        else real = xi(c) * cc < a_r;
+        if (real) {
+            const double g = cc / a_r;
+            for (int i = 0; i < 3; ++i) W[i] = W[i] * (r[i] * g);
+            result = tc;
+            break;
+        }
+        const double g = cc / a_n;
+        for (int i = 0; i < 3; ++i) W[i] = W[i] * (nn[i] * g);
+        w.t = tc;
+    }
+    if (steps) *steps = w.steps;
+    return result;
 }
 
 #endif

@@ -76,3 +76,56 @@ def reset_ext(owner):
     owner.clear_density_grid()
     owner.set_hetero_mis_fraction(0.5)
     owner.set_medium_colour(*GREY)
+
+
+# ---- estimators 15 and 16 (tests/test_oracle_hetero_resid_spectral.py, tests/test_gpu_hetero_resid_spectral_oracle.py):
+# the box EXT_LO .. EXT_HI, no emission grid.
+#
+# Estimator 16 takes the cloud and the medium of estimators 12-14 as they are, under three colours.  COLOUR has three
+# different extinctions, channel 2 the largest.  COLOUR_FIRST is COLOUR's absorption reversed under a scattering that
+# falls with the channel: channel 0 is the largest, so a statement that reads "the last channel" for "the largest" shows.
+# COLOUR_TOP_PAIR gives channels 0 and 1 the same multipliers and the largest extinction: both have f == x / x == 1.0 and
+# both are 0.0 after a rho >= mu point, the third still estimates.
+COLOUR_FIRST = ((0.3, 0.6, 1.0), (1.4, 1.0, 0.7))
+COLOUR_TOP_PAIR = ((1.0, 1.0, 0.3), (1.4, 1.4, 0.7))
+SPECTRAL_COLOURS = {"colour": COLOUR, "first": COLOUR_FIRST, "top_pair": COLOUR_TOP_PAIR}
+#
+# Estimator 15 needs a field of its own.  On cloud() every block minimum is 0 at the main configuration (block 2,
+# trilinear) and under the nearest lookup 4 of 18 are positive with a mean mn / mu of 0.05: the control grid is inert and
+# the estimator is estimator 11, so a test on it would pass whatever the residual code did.  floor_cloud() lays the
+# density FLOOR under the x slabs FLOOR_SLABS of the same cloud.  At blocks 1 and 2 under both lookups it has blocks with
+# mn == 0 and -- but at block 1 under the nearest lookup, where every block is uniform (mn == mu: the one-draw branch) --
+# blocks with 0 < mn < mu (tests/test_oracle_hetero_resid_spectral.py asserts it from residual_model.control).
+# Why this floor and these coefficients.  The roulette ends 40 % of the iterations, so surface and medium events share
+# less than 60 % and each is to have 25 %; and at block 2 under the nearest lookup a candidate in a block's densest voxel
+# makes the estimate 0.0, which costs lit samples in proportion to the candidates' rate mr sigma_t.  A floor of 0.5 under
+# three slabs lights 48 % of the samples at the sigma_t that gives 25 % medium events.  A high floor under four of the
+# six slabs at a quarter of (EXT_SA, EXT_SS) keeps the collisions (their rate has the floor in it) and thins the
+# candidates (theirs has not): at least 32 % surface events, 26 % medium events and 51 % lit samples on every
+# configuration.  A block >= max(n) is one super-voxel, the global control; its minimum is 0 here.
+FLOOR = np.float32(3.0)
+FLOOR_SLABS = slice(0, 4)
+RES_SA, RES_SS = 0.00065, 0.00585  # a quarter of (EXT_SA, EXT_SS)
+RES_CONFIGS = [(block, interp) for block in (1, 2) for interp in ("nearest", "trilinear")] + [(6, "trilinear")]
+# The configuration of the sensitivity tests, the other scenes, the extensions and the 72 spp render is block 2 under the
+# NEAREST lookup for both estimators, not EXT_MAIN.  Under the trilinear lookup a block's majorant is taken over the block
+# dilated by a voxel, so a looked-up rho >= mu is rare (1 of 4096 samples meets one): the branch that tells chromatic ratio
+# tracking from the scalar walker is not taken, and a walker that returned (0, 0, 0) there moves no sample.  Under the
+# nearest lookup 4800 ratio walks of 4096 samples go on past such a point.  For estimator 15, 13 of 18 block minima are
+# positive under the nearest lookup against 7 under the dilation, and a missing piece of tauc moves 411 samples, not 112.
+RES_MAIN = (2, "nearest")
+SPECTRAL_MAIN = (2, "nearest")
+ESTIMATORS.update({"hetero_residual": 15, "hetero_spectral": 16})
+
+
+def floor_cloud():
+    """cloud()'s density with FLOOR added to the voxels of the x slabs FLOOR_SLABS"""
+    rho = cloud()[0].copy()
+    rho[:, :, FLOOR_SLABS] += FLOOR
+    return rho
+
+
+def set_floor_cloud(owner, block, interp):
+    """estimator 15's field in EXT_LO .. EXT_HI on a Tracer or an Oracle"""
+    owner.set_density_grid(floor_cloud(), EXT_LO, EXT_HI, majorant_block=block, interpolation=interp)
+    owner.set_medium_colour(*GREY)
