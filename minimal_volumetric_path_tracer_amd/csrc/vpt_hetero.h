@@ -236,7 +236,7 @@ VPT_DEV void hetero_medium(const DevScene* __restrict__ S, const TP& tp, Sampler
     medium_tail<0, COUNT>(smp, p, Ld, 1.0, e.pdf, xt, m, true);
 }
 
-/* one camera sample, sequentially (vpt_trace_batch, render_kernel_simple<10>) */
+/* one camera sample, sequentially (vpt_trace_batch, render_kernel_simple_hetero) */
 template <bool COUNT, bool LM = false, bool TL = false, bool EM = false>
 __device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridTrT<TL, EM>& tp, Sampler<COUNT>& smp, dv3 o, dv3 d,
                                    const Medium& m, HeteroStats* hs = nullptr)
@@ -258,7 +258,7 @@ __device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridTrT
     return p.L;
 }
 
-/* the same for estimator 11 (render_kernel_simple<11>).  Restated, not a shared template: estimator 10's function
+/* the same for estimator 11 (render_kernel_simple_ratio).  Restated, not a shared template: estimator 10's function
  * above is an out-of-line function of its kernels, and its name and code are to stay what they were */
 template <bool COUNT, bool LM = false, bool TL = false, bool EM = false>
 __device__ static dv3 trace_hetero(const DevScene* __restrict__ S, const GridRatioTr<LM, TL, EM>& tp, Sampler<COUNT>& smp, dv3 o,
@@ -331,7 +331,8 @@ struct vpt_hetero_unit {
     /* the persistent-wave render kernel of the unit's estimator (K.est where it holds two), enqueued on `stream` (the
      * caller owns the queue word K.queue and has zeroed it in stream order) */
     int (*launch)(int device, const vpt::KParams& K, const DevScene* S, const vpt_hetero_args& a, void* stream);
-    /* render_kernel_simple<K.est> for the same render; counting iff K.counters (vpt_count_work's device counters) is set */
+    /* the unit's one-lane-per-pixel kernel of K.est (render_kernel_simple_<unit>) for the same render; counting iff K.counters
+     * (vpt_count_work's device counters) is set */
     int (*simple_launch)(const vpt::KParams& K, const DevScene* S, const vpt_hetero_args& a, void* stream);
     /* the per-sample call of estimator est and, below, the probes on device arrays, default stream (the caller reads
      * hipGetLastError); steps: a probe's per-ray tentative steps, else NULL; light: 3 doubles per ray */

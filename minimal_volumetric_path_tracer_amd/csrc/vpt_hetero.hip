@@ -7,8 +7,11 @@
  *
  * hetero_kernel: the persistent-wave loop of vpt_wave.h on estimator 10's steps (HeteroSteps, vpt_hetero.h).  A
  * lane owns one pixel and runs that pixel's samples strictly in order (acc = L + acc, then * (1 / (double)spp)),
- * so the image is render_kernel_simple<10>'s bit for bit.  What the kernel adds to the loop is the prologue
+ * so the image is render_kernel_simple_hetero's bit for bit.  What the kernel adds to the loop is the prologue
  * that stages the grid in LDS (stage_grid_lds, vpt_hetero_lds.h: one function for every density-grid kernel).
+ *
+ * render_kernel_simple_hetero / _ratio (one lane per pixel) and the two per-sample kernels are thin: each loads its policy
+ * and hands a lambda on trace_hetero to the one body every density-grid unit shares (vpt_hetero_simple.h).
  *
  * Density reads: a grid of at most 64 KiB (16 384 voxels) is staged in LDS once per workgroup
  * (VPT_HETERO_LDS, on by default); a larger one is read from global memory, where the L2 holds the grids of
@@ -29,11 +32,13 @@
  * density and the majorants as before.
  *
  * The launches at the end of the file are static and reach the caller through that table alone; what a launch does on
- * the host (flags to template arguments, the persistent-wave grid, render_kernel_simple's) is vpt_hetero_launch.h's.
+ * the host (flags to template arguments, the persistent-wave grid, the one-lane-per-pixel grid) is vpt_hetero_launch.h's.
  */
 #include <hip/hip_runtime.h>
 
 #include "vpt_wave.h"
+#include "vpt_hetero.h"
+#include "vpt_hetero_simple.h"
 #include "vpt_hetero_lds.h"
 #include "vpt_hetero_launch.h"
 
@@ -82,7 +87,27 @@ namespace {
 constexpr bool TLU = VPT_HETERO_TL != 0;  /* the unit's value of TL */
 constexpr bool EMU = VPT_HETERO_EM != 0;  /* and of EM */
 
-/* estimator 10's per-sample call (vpt_hetero.h) */
+/* render_kernel_simple (vpt_render_simple.h) for estimator 10: hetero_simple_render on trace_hetero */
+template <bool COUNT, int FB, bool LM, bool TL, bool EM>
+__global__ __launch_bounds__(256) void render_kernel_simple_hetero(KParams P, const DevScene* __restrict__ S)
+{
+    const GridTrT<TL, EM> tp = GridTrT<TL, EM>::template load<LM>(P.grid);
+    hetero_simple_render<COUNT, FB>(P, [&](Sampler<COUNT>& smp, dv3 o, dv3 dir, const Medium& m) {
+        return trace_hetero<COUNT, LM, TL>(S, tp, smp, o, dir, m);
+    });
+}
+
+/* and for estimator 11: the same on the ratio-tracking policy */
+template <bool COUNT, int FB, bool LM, bool TL, bool EM>
+__global__ __launch_bounds__(256) void render_kernel_simple_ratio(KParams P, const DevScene* __restrict__ S)
+{
+    const GridRatioTr<LM, TL, EM> tp = GridRatioTr<LM, TL, EM>::template load<LM>(P.grid);
+    hetero_simple_render<COUNT, FB>(P, [&](Sampler<COUNT>& smp, dv3 o, dv3 dir, const Medium& m) {
+        return trace_hetero<COUNT, LM, TL>(S, tp, smp, o, dir, m);
+    });
+}
+
+/* estimator 10's per-sample call (vpt_hetero.h); stats: vpt_debug_hetero_steps' two counters, else NULL */
 template <bool LM, bool TL, bool EM = false>
 __global__ __launch_bounds__(256) void trace_batch_hetero_kernel(const vpt_ray* __restrict__ rays,
                                                                  const uint64_t* __restrict__ states, int n, Medium m,
@@ -90,21 +115,17 @@ __global__ __launch_bounds__(256) void trace_batch_hetero_kernel(const vpt_ray* 
                                                                  const vpt_grid_view* __restrict__ grid, double* out,
                                                                  uint64_t* out_states, unsigned long long* stats)
 {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Sampler<false> smp;
-    smp.X = states[i] & 0xFFFFFFFFFFFFull;
-    smp.g = m.g;
-    HeteroStats hs{0, 0};
-    dv3 L = trace_hetero<false, LM, TL>(S, GridTrT<TL, EM>::template load<LM>(grid), smp, ld3(rays[i].o), ld3(rays[i].d), m, stats ? &hs : nullptr);
-    if (stats) {  /* vpt_debug_hetero_steps */
-        atomicAdd(&stats[0], hs.tracks);
-        atomicAdd(&stats[1], hs.steps);
-    }
-    out[3 * i] = L.x;
-    out[3 * i + 1] = L.y;
-    out[3 * i + 2] = L.z;
-    out_states[i] = smp.X;
+    hetero_trace_one(blockIdx.x * blockDim.x + threadIdx.x, rays, states, n, m, out, out_states,
+                     [&](Sampler<false>& smp, dv3 o, dv3 d, const Medium& m) {
+                         HeteroStats hs{0, 0};
+                         const dv3 L = trace_hetero<false, LM, TL>(S, GridTrT<TL, EM>::template load<LM>(grid), smp, o, d, m,
+                                                                   stats ? &hs : nullptr);
+                         if (stats) {
+                             atomicAdd(&stats[0], hs.tracks);
+                             atomicAdd(&stats[1], hs.steps);
+                         }
+                         return L;
+                     });
 }
 
 /* estimator 11's per-sample call: the same on the ratio-tracking policy (no step statistics) */
@@ -115,16 +136,10 @@ __global__ __launch_bounds__(256) void trace_batch_hetero_ratio_kernel(const vpt
                                                                        const vpt_grid_view* __restrict__ grid, double* out,
                                                                        uint64_t* out_states)
 {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Sampler<false> smp;
-    smp.X = states[i] & 0xFFFFFFFFFFFFull;
-    smp.g = m.g;
-    dv3 L = trace_hetero<false, LM, TL>(S, GridRatioTr<LM, TL, EM>::template load<LM>(grid), smp, ld3(rays[i].o), ld3(rays[i].d), m);
-    out[3 * i] = L.x;
-    out[3 * i + 1] = L.y;
-    out[3 * i + 2] = L.z;
-    out_states[i] = smp.X;
+    hetero_trace_one(blockIdx.x * blockDim.x + threadIdx.x, rays, states, n, m, out, out_states,
+                     [&](Sampler<false>& smp, dv3 o, dv3 d, const Medium& m) {
+                         return trace_hetero<false, LM, TL>(S, GridRatioTr<LM, TL, EM>::template load<LM>(grid), smp, o, d, m);
+                     });
 }
 
 /* the density grid's walkers (vpt_grid.h), one ray per lane (vpt_grid_probe, vpt_grid_probe_lm) */
@@ -231,19 +246,13 @@ static void grid_probe_launch(const vpt_grid_view* grid, bool lm, double sigma_t
 }
 #endif
 
-template <int EST>
-static int simple_launch_of(const KParams& K, const DevScene* S, bool lm, void* stream)
-{
-    return with_flags([&](auto lmc, auto count, auto f32) {
-        return vpt_simple_launch(render_kernel_simple<EST, decltype(count)::value, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU, EMU>,
-                                 K, S, stream);
-    }, lm, K.counters != nullptr, K.fb == VPT_FB_F32);
-}
-
 static int simple_launch(const KParams& K, const DevScene* S, const vpt_hetero_args& a, void* stream)
 {
     if (K.est == VPT_HETERO_RATIO) return ratio_simple_launch(K, S, a.lm, stream);
-    return simple_launch_of<VPT_HETERO_FREE>(K, S, a.lm, stream);
+    return with_flags([&](auto lmc, auto count, auto f32) {
+        return vpt_simple_launch(render_kernel_simple_hetero<decltype(count)::value, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU, EMU>,
+                                 K, S, stream);
+    }, a.lm, K.counters != nullptr, K.fb == VPT_FB_F32);
 }
 
 static int launch(int device, const KParams& K, const DevScene* S, const vpt_hetero_args& a, void* stream)
@@ -279,7 +288,10 @@ static void grid_ratio_probe_launch(const vpt_grid_view* grid, bool lm, double s
 
 static int ratio_simple_launch(const KParams& K, const DevScene* S, bool lm, void* stream)
 {
-    return simple_launch_of<VPT_HETERO_RATIO>(K, S, lm, stream);
+    return with_flags([&](auto lmc, auto count, auto f32) {
+        return vpt_simple_launch(render_kernel_simple_ratio<decltype(count)::value, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU, EMU>,
+                                 K, S, stream);
+    }, lm, K.counters != nullptr, K.fb == VPT_FB_F32);
 }
 
 static int ratio_launch(int device, const KParams& K, const DevScene* S, bool lm, void* stream)

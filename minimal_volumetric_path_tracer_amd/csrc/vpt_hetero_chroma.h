@@ -165,7 +165,7 @@ VPT_DEV void hetero_chroma_medium(const DevScene* __restrict__ S, const GridChro
     p.depth++;
 }
 
-/* one camera sample, sequentially (vpt_trace_batch, render_kernel_simple<14>) */
+/* one camera sample, sequentially (vpt_trace_batch, render_kernel_simple_chroma) */
 template <bool COUNT, bool LM, bool TL>
 __device__ static dv3 trace_hetero_chroma(const DevScene* __restrict__ S, const GridChromaTr<TL>& tp, Sampler<COUNT>& smp, dv3 o,
                                           dv3 d, const Medium& m)

@@ -118,7 +118,7 @@ VPT_DEV void hetero_eqa_medium(const DevScene* __restrict__ S, const TP& tp, Sam
     medium_tail<1, COUNT>(smp, p, Ld, T, e.pdf, xt, ml, true);
 }
 
-/* one camera sample, sequentially (vpt_trace_batch, render_kernel_simple<12>) */
+/* one camera sample, sequentially (vpt_trace_batch, render_kernel_simple_eqa) */
 template <bool COUNT, bool TL>
 __device__ static dv3 trace_hetero_eqa(const DevScene* __restrict__ S, const GridTrT<TL>& tp, Sampler<COUNT>& smp, dv3 o, dv3 d,
                                        const Medium& m)

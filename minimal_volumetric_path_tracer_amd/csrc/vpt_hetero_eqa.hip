@@ -3,18 +3,23 @@
  * their own, as vpt_hetero.hip is for estimators 10 and 11: the code objects of those stay what they were.
  *
  * hetero_eqa_kernel: the persistent-wave loop of vpt_wave.h on estimator 12's steps (HeteroEqaSteps).  A lane owns one
- * pixel and runs that pixel's samples strictly in order, so the image is render_kernel_simple<12>'s bit for bit.  The
+ * pixel and runs that pixel's samples strictly in order, so the image is render_kernel_simple_eqa's bit for bit.  The
  * prologue that stages a grid of at most 64 KiB in LDS is stage_grid_lds (vpt_hetero_lds.h) with LM = false: there is
  * no majorant grid to stage, because nothing tracks.
+ *
+ * render_kernel_simple_eqa (one lane per pixel) and the per-sample kernel are thin: each hands a lambda on trace_hetero_eqa
+ * to the one body every density-grid unit shares (vpt_hetero_simple.h).
  *
  * Trilinear interpolation: the unit instantiates one value of TL, VPT_HETERO_TL.  Compiled as it stands (0) it holds the
  * nearest-lookup kernels and exports their launches as the table vpt_int_hetero_eqa_unit (vpt_hetero.h);
  * vpt_hetero_eqa_tl.hip includes this file with VPT_HETERO_TL = 1 and exports vpt_int_hetero_eqa_unit_tl.  The launches
- * are static; their host side is vpt_hetero_launch.h's, shared with vpt_hetero.hip.
+ * are static; their host side is vpt_hetero_launch.h's, shared with the other density-grid units.
  */
 #include <hip/hip_runtime.h>
 
 #include "vpt_wave.h"
+#include "vpt_hetero_eqa.h"
+#include "vpt_hetero_simple.h"
 #include "vpt_hetero_lds.h"
 #include "vpt_hetero_launch.h"
 
@@ -38,6 +43,16 @@ namespace {
 
 constexpr bool TLU = VPT_HETERO_TL != 0;  /* the unit's value of TL */
 
+/* render_kernel_simple (vpt_render_simple.h) for estimator 12: hetero_simple_render on trace_hetero_eqa */
+template <bool COUNT, int FB, bool TL>
+__global__ __launch_bounds__(256) void render_kernel_simple_eqa(KParams P, const DevScene* __restrict__ S)
+{
+    const GridTrT<TL> tp = GridTrT<TL>::template load<false>(P.grid);
+    hetero_simple_render<COUNT, FB>(P, [&](Sampler<COUNT>& smp, dv3 o, dv3 dir, const Medium& m) {
+        return trace_hetero_eqa<COUNT, TL>(S, tp, smp, o, dir, m);
+    });
+}
+
 /* estimator 12's per-sample call (vpt_hetero_eqa.h) */
 template <bool TL>
 __global__ __launch_bounds__(256) void trace_batch_hetero_eqa_kernel(const vpt_ray* __restrict__ rays,
@@ -46,16 +61,10 @@ __global__ __launch_bounds__(256) void trace_batch_hetero_eqa_kernel(const vpt_r
                                                                      const vpt_grid_view* __restrict__ grid, double* out,
                                                                      uint64_t* out_states)
 {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Sampler<false> smp;
-    smp.X = states[i] & 0xFFFFFFFFFFFFull;
-    smp.g = m.g;
-    dv3 L = trace_hetero_eqa<false, TL>(S, GridTrT<TL>::template load<false>(grid), smp, ld3(rays[i].o), ld3(rays[i].d), m);
-    out[3 * i] = L.x;
-    out[3 * i + 1] = L.y;
-    out[3 * i + 2] = L.z;
-    out_states[i] = smp.X;
+    hetero_trace_one(blockIdx.x * blockDim.x + threadIdx.x, rays, states, n, m, out, out_states,
+                     [&](Sampler<false>& smp, dv3 o, dv3 d, const Medium& m) {
+                         return trace_hetero_eqa<false, TL>(S, GridTrT<TL>::template load<false>(grid), smp, o, d, m);
+                     });
 }
 
 /* one equi-angular decision per lane (vpt_grid_eqa.h: vpt_grid_eqa_one; vpt_grid_eqa_probe) */
@@ -103,7 +112,7 @@ static void grid_eqa_probe_launch(const vpt_grid_view* grid, double sigma_t, con
 static int simple_launch(const KParams& K, const DevScene* S, const vpt_hetero_args&, void* stream)
 {
     return with_flags([&](auto count, auto f32) {
-        return vpt_simple_launch(render_kernel_simple<VPT_HETERO_EQUIANGULAR, decltype(count)::value, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, false, TLU, false>,
+        return vpt_simple_launch(render_kernel_simple_eqa<decltype(count)::value, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, TLU>,
                                  K, S, stream);
     }, K.counters != nullptr, K.fb == VPT_FB_F32);
 }

@@ -1,8 +1,9 @@
 /*
- * vpt_hetero_launch.h -- the host side of a launch, shared by the density-grid units (vpt_hetero.hip, vpt_hetero_eqa.hip,
- * vpt_hetero_mis.hip, vpt_hetero_chroma.hip and the units that include them) and vpt_kernels.hip.  Host code only: it
- * names kernels and launches them, and holds no __global__ or __device__ function, so including it leaves a unit's code
- * object what it was (what the units share on the device is vpt_hetero_lds.h's).
+ * vpt_hetero_launch.h -- the host side of a launch, shared by the seven density-grid units (vpt_hetero.hip for estimators
+ * 10 and 11, vpt_hetero_eqa.hip, vpt_hetero_mis.hip, vpt_hetero_chroma.hip, vpt_hetero_residual.hip, vpt_hetero_spectral.hip
+ * for 12 to 16, and the _tl / _em units that include them) and vpt_kernels.hip.  Host code only: it names kernels and
+ * launches them, and holds no __global__ or __device__ function, so including it leaves a unit's code object what it was
+ * (what the units share on the device is vpt_hetero_lds.h's and vpt_hetero_simple.h's).
  */
 #ifndef VPT_HETERO_LAUNCH_H
 #define VPT_HETERO_LAUNCH_H
@@ -50,7 +51,7 @@ static inline int vpt_wave_blocks(int blocks, const vpt::KParams& K)
 }
 
 /* a persistent-wave kernel on as many workgroups as the device holds, clamped as above; `name` stands in the message.
- * a: the kernel's arguments behind (K, S) -- none, estimator 13's track fraction, estimator 14's coefficients */
+ * a: the kernel's arguments behind (K, S) -- none, estimator 13's track fraction, estimator 14's and 16's coefficients */
 template <class Kern, class... A>
 static int vpt_persistent_launch(Kern kern, const char* name, int device, const vpt::KParams& K, const DevScene* S,
                                  void* stream, const A&... a)
@@ -64,8 +65,8 @@ static int vpt_persistent_launch(Kern kern, const char* name, int device, const 
     return (int)VPT_OK;
 }
 
-/* kern: the render_kernel_simple<K.est, ...> (vpt_render_simple.h, or a unit's overload of it) of a render, one lane per
- * pixel: counting mode (K.counters != NULL) and VPT_SIMPLE_KERNEL=1; a: as above, and what picks the overload */
+/* kern: a unit's render_kernel_simple_<unit> of K.est (the body: vpt_hetero_simple.h), one lane per pixel: counting mode
+ * (K.counters != NULL) and VPT_SIMPLE_KERNEL=1; a: as above */
 template <class... A>
 static int vpt_simple_launch(void (*kern)(vpt::KParams, const DevScene*, A...), const vpt::KParams& K, const DevScene* S,
                              void* stream, const A&... a)

@@ -1,8 +1,9 @@
 /*
- * vpt_hetero_lds.h -- what the persistent-wave kernels of the density-grid units (vpt_hetero.hip, vpt_hetero_eqa.hip,
- * vpt_hetero_mis.hip, vpt_hetero_chroma.hip and the units that include them) share on the device: the compile-time
- * switches with their defaults, and the prologue that stages the grid in LDS.  Device code, unlike vpt_hetero_launch.h;
- * the prologue is inlined into each kernel and leaves its code what it was ("One LDS prologue").
+ * vpt_hetero_lds.h -- what the persistent-wave kernels of the seven density-grid units (vpt_hetero.hip, vpt_hetero_eqa.hip,
+ * vpt_hetero_mis.hip, vpt_hetero_chroma.hip, vpt_hetero_residual.hip, vpt_hetero_spectral.hip and the units that include
+ * them) share on the device: the compile-time switches with their defaults, and the prologue that stages the grid in LDS.
+ * Device code, unlike vpt_hetero_launch.h; the prologue is inlined into each kernel and leaves its code what it was
+ * ("One LDS prologue").  The units' one-lane-per-pixel and per-sample kernels share vpt_hetero_simple.h.
  *
  * VPT_HETERO_LDS (1): a grid of at most 64 KiB (16 384 voxels) is staged in LDS once per workgroup; 0 reads every grid
  * from global memory.  VPT_HETERO_LDS_MAJ (1): with local majorants the majorant grid is staged in what the density

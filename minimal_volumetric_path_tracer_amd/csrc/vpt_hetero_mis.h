@@ -95,7 +95,7 @@ VPT_DEV void hetero_mis_medium(const DevScene* __restrict__ S, const GridTrT<TL>
     medium_tail<1, COUNT>(smp, p, Ld, T, e.pdf, xt, ml, true);
 }
 
-/* one camera sample, sequentially (vpt_trace_batch, render_kernel_simple<13>) */
+/* one camera sample, sequentially (vpt_trace_batch, render_kernel_simple_mis) */
 template <bool COUNT, bool LM, bool TL>
 __device__ static dv3 trace_hetero_mis(const DevScene* __restrict__ S, const GridTrT<TL>& tp, double q, Sampler<COUNT>& smp,
                                        dv3 o, dv3 d, const Medium& m)

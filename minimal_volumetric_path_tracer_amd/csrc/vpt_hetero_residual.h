@@ -73,7 +73,7 @@ struct GridResidualTr : GridNoColour {
     }
 };
 
-/* one camera sample, sequentially (vpt_trace_batch, render_kernel_simple<15>): vpt_hetero.h's trace_hetero on this policy */
+/* one camera sample, sequentially (vpt_trace_batch, render_kernel_simple_residual): vpt_hetero.h's trace_hetero on this policy */
 template <bool COUNT, bool TL>
 __device__ static dv3 trace_hetero_residual(const DevScene* __restrict__ S, const GridResidualTr<TL>& tp, Sampler<COUNT>& smp,
                                             dv3 o, dv3 d, const Medium& m)

@@ -3,13 +3,13 @@
  * of their own, as vpt_hetero_eqa.hip is for estimator 12: the code objects of the other estimators stay what they were.
  *
  * hetero_residual_kernel: the persistent-wave loop of vpt_wave.h on vpt_hetero.h's steps (HeteroSteps) with estimator 15's
- * policy.  A lane owns one pixel and runs that pixel's samples strictly in order, so the image is render_kernel_simple<15>'s
+ * policy.  A lane owns one pixel and runs that pixel's samples strictly in order, so the image is render_kernel_simple_residual's
  * bit for bit.  The prologue is stage_grid_control_lds (vpt_hetero_lds.h): stage_grid_lds's budget with the control grid
  * beside the majorants where the 64 KiB hold all three arrays.  The probe kernel runs the same prologue, so the probe's
  * bit-for-bit comparison with the host covers the staged and the global-memory reads.
  *
- * render_kernel_simple<15> is an overload on a tag argument (vpt_render_simple.h's kernel stays what it is): that kernel
- * with trace_hetero_residual in the estimator's place.
+ * render_kernel_simple_residual (one lane per pixel) and the per-sample kernel are thin: each hands a lambda on
+ * trace_hetero_residual to the one body every density-grid unit shares (vpt_hetero_simple.h).
  *
  * Trilinear interpolation: the unit instantiates one value of TL, VPT_HETERO_TL.  Compiled as it stands (0) it holds the
  * nearest-lookup kernels and exports their launches as the table vpt_int_hetero_residual_unit (vpt_hetero.h);
@@ -20,13 +20,11 @@
 
 #include "vpt_wave.h"
 #include "vpt_hetero_residual.h"
+#include "vpt_hetero_simple.h"
 #include "vpt_hetero_lds.h"
 #include "vpt_hetero_launch.h"
 
 namespace vpt {
-
-/* what picks this unit's overload of render_kernel_simple */
-struct ResidualTag {};
 
 template <bool COUNT, int FB, bool TL>
 __global__ __launch_bounds__(256, 2) void hetero_residual_kernel(KParams P, const DevScene* __restrict__ S)
@@ -46,43 +44,14 @@ namespace {
 
 constexpr bool TLU = VPT_HETERO_TL != 0;  /* the unit's value of TL */
 
-/* render_kernel_simple (vpt_render_simple.h) for estimator 15: one lane per pixel, the samples in sequence */
-template <int EST, bool COUNT, int FB, bool TL>
-__global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const DevScene* __restrict__ S, ResidualTag)
+/* render_kernel_simple (vpt_render_simple.h) for estimator 15: hetero_simple_render on trace_hetero_residual */
+template <bool COUNT, int FB, bool TL>
+__global__ __launch_bounds__(256) void render_kernel_simple_residual(KParams P, const DevScene* __restrict__ S)
 {
-    static_assert(EST == VPT_HETERO_RESIDUAL, "the overload with the tag is estimator 15's");
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
-    const int lr = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
-    if (x >= P.w || lr >= P.shard_rows) return;
-    const PixelRow row = pixel_row(P, x, lr);
-    const Medium m = medium_of(P);
-    const dv3 o = mk(P.o[0], P.o[1], P.o[2]);
     const GridResidualTr<TL> tp = GridResidualTr<TL>::template load<true>(P.grid);
-    dv3 acc = mk(0, 0, 0);
-    uint64_t tests = 0, iters = 0, mism = 0;
-    for (int i = 0; i < P.spp; ++i) {
-        Sampler<COUNT> smp;
-        smp.X = vpt_stream_start(P.seed, row.idx, (uint64_t)i);
-        smp.g = P.g;
-        smp.cnt.tests = 0;
-        smp.cnt.iterations = 0;
-        smp.cnt.draw_mismatch = 0;
-        const dv3 dir = camera_dir(P, smp, x, row.y);
-        const dv3 L = trace_hetero_residual<COUNT, TL>(S, tp, smp, o, dir, m);
-        acc = add(L, acc);
-        if (COUNT) {
-            tests += smp.cnt.tests;
-            iters += smp.cnt.iterations;
-            mism += smp.cnt.draw_mismatch;
-        }
-    }
-    store_pixel<FB>(P, x, lr, acc);
-    if (COUNT) {
-        atomicAdd(&P.counters[0], (unsigned long long)tests);
-        atomicAdd(&P.counters[1], (unsigned long long)iters);
-        if (mism) atomicAdd(&P.counters[2], (unsigned long long)mism);
-    }
+    hetero_simple_render<COUNT, FB>(P, [&](Sampler<COUNT>& smp, dv3 o, dv3 dir, const Medium& m) {
+        return trace_hetero_residual<COUNT, TL>(S, tp, smp, o, dir, m);
+    });
 }
 
 /* estimator 15's per-sample call (vpt_hetero_residual.h) */
@@ -93,16 +62,10 @@ __global__ __launch_bounds__(256) void trace_batch_hetero_residual_kernel(const 
                                                                           const vpt_grid_view* __restrict__ grid, double* out,
                                                                           uint64_t* out_states)
 {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Sampler<false> smp;
-    smp.X = states[i] & 0xFFFFFFFFFFFFull;
-    smp.g = m.g;
-    dv3 L = trace_hetero_residual<false, TL>(S, GridResidualTr<TL>::template load<true>(grid), smp, ld3(rays[i].o), ld3(rays[i].d), m);
-    out[3 * i] = L.x;
-    out[3 * i + 1] = L.y;
-    out[3 * i + 2] = L.z;
-    out_states[i] = smp.X;
+    hetero_trace_one(blockIdx.x * blockDim.x + threadIdx.x, rays, states, n, m, out, out_states,
+                     [&](Sampler<false>& smp, dv3 o, dv3 d, const Medium& m) {
+                         return trace_hetero_residual<false, TL>(S, GridResidualTr<TL>::template load<true>(grid), smp, o, d, m);
+                     });
 }
 
 /* the residual walker (vpt_grid.h), one ray per lane (vpt_grid_residual_probe), behind the render kernel's prologue: every
@@ -148,8 +111,8 @@ static void grid_residual_probe_launch(const vpt_grid_view* grid, double sigma_t
 static int simple_launch(const KParams& K, const DevScene* S, const vpt_hetero_args&, void* stream)
 {
     return with_flags([&](auto count, auto f32) {
-        return vpt_simple_launch(render_kernel_simple<VPT_HETERO_RESIDUAL, decltype(count)::value, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, TLU>,
-                                 K, S, stream, ResidualTag{});
+        return vpt_simple_launch(render_kernel_simple_residual<decltype(count)::value, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, TLU>,
+                                 K, S, stream);
     }, K.counters != nullptr, K.fb == VPT_FB_F32);
 }
 

@@ -154,7 +154,7 @@ VPT_DEV void hetero_spectral_medium(const DevScene* __restrict__ S, const GridSp
     p.depth++;
 }
 
-/* one camera sample, sequentially (vpt_trace_batch, render_kernel_simple<16>) */
+/* one camera sample, sequentially (vpt_trace_batch, render_kernel_simple_spectral) */
 template <bool COUNT, bool LM, bool TL>
 __device__ static dv3 trace_hetero_spectral(const DevScene* __restrict__ S, const GridSpectralTr<LM, TL>& tp, Sampler<COUNT>& smp,
                                             dv3 o, dv3 d, const Medium& m)

@@ -3,13 +3,13 @@
  * of their own, as vpt_hetero_chroma.hip is for estimator 14: the code objects of the other estimators stay what they were.
  *
  * hetero_spectral_kernel: the persistent-wave loop of vpt_wave.h on estimator 16's steps (HeteroSpectralSteps).  A lane owns
- * one pixel and runs that pixel's samples strictly in order, so the image is render_kernel_simple<16>'s bit for bit.  The
+ * one pixel and runs that pixel's samples strictly in order, so the image is render_kernel_simple_spectral's bit for bit.  The
  * prologue that stages a grid of at most 64 KiB in LDS, and with local majorants the majorant grid in what the density
  * left of the budget, is stage_grid_lds (vpt_hetero_lds.h), every density-grid kernel's.
  *
- * The six per-channel coefficients (ChromaCoef) are a kernel argument of every kernel here (KParams keeps its layout),
- * so render_kernel_simple<16> is an overload with that argument: vpt_render_simple.h's kernel with trace_hetero_spectral
- * in the estimator's place.
+ * The six per-channel coefficients (ChromaCoef) are a kernel argument of every kernel here (KParams keeps its layout).
+ * render_kernel_simple_spectral (one lane per pixel) and the per-sample kernel are thin: each hands a lambda on
+ * trace_hetero_spectral to the one body every density-grid unit shares (vpt_hetero_simple.h).
  *
  * Trilinear interpolation: the unit instantiates one value of TL, VPT_HETERO_TL.  Compiled as it stands (0) it holds the
  * nearest-lookup kernels and exports their launches as the table vpt_int_hetero_spectral_unit (vpt_hetero.h);
@@ -20,6 +20,7 @@
 
 #include "vpt_wave.h"
 #include "vpt_hetero_spectral.h"
+#include "vpt_hetero_simple.h"
 #include "vpt_hetero_lds.h"
 #include "vpt_hetero_launch.h"
 
@@ -43,44 +44,14 @@ namespace {
 
 constexpr bool TLU = VPT_HETERO_TL != 0;  /* the unit's value of TL */
 
-/* render_kernel_simple (vpt_render_simple.h) for estimator 16: one lane per pixel, the samples in sequence; c holds the
- * per-channel coefficients */
-template <int EST, bool COUNT, int FB, bool LM, bool TL>
-__global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const DevScene* __restrict__ S, ChromaCoef c)
+/* render_kernel_simple (vpt_render_simple.h) for estimator 16: hetero_simple_render on trace_hetero_spectral */
+template <bool COUNT, int FB, bool LM, bool TL>
+__global__ __launch_bounds__(256) void render_kernel_simple_spectral(KParams P, const DevScene* __restrict__ S, ChromaCoef c)
 {
-    static_assert(EST == VPT_HETERO_SPECTRAL, "the overload with per-channel coefficients is estimator 16's here");
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
-    const int lr = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
-    if (x >= P.w || lr >= P.shard_rows) return;
-    const PixelRow row = pixel_row(P, x, lr);
-    const Medium m = medium_of(P);
-    const dv3 o = mk(P.o[0], P.o[1], P.o[2]);
     const GridSpectralTr<LM, TL> tp = GridSpectralTr<LM, TL>::template load<LM>(P.grid, c);
-    dv3 acc = mk(0, 0, 0);
-    uint64_t tests = 0, iters = 0, mism = 0;
-    for (int i = 0; i < P.spp; ++i) {
-        Sampler<COUNT> smp;
-        smp.X = vpt_stream_start(P.seed, row.idx, (uint64_t)i);
-        smp.g = P.g;
-        smp.cnt.tests = 0;
-        smp.cnt.iterations = 0;
-        smp.cnt.draw_mismatch = 0;
-        const dv3 dir = camera_dir(P, smp, x, row.y);
-        const dv3 L = trace_hetero_spectral<COUNT, LM, TL>(S, tp, smp, o, dir, m);
-        acc = add(L, acc);
-        if (COUNT) {
-            tests += smp.cnt.tests;
-            iters += smp.cnt.iterations;
-            mism += smp.cnt.draw_mismatch;
-        }
-    }
-    store_pixel<FB>(P, x, lr, acc);
-    if (COUNT) {
-        atomicAdd(&P.counters[0], (unsigned long long)tests);
-        atomicAdd(&P.counters[1], (unsigned long long)iters);
-        if (mism) atomicAdd(&P.counters[2], (unsigned long long)mism);
-    }
+    hetero_simple_render<COUNT, FB>(P, [&](Sampler<COUNT>& smp, dv3 o, dv3 dir, const Medium& m) {
+        return trace_hetero_spectral<COUNT, LM, TL>(S, tp, smp, o, dir, m);
+    });
 }
 
 /* estimator 16's per-sample call (vpt_hetero_spectral.h) */
@@ -91,17 +62,11 @@ __global__ __launch_bounds__(256) void trace_batch_hetero_spectral_kernel(const 
                                                                           const vpt_grid_view* __restrict__ grid, ChromaCoef c,
                                                                           double* out, uint64_t* out_states)
 {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Sampler<false> smp;
-    smp.X = states[i] & 0xFFFFFFFFFFFFull;
-    smp.g = m.g;
-    dv3 L = trace_hetero_spectral<false, LM, TL>(S, GridSpectralTr<LM, TL>::template load<LM>(grid, c), smp, ld3(rays[i].o),
-                                                 ld3(rays[i].d), m);
-    out[3 * i] = L.x;
-    out[3 * i + 1] = L.y;
-    out[3 * i + 2] = L.z;
-    out_states[i] = smp.X;
+    hetero_trace_one(blockIdx.x * blockDim.x + threadIdx.x, rays, states, n, m, out, out_states,
+                     [&](Sampler<false>& smp, dv3 o, dv3 d, const Medium& m) {
+                         return trace_hetero_spectral<false, LM, TL>(S, GridSpectralTr<LM, TL>::template load<LM>(grid, c), smp,
+                                                                      o, d, m);
+                     });
 }
 
 /* the spectral delta track, one ray per lane (vpt_grid_spectral.h; vpt_grid_spectral_probe).  beta: 3 doubles per ray, or
@@ -195,7 +160,7 @@ static void grid_spectral_ratio_probe_launch(const vpt_grid_view* grid, bool lm,
 static int simple_launch(const KParams& K, const DevScene* S, const vpt_hetero_args& a, void* stream)
 {
     return with_flags([&](auto lmc, auto count, auto f32) {
-        return vpt_simple_launch(render_kernel_simple<VPT_HETERO_SPECTRAL, decltype(count)::value, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU>,
+        return vpt_simple_launch(render_kernel_simple_spectral<decltype(count)::value, decltype(f32)::value ? VPT_FB_F32 : VPT_FB_F64, decltype(lmc)::value, TLU>,
                                  K, S, stream, a.c);
     }, a.lm, K.counters != nullptr, K.fb == VPT_FB_F32);
 }

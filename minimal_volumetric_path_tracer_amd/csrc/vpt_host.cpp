@@ -242,16 +242,38 @@ static void probe_view(vpt_grid_view* G, std::vector<float>& maj, const vpt_grid
     }
 }
 
+/* the host probes' refusals of a majorant block below min_block (0, or the residual probe's 1: its control grid is per
+ * super-voxel) and of an interpolation mode that does not exist */
+static int probe_block_interp_check(const char* who, int block, int min_block, int interp)
+{
+    if (block < min_block)
+        return min_block ? vpt_fail(VPT_E_INVALID, "%s: block %d (>= 1: the control grid is per super-voxel)", who, block)
+                         : vpt_fail(VPT_E_INVALID, "%s: block %d (0 = the global majorant, else >= 1)", who, block);
+    if (interp != VPT_GRID_NEAREST && interp != VPT_GRID_TRILINEAR)
+        return vpt_fail(VPT_E_INVALID, "%s: interp %d (0 = nearest, 1 = trilinear)", who, interp);
+    return VPT_OK;
+}
+
+/* the per-channel coefficients of the chromatic probes: finite, >= 0, and an extinction st[k] = sa[k] + ss[k] > 0 */
+static int probe_channels_check(const char* who, const double sa[3], const double ss[3], double st[3])
+{
+    for (int k = 0; k < 3; ++k) {
+        if (!(sa[k] >= 0.0 && sa[k] - sa[k] == 0.0 && ss[k] >= 0.0 && ss[k] - ss[k] == 0.0))  /* a NaN fails both */
+            return vpt_fail(VPT_E_INVALID, "%s: channel %d: sa %g, ss %g (finite, >= 0)", who, k, sa[k], ss[k]);
+        st[k] = sa[k] + ss[k];
+        if (!(st[k] > 0.0)) return vpt_fail(VPT_E_INVALID, "%s: channel %d has no extinction", who, k);
+    }
+    return VPT_OK;
+}
+
 static int grid_probe_host(const char* who, const vpt_grid_desc* desc, const float* density, int block, int interp,
                            double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states, int n, double* tau,
                            double* t_coll, uint64_t* states_out, uint32_t* steps)
 {
     vpt_clear_error();
     if (!rays || !tmax || !states || n < 0) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
-    if (block < 0) return vpt_fail(VPT_E_INVALID, "%s: block %d (0 = the global majorant, else >= 1)", who, block);
-    if (interp != VPT_GRID_NEAREST && interp != VPT_GRID_TRILINEAR)
-        return vpt_fail(VPT_E_INVALID, "%s: interp %d (0 = nearest, 1 = trilinear)", who, interp);
-    int rc = vpt_int_grid_check(desc, density, who);
+    int rc = probe_block_interp_check(who, block, 0, interp);
+    if (!rc) rc = vpt_int_grid_check(desc, density, who);
     if (rc) return rc;
     vpt_grid_view G;
     std::vector<float> maj;
@@ -276,10 +298,8 @@ int vpt_grid_emission_probe_host(const vpt_grid_desc* desc, const float* density
     const char* who = "vpt_grid_emission_probe_host";
     vpt_clear_error();
     if (!rays || !tmax || !states || !eps || n < 0) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
-    if (block < 0) return vpt_fail(VPT_E_INVALID, "%s: block %d (0 = the global majorant, else >= 1)", who, block);
-    if (interp != VPT_GRID_NEAREST && interp != VPT_GRID_TRILINEAR)
-        return vpt_fail(VPT_E_INVALID, "%s: interp %d (0 = nearest, 1 = trilinear)", who, interp);
-    int rc = vpt_int_grid_check(desc, density, who);
+    int rc = probe_block_interp_check(who, block, 0, interp);
+    if (!rc) rc = vpt_int_grid_check(desc, density, who);
     if (rc) return rc;
     rc = vpt_int_emission_check(eps, (size_t)desc->nx * (size_t)desc->ny * (size_t)desc->nz, nullptr, who);
     if (rc) return rc;
@@ -307,10 +327,8 @@ static int grid_ratio_probe_host(const char* who, const vpt_grid_desc* desc, con
 {
     vpt_clear_error();
     if (!rays || !tmax || !states || n < 0) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
-    if (block < 0) return vpt_fail(VPT_E_INVALID, "%s: block %d (0 = the global majorant, else >= 1)", who, block);
-    if (interp != VPT_GRID_NEAREST && interp != VPT_GRID_TRILINEAR)
-        return vpt_fail(VPT_E_INVALID, "%s: interp %d (0 = nearest, 1 = trilinear)", who, interp);
-    int rc = vpt_int_grid_check(desc, density, who);
+    int rc = probe_block_interp_check(who, block, 0, interp);
+    if (!rc) rc = vpt_int_grid_check(desc, density, who);
     if (rc) return rc;
     vpt_grid_view G;
     std::vector<float> maj;
@@ -334,10 +352,8 @@ int vpt_grid_residual_probe_host(const vpt_grid_desc* desc, const float* density
     const char* who = "vpt_grid_residual_probe_host";
     vpt_clear_error();
     if (!rays || !tmax || !states || n < 0) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
-    if (block < 1) return vpt_fail(VPT_E_INVALID, "%s: block %d (>= 1: the control grid is per super-voxel)", who, block);
-    if (interp != VPT_GRID_NEAREST && interp != VPT_GRID_TRILINEAR)
-        return vpt_fail(VPT_E_INVALID, "%s: interp %d (0 = nearest, 1 = trilinear)", who, interp);
-    int rc = vpt_int_grid_check(desc, density, who);
+    int rc = probe_block_interp_check(who, block, 1, interp);
+    if (!rc) rc = vpt_int_grid_check(desc, density, who);
     if (rc) return rc;
     /* the view with the majorant allocation as the context keeps it: the maxima, and behind them the minima */
     const int32_t dims[3] = {desc->nx, desc->ny, desc->nz};
@@ -410,9 +426,8 @@ int vpt_grid_eqa_probe_host(const vpt_grid_desc* desc, const float* density, int
     const char* who = "vpt_grid_eqa_probe_host";
     vpt_clear_error();
     if (!rays || !tmax || !light || !states || n < 0) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
-    if (interp != VPT_GRID_NEAREST && interp != VPT_GRID_TRILINEAR)
-        return vpt_fail(VPT_E_INVALID, "%s: interp %d (0 = nearest, 1 = trilinear)", who, interp);
-    int rc = vpt_int_grid_check(desc, density, who);
+    int rc = probe_block_interp_check(who, 0, 0, interp);  /* no block: nothing tracks */
+    if (!rc) rc = vpt_int_grid_check(desc, density, who);
     if (rc) return rc;
     vpt_grid_view G;
     std::vector<float> maj;
@@ -439,11 +454,10 @@ int vpt_grid_mis_probe_host(const vpt_grid_desc* desc, const float* density, int
     const char* who = "vpt_grid_mis_probe_host";
     vpt_clear_error();
     if (!rays || !tmax || !light || !states || n < 0) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
-    if (block < 0) return vpt_fail(VPT_E_INVALID, "%s: block %d (0 = the global majorant, else >= 1)", who, block);
-    if (interp != VPT_GRID_NEAREST && interp != VPT_GRID_TRILINEAR)
-        return vpt_fail(VPT_E_INVALID, "%s: interp %d (0 = nearest, 1 = trilinear)", who, interp);
+    int rc = probe_block_interp_check(who, block, 0, interp);
+    if (rc) return rc;
     if (!(q >= 0.0 && q <= 1.0)) return vpt_fail(VPT_E_INVALID, "%s: q %g (finite, in [0, 1])", who, q);
-    int rc = vpt_int_grid_check(desc, density, who);
+    rc = vpt_int_grid_check(desc, density, who);
     if (rc) return rc;
     vpt_grid_view G;
     std::vector<float> maj;
@@ -475,17 +489,10 @@ int vpt_grid_chroma_probe_host(const vpt_grid_desc* desc, const float* density, 
     const char* who = "vpt_grid_chroma_probe_host";
     vpt_clear_error();
     if (!sa || !ss || !rays || !tmax || !states || n < 0) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
-    if (block < 0) return vpt_fail(VPT_E_INVALID, "%s: block %d (0 = the global majorant, else >= 1)", who, block);
-    if (interp != VPT_GRID_NEAREST && interp != VPT_GRID_TRILINEAR)
-        return vpt_fail(VPT_E_INVALID, "%s: interp %d (0 = nearest, 1 = trilinear)", who, interp);
+    int rc = probe_block_interp_check(who, block, 0, interp);
     double st[3];
-    for (int k = 0; k < 3; ++k) {
-        if (!(sa[k] >= 0.0 && sa[k] - sa[k] == 0.0 && ss[k] >= 0.0 && ss[k] - ss[k] == 0.0))  /* a NaN fails both */
-            return vpt_fail(VPT_E_INVALID, "%s: channel %d: sa %g, ss %g (finite, >= 0)", who, k, sa[k], ss[k]);
-        st[k] = sa[k] + ss[k];
-        if (!(st[k] > 0.0)) return vpt_fail(VPT_E_INVALID, "%s: channel %d has no extinction", who, k);
-    }
-    int rc = vpt_int_grid_check(desc, density, who);
+    if (!rc) rc = probe_channels_check(who, sa, ss, st);
+    if (!rc) rc = vpt_int_grid_check(desc, density, who);
     if (rc) return rc;
     vpt_grid_view G;
     std::vector<float> maj;
@@ -516,17 +523,10 @@ int vpt_grid_spectral_probe_host(const vpt_grid_desc* desc, const float* density
     const char* who = "vpt_grid_spectral_probe_host";
     vpt_clear_error();
     if (!sa || !ss || !rays || !tmax || !states || n < 0) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
-    if (block < 0) return vpt_fail(VPT_E_INVALID, "%s: block %d (0 = the global majorant, else >= 1)", who, block);
-    if (interp != VPT_GRID_NEAREST && interp != VPT_GRID_TRILINEAR)
-        return vpt_fail(VPT_E_INVALID, "%s: interp %d (0 = nearest, 1 = trilinear)", who, interp);
+    int rc = probe_block_interp_check(who, block, 0, interp);
     double st[3];
-    for (int k = 0; k < 3; ++k) {
-        if (!(sa[k] >= 0.0 && sa[k] - sa[k] == 0.0 && ss[k] >= 0.0 && ss[k] - ss[k] == 0.0))  /* a NaN fails both */
-            return vpt_fail(VPT_E_INVALID, "%s: channel %d: sa %g, ss %g (finite, >= 0)", who, k, sa[k], ss[k]);
-        st[k] = sa[k] + ss[k];
-        if (!(st[k] > 0.0)) return vpt_fail(VPT_E_INVALID, "%s: channel %d has no extinction", who, k);
-    }
-    int rc = vpt_int_grid_check(desc, density, who);
+    if (!rc) rc = probe_channels_check(who, sa, ss, st);
+    if (!rc) rc = vpt_int_grid_check(desc, density, who);
     if (rc) return rc;
     vpt_grid_view G;
     std::vector<float> maj;

@@ -3,8 +3,9 @@
  *
  * A render of the estimators 0-5 runs on the workgroup task pool (pool_kernel, vpt_pool.h) and reduce_kernel;
  * ray marching (6-9), counting mode and VPT_SIMPLE_KERNEL=1 run render_kernel_simple (vpt_render_simple.h), one
- * lane per pixel; estimator 10's kernels live in vpt_hetero.hip.  render_kernel, the persistent-wave loop of
- * vpt_wave.h, is compiled only into -DVPT_DEBUG_ENV=1 builds.  The rest are the per-sample calls and the probes.
+ * lane per pixel; the kernels of estimators 10 to 16 live in the density-grid units (vpt_hetero*.hip).  render_kernel,
+ * the persistent-wave loop of vpt_wave.h, is compiled only into -DVPT_DEBUG_ENV=1 builds.  The rest are the per-sample
+ * calls and the probes.
  */
 #include <hip/hip_runtime.h>
 
@@ -108,6 +109,29 @@ public:
 private:
     std::vector<void*> owned_;
     hipError_t err_ = hipSuccess;
+};
+
+/* What every device probe of the density grid stages first, on the context's device: the rays, their stream states and
+ * tmax, and the array of the states behind the walk.  The probe adds its own arrays, launches and copies down as with
+ * any Staging */
+struct ProbeStaging : Staging {
+    size_t nn = 0;
+    vpt_ray* dr = nullptr;
+    uint64_t *ds = nullptr, *dso = nullptr;
+    double* dtm = nullptr;
+    int stage(int device, const vpt_ray* rays, const uint64_t* states, const double* tmax, int n)
+    {
+        HIP_OK(hipSetDevice(device));
+        nn = (size_t)n;
+        dr = alloc<vpt_ray>(nn);
+        ds = alloc<uint64_t>(nn);
+        dso = alloc<uint64_t>(nn);
+        dtm = alloc<double>(nn);
+        up(dr, rays, nn);
+        up(ds, states, nn);
+        up(dtm, tmax, nn);
+        return VPT_OK;
+    }
 };
 
 /* the persistent-wave loop (vpt_wave.h) on the estimators 0-9: the round-1 design, which the pool kernel
@@ -589,8 +613,8 @@ static vpt_hetero_args hetero_args(const vpt_context* ctx, double sigma_a, doubl
 /* estimators 10, 11 (by K.est: hetero_kernel / hetero_ratio_kernel), 12 (hetero_eqa_kernel; the majorant block plays no
  * part), 13 (hetero_mis_kernel, with the context's track fraction), 14 (hetero_chroma_kernel, with the coefficients
  * of the context's medium colour), 15 (hetero_residual_kernel) and 16 (hetero_spectral_kernel, with the same coefficients)
- * on the stream's queue word; counting mode and
- * VPT_SIMPLE_KERNEL=1: render_kernel_simple<K.est> */
+ * on the stream's queue word; counting mode and VPT_SIMPLE_KERNEL=1: the unit's render_kernel_simple_<unit> (one body,
+ * vpt_hetero_simple.h) */
 static int launch_hetero(vpt_context* ctx, KParams K, hipStream_t stream)
 {
     const vpt_hetero_unit& u = hetero_unit(ctx, K.est);
@@ -1165,22 +1189,37 @@ int vpt_set_grid_interpolation(vpt_context* ctx, int mode)
     return VPT_OK;
 }
 
+/* how every device probe of the density grid opens; args_ok: the context and the entry point's arrays are there */
+static int grid_probe_open(const vpt_context* ctx, const char* who, bool args_ok)
+{
+    vpt_clear_error();
+    if (!args_ok) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
+    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "%s: no density grid set (vpt_set_density_grid)", who);
+    return VPT_OK;
+}
+
+/* the chromatic probes' coefficients (chroma_coef), or the refusal of a medium they cannot walk */
+static int probe_chroma_coef(const vpt_context* ctx, const char* who, double sigma_a, double sigma_s, ChromaCoef* cc)
+{
+    if (!is_finite(sigma_a) || !is_finite(sigma_s) || sigma_a < 0 || sigma_s < 0)
+        return vpt_fail(VPT_E_INVALID, "%s: sigma_a/sigma_s must be finite and >= 0", who);
+    *cc = chroma_coef(ctx, sigma_a, sigma_s);
+    for (int k = 0; k < 3; ++k)
+        if (!(cc->st[k] > 0)) return vpt_fail(VPT_E_INVALID, "%s: channel %d has no extinction", who, k);
+    return VPT_OK;
+}
+
 /* vpt_grid_probe (lm false: the global-majorant track whatever the context's setting) and vpt_grid_probe_lm */
 static int grid_probe(vpt_context* ctx, bool lm, double sigma_t, const vpt_ray* rays, const double* tmax,
                       const uint64_t* states, int n, double* tau, double* t_coll, uint64_t* states_out, uint32_t* steps)
 {
     const char* who = lm ? "vpt_grid_probe_lm" : "vpt_grid_probe";
-    vpt_clear_error();
-    if (!ctx || !rays || !tmax || !states || !tau || !t_coll || !states_out || n < 0)
-        return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
-    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "%s: no density grid set (vpt_set_density_grid)", who);
+    if (int rc = grid_probe_open(ctx, who, ctx && rays && tmax && states && tau && t_coll && states_out && n >= 0)) return rc;
     if (n == 0) return VPT_OK;
-    HIP_OK(hipSetDevice(ctx->device));
-    Staging st;
-    const size_t nn = (size_t)n;
-    vpt_ray* dr = st.alloc<vpt_ray>(nn);
-    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn);
-    double *dtm = st.alloc<double>(nn), *dtau = st.alloc<double>(nn), *dtc = st.alloc<double>(nn);
+    ProbeStaging st;
+    if (int rc = st.stage(ctx->device, rays, states, tmax, n)) return rc;
+    const size_t nn = st.nn;
+    double *dtau = st.alloc<double>(nn), *dtc = st.alloc<double>(nn);
     uint32_t* dst = st.alloc_if(steps, nn);
     /* the existing probe keeps its global-majorant behaviour: a copy of the view without the majorant grid */
     const vpt_grid_view* dview = ctx->d_grid;
@@ -1191,16 +1230,13 @@ static int grid_probe(vpt_context* ctx, bool lm, double sigma_t, const vpt_ray* 
         st.up(dplain, &G, 1);
         dview = dplain;
     }
-    st.up(dr, rays, nn);
-    st.up(ds, states, nn);
-    st.up(dtm, tmax, nn);
     st.launch([&] {
         hetero_unit(VPT_HETERO_FREE, ctx->h_grid.interp != 0, false)
-            .grid_probe_launch(dview, lm && ctx->h_grid.block > 0, sigma_t, dr, dtm, ds, n, dtau, dtc, dso, dst);
+            .grid_probe_launch(dview, lm && ctx->h_grid.block > 0, sigma_t, st.dr, st.dtm, st.ds, n, dtau, dtc, st.dso, dst);
     });
     st.down(tau, dtau, nn);
     st.down(t_coll, dtc, nn);
-    st.down(states_out, dso, nn);
+    st.down(states_out, st.dso, nn);
     st.down(steps, dst, nn);
     return st.status(who);
 }
@@ -1220,27 +1256,20 @@ int vpt_grid_probe_lm(vpt_context* ctx, double sigma_t, const vpt_ray* rays, con
 int vpt_grid_ratio_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax,
                          const uint64_t* states, int n, double* that, uint64_t* states_out, uint32_t* steps)
 {
-    vpt_clear_error();
-    if (!ctx || !rays || !tmax || !states || !that || !states_out || n < 0)
-        return vpt_fail(VPT_E_INVALID, "vpt_grid_ratio_probe: bad arguments");
-    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "vpt_grid_ratio_probe: no density grid set (vpt_set_density_grid)");
+    if (int rc = grid_probe_open(ctx, "vpt_grid_ratio_probe", ctx && rays && tmax && states && that && states_out && n >= 0))
+        return rc;
     if (n == 0) return VPT_OK;
-    HIP_OK(hipSetDevice(ctx->device));
-    Staging st;
-    const size_t nn = (size_t)n;
-    vpt_ray* dr = st.alloc<vpt_ray>(nn);
-    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn);
-    double *dtm = st.alloc<double>(nn), *dth = st.alloc<double>(nn);
+    ProbeStaging st;
+    if (int rc = st.stage(ctx->device, rays, states, tmax, n)) return rc;
+    const size_t nn = st.nn;
+    double* dth = st.alloc<double>(nn);
     uint32_t* dst = st.alloc_if(steps, nn);
-    st.up(dr, rays, nn);
-    st.up(ds, states, nn);
-    st.up(dtm, tmax, nn);
     st.launch([&] {
         hetero_unit(VPT_HETERO_RATIO, ctx->h_grid.interp != 0, false)
-            .grid_ratio_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, sigma_t, dr, dtm, ds, n, dth, dso, dst);
+            .grid_ratio_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, sigma_t, st.dr, st.dtm, st.ds, n, dth, st.dso, dst);
     });
     st.down(that, dth, nn);
-    st.down(states_out, dso, nn);
+    st.down(states_out, st.dso, nn);
     st.down(steps, dst, nn);
     return st.status("vpt_grid_ratio_probe");
 }
@@ -1249,30 +1278,25 @@ int vpt_grid_eqa_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, co
                        const uint64_t* states, int n, double* psurf, double* dist, double* pdf, double* T, double* rho_t,
                        uint64_t* states_out)
 {
-    vpt_clear_error();
-    if (!ctx || !rays || !tmax || !light || !states || !psurf || !dist || !pdf || !T || !rho_t || !states_out || n < 0)
-        return vpt_fail(VPT_E_INVALID, "vpt_grid_eqa_probe: bad arguments");
-    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "vpt_grid_eqa_probe: no density grid set (vpt_set_density_grid)");
+    if (int rc = grid_probe_open(ctx, "vpt_grid_eqa_probe",
+                                 ctx && rays && tmax && light && states && psurf && dist && pdf && T && rho_t && states_out &&
+                                     n >= 0))
+        return rc;
     if (n == 0) return VPT_OK;
-    HIP_OK(hipSetDevice(ctx->device));
-    Staging st;
-    const size_t nn = (size_t)n;
-    vpt_ray* dr = st.alloc<vpt_ray>(nn);
-    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn);
-    double *dtm = st.alloc<double>(nn), *dl = st.alloc<double>(3 * nn);
+    ProbeStaging st;
+    if (int rc = st.stage(ctx->device, rays, states, tmax, n)) return rc;
+    const size_t nn = st.nn;
+    double* dl = st.alloc<double>(3 * nn);
     double* dres = st.alloc<double>(5 * nn);  /* the five result arrays, one behind the other */
-    st.up(dr, rays, nn);
-    st.up(ds, states, nn);
-    st.up(dtm, tmax, nn);
     st.up(dl, light, 3 * nn);
     st.launch([&] {
         hetero_unit(ctx, VPT_HETERO_EQUIANGULAR)
-            .grid_eqa_probe_launch(ctx->d_grid, sigma_t, dr, dtm, dl, ds, n, dres, dres + nn, dres + 2 * nn, dres + 3 * nn,
-                                   dres + 4 * nn, dso);
+            .grid_eqa_probe_launch(ctx->d_grid, sigma_t, st.dr, st.dtm, dl, st.ds, n, dres, dres + nn, dres + 2 * nn, dres + 3 * nn,
+                                   dres + 4 * nn, st.dso);
     });
     double* const res[5] = {psurf, dist, pdf, T, rho_t};
     for (int k = 0; k < 5; ++k) st.down(res[k], dres + (size_t)k * nn, nn);
-    st.down(states_out, dso, nn);
+    st.down(states_out, st.dso, nn);
     return st.status("vpt_grid_eqa_probe");
 }
 
@@ -1280,35 +1304,29 @@ int vpt_grid_mis_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, co
                        const uint64_t* states, int n, double* psurf, int32_t* strategy, double* dist, double* pdf, double* pe,
                        double* T, double* rho_t, uint32_t* steps, uint64_t* states_out)
 {
-    vpt_clear_error();
-    if (!ctx || !rays || !tmax || !light || !states || !psurf || !strategy || !dist || !pdf || !pe || !T || !rho_t || !steps ||
-        !states_out || n < 0)
-        return vpt_fail(VPT_E_INVALID, "vpt_grid_mis_probe: bad arguments");
-    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "vpt_grid_mis_probe: no density grid set (vpt_set_density_grid)");
+    if (int rc = grid_probe_open(ctx, "vpt_grid_mis_probe",
+                                 ctx && rays && tmax && light && states && psurf && strategy && dist && pdf && pe && T && rho_t &&
+                                     steps && states_out && n >= 0))
+        return rc;
     if (n == 0) return VPT_OK;
-    HIP_OK(hipSetDevice(ctx->device));
-    Staging st;
-    const size_t nn = (size_t)n;
-    vpt_ray* dr = st.alloc<vpt_ray>(nn);
-    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn);
-    double *dtm = st.alloc<double>(nn), *dl = st.alloc<double>(3 * nn);
+    ProbeStaging st;
+    if (int rc = st.stage(ctx->device, rays, states, tmax, n)) return rc;
+    const size_t nn = st.nn;
+    double* dl = st.alloc<double>(3 * nn);
     double* dres = st.alloc<double>(6 * nn);  /* the six result arrays of doubles, one behind the other */
     int32_t* dsg = st.alloc<int32_t>(nn);
     uint32_t* dst = st.alloc<uint32_t>(nn);
-    st.up(dr, rays, nn);
-    st.up(ds, states, nn);
-    st.up(dtm, tmax, nn);
     st.up(dl, light, 3 * nn);
     st.launch([&] {
         hetero_unit(ctx, VPT_HETERO_MIS)
-            .grid_mis_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, sigma_t, ctx->mis_fraction, dr, dtm, dl, ds, n, dres,
-                                   dsg, dst, dso);
+            .grid_mis_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, sigma_t, ctx->mis_fraction, st.dr, st.dtm, dl, st.ds, n,
+                                   dres, dsg, dst, st.dso);
     });
     double* const res[6] = {psurf, dist, pdf, pe, T, rho_t};
     for (int k = 0; k < 6; ++k) st.down(res[k], dres + (size_t)k * nn, nn);
     st.down(strategy, dsg, nn);
     st.down(steps, dst, nn);
-    st.down(states_out, dso, nn);
+    st.down(states_out, st.dso, nn);
     return st.status("vpt_grid_mis_probe");
 }
 
@@ -1316,111 +1334,89 @@ int vpt_grid_chroma_probe(vpt_context* ctx, double sigma_a, double sigma_s, cons
                           const uint64_t* states, int n, int32_t* hero, double* t_coll, double* tau, double* w, uint32_t* steps,
                           uint64_t* states_out)
 {
-    vpt_clear_error();
-    if (!ctx || !rays || !tmax || !states || !hero || !t_coll || !tau || !w || !steps || !states_out || n < 0)
-        return vpt_fail(VPT_E_INVALID, "vpt_grid_chroma_probe: bad arguments");
-    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "vpt_grid_chroma_probe: no density grid set (vpt_set_density_grid)");
-    if (!is_finite(sigma_a) || !is_finite(sigma_s) || sigma_a < 0 || sigma_s < 0)
-        return vpt_fail(VPT_E_INVALID, "vpt_grid_chroma_probe: sigma_a/sigma_s must be finite and >= 0");
-    const ChromaCoef cc = chroma_coef(ctx, sigma_a, sigma_s);
-    for (int k = 0; k < 3; ++k)
-        if (!(cc.st[k] > 0)) return vpt_fail(VPT_E_INVALID, "vpt_grid_chroma_probe: channel %d has no extinction", k);
-    if (n == 0) return VPT_OK;
-    HIP_OK(hipSetDevice(ctx->device));
-    Staging st;
-    const size_t nn = (size_t)n;
-    vpt_ray* dr = st.alloc<vpt_ray>(nn);
-    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn);
-    double* dtm = st.alloc<double>(nn);
+    const char* who = "vpt_grid_chroma_probe";
+    ChromaCoef cc;
+    int rc = grid_probe_open(ctx, who,
+                             ctx && rays && tmax && states && hero && t_coll && tau && w && steps && states_out && n >= 0);
+    if (!rc) rc = probe_chroma_coef(ctx, who, sigma_a, sigma_s, &cc);
+    if (rc || n == 0) return rc;
+    ProbeStaging st;
+    rc = st.stage(ctx->device, rays, states, tmax, n);
+    if (rc) return rc;
+    const size_t nn = st.nn;
     double* dres = st.alloc<double>(5 * nn);  /* t_coll, tau and the three weights, one array behind the other */
     int32_t* dh = st.alloc<int32_t>(nn);
     uint32_t* dst = st.alloc<uint32_t>(nn);
-    st.up(dr, rays, nn);
-    st.up(ds, states, nn);
-    st.up(dtm, tmax, nn);
     st.launch([&] {
         hetero_unit(ctx, VPT_HETERO_CHROMATIC)
-            .grid_chroma_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, cc, dr, dtm, ds, n, dres, dh, dst, dso);
+            .grid_chroma_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, cc, st.dr, st.dtm, st.ds, n, dres, dh, dst, st.dso);
     });
     st.down(t_coll, dres, nn);
     st.down(tau, dres + nn, nn);
     st.down(w, dres + 2 * nn, 3 * nn);  /* w[c * n + i] */
     st.down(hero, dh, nn);
     st.down(steps, dst, nn);
-    st.down(states_out, dso, nn);
-    return st.status("vpt_grid_chroma_probe");
+    st.down(states_out, st.dso, nn);
+    return st.status(who);
 }
 
 int vpt_grid_spectral_probe(vpt_context* ctx, double sigma_a, double sigma_s, const vpt_ray* rays, const double* tmax,
                             const double* beta, const uint64_t* states, int n, double* t_coll, double* w, uint32_t* steps,
                             uint64_t* states_out, double* T, uint32_t* ratio_steps, uint64_t* ratio_states_out)
 {
-    vpt_clear_error();
-    if (!ctx || !rays || !tmax || !states || !t_coll || !w || !steps || !states_out || !T || !ratio_steps || !ratio_states_out ||
-        n < 0)
-        return vpt_fail(VPT_E_INVALID, "vpt_grid_spectral_probe: bad arguments");
-    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "vpt_grid_spectral_probe: no density grid set (vpt_set_density_grid)");
-    if (!is_finite(sigma_a) || !is_finite(sigma_s) || sigma_a < 0 || sigma_s < 0)
-        return vpt_fail(VPT_E_INVALID, "vpt_grid_spectral_probe: sigma_a/sigma_s must be finite and >= 0");
-    const ChromaCoef cc = chroma_coef(ctx, sigma_a, sigma_s);
-    for (int k = 0; k < 3; ++k)
-        if (!(cc.st[k] > 0)) return vpt_fail(VPT_E_INVALID, "vpt_grid_spectral_probe: channel %d has no extinction", k);
-    if (n == 0) return VPT_OK;
-    HIP_OK(hipSetDevice(ctx->device));
-    Staging st;
-    const size_t nn = (size_t)n;
-    vpt_ray* dr = st.alloc<vpt_ray>(nn);
-    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn), *dro = st.alloc<uint64_t>(nn);
-    double* dtm = st.alloc<double>(nn);
+    const char* who = "vpt_grid_spectral_probe";
+    ChromaCoef cc;
+    int rc = grid_probe_open(ctx, who,
+                             ctx && rays && tmax && states && t_coll && w && steps && states_out && T && ratio_steps &&
+                                 ratio_states_out && n >= 0);
+    if (!rc) rc = probe_chroma_coef(ctx, who, sigma_a, sigma_s, &cc);
+    if (rc || n == 0) return rc;
+    ProbeStaging st;
+    rc = st.stage(ctx->device, rays, states, tmax, n);
+    if (rc) return rc;
+    const size_t nn = st.nn;
+    uint64_t* dro = st.alloc<uint64_t>(nn);
     double* db = beta ? st.alloc<double>(3 * nn) : nullptr;
     double* dres = st.alloc<double>(4 * nn);  /* t_coll and the three weights, one array behind the other */
     double* dT = st.alloc<double>(3 * nn);
     uint32_t *dst = st.alloc<uint32_t>(nn), *drs = st.alloc<uint32_t>(nn);
-    st.up(dr, rays, nn);
-    st.up(ds, states, nn);
-    st.up(dtm, tmax, nn);
     if (beta) st.up(db, beta, 3 * nn);
     st.launch([&] {
         const vpt_hetero_unit& u = hetero_unit(ctx, VPT_HETERO_SPECTRAL);
-        u.grid_spectral_track_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, cc, dr, dtm, db, ds, n, dres, dst, dso);
-        u.grid_spectral_ratio_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, cc, dr, dtm, ds, n, dT, drs, dro);
+        u.grid_spectral_track_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, cc, st.dr, st.dtm, db, st.ds, n, dres, dst, st.dso);
+        u.grid_spectral_ratio_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, cc, st.dr, st.dtm, st.ds, n, dT, drs, dro);
     });
     st.down(t_coll, dres, nn);
     st.down(w, dres + nn, 3 * nn);  /* w[c * n + i] */
     st.down(steps, dst, nn);
-    st.down(states_out, dso, nn);
+    st.down(states_out, st.dso, nn);
     st.down(T, dT, 3 * nn);  /* T[c * n + i] */
     st.down(ratio_steps, drs, nn);
     st.down(ratio_states_out, dro, nn);
-    return st.status("vpt_grid_spectral_probe");
+    return st.status(who);
 }
 
 int vpt_grid_residual_probe(vpt_context* ctx, double sigma_t, const vpt_ray* rays, const double* tmax, const uint64_t* states,
                             int n, double* that, double* tauc, uint64_t* states_out, uint32_t* steps)
 {
-    vpt_clear_error();
-    if (!ctx || !rays || !tmax || !states || !that || !tauc || !states_out || n < 0)
-        return vpt_fail(VPT_E_INVALID, "vpt_grid_residual_probe: bad arguments");
-    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "vpt_grid_residual_probe: no density grid set (vpt_set_density_grid)");
+    if (int rc = grid_probe_open(ctx, "vpt_grid_residual_probe",
+                                 ctx && rays && tmax && states && that && tauc && states_out && n >= 0))
+        return rc;
     if (ctx->h_grid.block < 1)
         return vpt_fail(VPT_E_INVALID, "vpt_grid_residual_probe: no majorant block set (vpt_set_grid_majorant_block)");
     if (n == 0) return VPT_OK;
-    HIP_OK(hipSetDevice(ctx->device));
-    Staging st;
-    const size_t nn = (size_t)n;
-    vpt_ray* dr = st.alloc<vpt_ray>(nn);
-    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn);
-    double *dtm = st.alloc<double>(nn), *dth = st.alloc<double>(nn), *dtc = st.alloc<double>(nn);
+    ProbeStaging st;
+    if (int rc = st.stage(ctx->device, rays, states, tmax, n)) return rc;
+    const size_t nn = st.nn;
+    double *dth = st.alloc<double>(nn), *dtc = st.alloc<double>(nn);
     uint32_t* dst = st.alloc_if(steps, nn);
-    st.up(dr, rays, nn);
-    st.up(ds, states, nn);
-    st.up(dtm, tmax, nn);
     st.launch([&] {
-        hetero_unit(ctx, VPT_HETERO_RESIDUAL).grid_residual_probe_launch(ctx->d_grid, sigma_t, dr, dtm, ds, n, dth, dtc, dso, dst);
+        hetero_unit(ctx, VPT_HETERO_RESIDUAL)
+            .grid_residual_probe_launch(ctx->d_grid, sigma_t, st.dr, st.dtm, st.ds, n, dth, dtc, st.dso, dst);
     });
     st.down(that, dth, nn);
     st.down(tauc, dtc, nn);
-    st.down(states_out, dso, nn);
+    st.down(states_out, st.dso, nn);
     st.down(steps, dst, nn);
     return st.status("vpt_grid_residual_probe");
 }
@@ -1434,23 +1430,19 @@ int vpt_grid_emission_probe(vpt_context* ctx, double sigma_t, const vpt_ray* ray
     if (!ctx->has_grid || !ctx->h_grid.emit)
         return vpt_fail(VPT_E_INVALID, "vpt_grid_emission_probe: no emission grid set (vpt_set_emission_grid)");
     if (n == 0) return VPT_OK;
-    HIP_OK(hipSetDevice(ctx->device));
-    Staging st;
-    const size_t nn = (size_t)n;
-    vpt_ray* dr = st.alloc<vpt_ray>(nn);
-    uint64_t *ds = st.alloc<uint64_t>(nn), *dso = st.alloc<uint64_t>(nn);
-    double *dtm = st.alloc<double>(nn), *dtc = st.alloc<double>(nn), *des = st.alloc<double>(nn);
+    ProbeStaging st;
+    if (int rc = st.stage(ctx->device, rays, states, tmax, n)) return rc;
+    const size_t nn = st.nn;
+    double *dtc = st.alloc<double>(nn), *des = st.alloc<double>(nn);
     uint32_t* dst = st.alloc_if(steps, nn);
-    st.up(dr, rays, nn);
-    st.up(ds, states, nn);
-    st.up(dtm, tmax, nn);
     st.launch([&] {
         hetero_unit(VPT_HETERO_FREE, ctx->h_grid.interp != 0, true)
-            .grid_emission_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, sigma_t, dr, dtm, ds, n, dtc, des, dso, dst);
+            .grid_emission_probe_launch(ctx->d_grid, ctx->h_grid.block > 0, sigma_t, st.dr, st.dtm, st.ds, n, dtc, des, st.dso,
+                                        dst);
     });
     st.down(t_coll, dtc, nn);
     st.down(esum, des, nn);
-    st.down(states_out, dso, nn);
+    st.down(states_out, st.dso, nn);
     st.down(steps, dst, nn);
     return st.status("vpt_grid_emission_probe");
 }

@@ -1,12 +1,10 @@
 /*
- * vpt_render_simple.h -- a render's launch parameters (KParams), the per-pixel helpers every render kernel but
- * the pool kernel uses (row mapping, camera ray, pixel store), and the one-lane-per-pixel render kernel, shared by
- * the translation units that instantiate it: vpt_kernels.hip (estimators 0-9) and the density-grid units -- vpt_hetero.hip
- * (estimators 10 and 11), vpt_hetero_eqa.hip (12), vpt_hetero_mis.hip (13) and vpt_hetero_chroma.hip (14), each compiled
- * again by the units that include it (_tl for the trilinear field, _em for the emission grid); the last two overload the
- * kernel with a third argument.  So the code object of vpt_kernels.hip -- the tuned pool kernels and their placement --
- * stays what it was before estimator 10 existed.  render_kernel_simple replaces main()'s OpenMP pixel loop
- * (src/rt.cpp:767-805):
+ * vpt_render_simple.h -- a render's launch parameters (KParams) and the per-pixel helpers every render kernel but the
+ * pool kernel uses (row mapping, camera ray, pixel store), for every unit; and render_kernel_simple, the one-lane-per-pixel
+ * render kernel of estimators 0 to 9, which vpt_kernels.hip instantiates.  The density-grid units (estimators 10 to 16)
+ * have that loop as a body of their own, hetero_simple_render (vpt_hetero_simple.h), so this header knows none of their
+ * estimators and the code object of vpt_kernels.hip -- the tuned pool kernels and their placement -- stays what it was
+ * before estimator 10 existed.  render_kernel_simple replaces main()'s OpenMP pixel loop (src/rt.cpp:767-805):
  * one lane owns one pixel and runs its spp camera samples (src/rt.cpp:786-798) through the estimator,
  * accumulating in FP64 in the reference's order, then writes the average (src/rt.cpp:800) once.
  */
@@ -14,7 +12,8 @@
 #define VPT_RENDER_SIMPLE_H
 
 #include "vpt_device.h"
-#include "vpt_hetero_eqa.h"
+
+struct vpt_grid_view;  /* the density grid as the walkers see it (vpt_grid.h) */
 
 namespace vpt {
 
@@ -34,7 +33,7 @@ struct KParams {
     int32_t cost_surf, cost_med;   /* event scheduler weights */
     int32_t chunk;                 /* samples per partial sum (pool kernel) */
     int32_t taper;                 /* tapered chunk layout (auto mode, vpt_chunks.h) */
-    const vpt_grid_view* grid;     /* estimators 10 to 14: the context's density grid (device), else NULL */
+    const vpt_grid_view* grid;     /* estimators 10 to 16: the context's density grid (device), else NULL */
 };
 
 __host__ __device__ __forceinline__ Medium medium_of(const KParams& P)
@@ -92,10 +91,8 @@ namespace {
 
 using namespace vpt;
 
-/* LM, TL, EM: estimators 10 and 11 only -- the grid has a majorant grid, the field is trilinear, the context holds an
- * emission grid (vpt_hetero.h); estimator 12 takes TL alone (vpt_hetero_eqa.h).  Estimators 13 and 14 have overloads of
- * their own in their units, with the track fraction and the coefficients behind (P, S) */
-template <int EST, bool COUNT, int FB, bool LM = false, bool TL = false, bool EM = false>
+/* estimators 0 to 9 (the density-grid units: vpt_hetero_simple.h) */
+template <int EST, bool COUNT, int FB>
 __global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const DevScene* __restrict__ S)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -122,13 +119,7 @@ __global__ __launch_bounds__(256) void render_kernel_simple(KParams P, const Dev
         smp.cnt.iterations = 0;
         smp.cnt.draw_mismatch = 0;
         const dv3 dir = camera_dir(P, smp, x, row.y);
-        dv3 L;
-        if constexpr (EST == VPT_HETERO_FREE) L = trace_hetero<COUNT, LM, TL>(S, GridTrT<TL, EM>::template load<LM>(P.grid), smp, o, dir, m);
-        else if constexpr (EST == VPT_HETERO_RATIO)
-            L = trace_hetero<COUNT, LM, TL>(S, GridRatioTr<LM, TL, EM>::template load<LM>(P.grid), smp, o, dir, m);
-        else if constexpr (EST == VPT_HETERO_EQUIANGULAR)
-            L = trace_hetero_eqa<COUNT, TL>(S, GridTrT<TL>::template load<false>(P.grid), smp, o, dir, m);
-        else L = trace_sample<EST, COUNT>(S, smp, o, dir, m, EST == 6 ? march_oc : nullptr);
+        const dv3 L = trace_sample<EST, COUNT>(S, smp, o, dir, m, EST == 6 ? march_oc : nullptr);
         acc = add(L, acc);
         if (COUNT) {
             tests += smp.cnt.tests;

@@ -1,9 +1,11 @@
 /*
- * vpt_wave.h -- the persistent-wave render loop, shared by its two kernels: hetero_kernel (vpt_hetero.hip,
- * estimator 10) and render_kernel (vpt_kernels.hip, the A/B path of -DVPT_DEBUG_ENV=1 builds).
+ * vpt_wave.h -- the persistent-wave render loop, shared by its kernels: the density-grid units' seven (hetero_kernel and
+ * hetero_ratio_kernel in vpt_hetero.hip, hetero_eqa_kernel, hetero_mis_kernel, hetero_chroma_kernel, hetero_residual_kernel
+ * and hetero_spectral_kernel in the units of estimators 12 to 16) and render_kernel (vpt_kernels.hip, the A/B path of
+ * -DVPT_DEBUG_ENV=1 builds).
  *
  * Every lane owns one pixel at a time and runs that pixel's camera samples strictly in order (so the
- * per-pixel FP64 sum is render_kernel_simple's, bit for bit), but the wave does not wait for its longest path:
+ * per-pixel FP64 sum is the one-lane-per-pixel kernels', bit for bit), but the wave does not wait for its longest path:
  *   - path regeneration: a lane whose path ends starts its next sample at once;
  *   - a lane that finishes its pixel takes the next one from a device-wide queue (one atomic per
  *     wave, 8x8-tile order for coherent camera rays), so waves drain together at the very end;

@@ -7,7 +7,7 @@ default stream, best and all of --reps repetitions after one untimed run.  Rows:
   c          estimator 10 on a 64^3 procedural cloud in the room (rho_max / mean about 10: most collisions are
              null), with the mean tentative delta-tracking steps per track (65 536 camera samples)
   b16, c16   b and c on 16^3 grids (64 KiB of LDS hold them)
-each of b, c, b16, c16 with hetero_kernel and with VPT_SIMPLE_KERNEL=1 (render_kernel_simple<10>), and with
+each of b, c, b16, c16 with hetero_kernel and with VPT_SIMPLE_KERNEL=1 (render_kernel_simple_hetero), and with
 hetero_kernel on --nolds-lib, a build that reads every grid from global memory
 (bash scripts/build_variant.sh hetero_nolds -DVPT_HETERO_LDS=0; the default stages grids of at most 64 KiB -- b, b16
 and c16 -- in LDS).

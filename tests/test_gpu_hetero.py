@@ -147,7 +147,7 @@ t.close()
 
 
 def _simple_kernel_images(tmp_path):
-    """the render of render_kernel_simple<10>: a fresh process with VPT_SIMPLE_KERNEL=1"""
+    """the render of render_kernel_simple_hetero: a fresh process with VPT_SIMPLE_KERNEL=1"""
     out = str(tmp_path / "simple.npz")
     env = dict(os.environ, VPT_SIMPLE_KERNEL="1")
     code = _CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests"), out=out)

@@ -1,8 +1,9 @@
 """Estimator 14 (VPT_HETERO_CHROMATIC: estimator 10 in a medium whose coefficients depend on the colour channel) on the
 GPU: the chromatic probe against its host build bit for bit, the grey medium against estimator 10 bit for bit,
-hetero_chroma_kernel against render_kernel_simple<14> and the per-sample call, every channel's expectation against
+hetero_chroma_kernel against render_kernel_simple_chroma and the per-sample call, every channel's expectation against
 estimator 10 under that channel's coefficients, the multi-tracer, the errors and the setting.  Shapes: 4096 rays or
-samples per batch, 16 x 16 x 4 spp images; the expectation test alone takes 2^20 samples per trace."""
+samples per batch, 16 x 16 x 4 spp images (and 24 x 20 x 8 where the two render kernels are compared); the expectation
+test alone takes 2^20 samples per trace."""
 import os
 import subprocess
 import sys
@@ -24,6 +25,7 @@ pytestmark = pytest.mark.gpu
 SA, SS = T.SA, T.SS
 ROOM_LO, ROOM_HI = T.ROOM_LO, T.ROOM_HI
 W, H, SPP, SEED = 16, 16, 4, T.SEED
+ODD = (24, 20, 8)  # width and height no multiples of the one-lane-per-pixel kernel's 16 x 16 workgroup
 EST, E10 = "hetero_chromatic", "hetero"
 INTERPS = ("nearest", "trilinear")
 BLOCKS = (0, 2)
@@ -47,8 +49,9 @@ def _reset(t):
     t.set_medium_colour(*GREY)
 
 
-def _cfg(est=EST, fp64=True, sa=SA, ss=SS, **kw):
-    return RenderConfig(width=W, height=H, spp=SPP, estimator=est, sigma_a=sa, sigma_s=ss, seed=SEED, fp64=fp64, **kw)
+def _cfg(est=EST, fp64=True, sa=SA, ss=SS, shape=(W, H, SPP), **kw):
+    w, h, spp = shape
+    return RenderConfig(width=w, height=h, spp=spp, estimator=est, sigma_a=sa, sigma_s=ss, seed=SEED, fp64=fp64, **kw)
 
 
 @pytest.mark.parametrize("case", C.CASES, ids=C.CASE_IDS)
@@ -117,15 +120,19 @@ for ip in M.INTERPS:
         out[f"f64{{ip}}{{block}}"] = t.render(M._cfg())
         out[f"f32{{ip}}{{block}}"] = t.render(M._cfg(fp64=False))
         out[f"work{{ip}}{{block}}"] = np.array(t.count_work(M._cfg()), dtype=np.uint64)
+        out[f"odd64{{ip}}{{block}}"] = t.render(M._cfg(shape=M.ODD))
+        out[f"odd32{{ip}}{{block}}"] = t.render(M._cfg(shape=M.ODD, fp64=False))
+        out[f"oddwork{{ip}}{{block}}"] = np.array(t.count_work(M._cfg(shape=M.ODD)), dtype=np.uint64)
 np.savez({out!r}, **out)
 t.close()
 """
 
 
 def test_kernels_agree(ct, orc_vm, tmp_path):
-    """the coloured medium: hetero_chroma_kernel against render_kernel_simple<14> (a fresh process with
+    """the coloured medium: hetero_chroma_kernel against render_kernel_simple_chroma (a fresh process with
     VPT_SIMPLE_KERNEL=1) and against the in-order per-pixel sum of the per-sample call, bitwise, fp64 and fp32, nearest
-    and trilinear, blocks 0 and 2; count_work is equal; the image is not estimator 10's; the multi-tracer's is the
+    and trilinear, blocks 0 and 2; count_work is equal; the two kernels and count_work agree at 24 x 20 x 8 too, where the
+    one-lane-per-pixel kernel's workgroups overhang the image; the image is not estimator 10's; the multi-tracer's is the
     single tracer's"""
     assert not os.environ.get("VPT_SIMPLE_KERNEL"), "this process must run hetero_chroma_kernel"
     out = str(tmp_path / "simple.npz")
@@ -155,6 +162,11 @@ def test_kernels_agree(ct, orc_vm, tmp_path):
                 assert np.isfinite(img).all() and np.count_nonzero(img) > W * H
                 work = ct.count_work(_cfg())
                 assert work == tuple(int(v) for v in simple["work" + key]) and work[0] > 0 and work[1] > 0
+                odd = ct.render(_cfg(shape=ODD))
+                assert odd.shape == (ODD[1], ODD[0], 3) and np.count_nonzero(odd) > ODD[0] * ODD[1]
+                assert bitwise_equal(odd, simple["odd64" + key]).all(), f"{key}: {(~bitwise_equal(odd, simple['odd64' + key])).sum()} differ"
+                assert bitwise_equal(ct.render(_cfg(shape=ODD, fp64=False)), simple["odd32" + key]).all()
+                assert ct.count_work(_cfg(shape=ODD)) == tuple(int(v) for v in simple["oddwork" + key])
                 assert not bitwise_equal(img, ct.render(_cfg(E10))).all()  # not estimator 10
         assert not bitwise_equal(imgs["nearest0"], imgs["trilinear0"]).all()  # the interpolation is felt
         assert not bitwise_equal(imgs["nearest0"], imgs["nearest2"]).all()    # the block is felt

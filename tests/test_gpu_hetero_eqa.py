@@ -1,6 +1,6 @@
 """Estimator 12 (VPT_HETERO_EQUIANGULAR: estimator 1's control flow in the density grid) on the GPU: the equi-angular
 probe against its host build bit for bit, the reduction to estimator 1 on uniform grids, voxel indexing on a resampled
-field, hetero_eqa_kernel against render_kernel_simple<12> and the per-sample call, the expectation against estimator
+field, hetero_eqa_kernel against render_kernel_simple_eqa and the per-sample call, the expectation against estimator
 10's, the multi-tracer and the errors.  Shapes are those of tests/test_gpu_hetero.py: 4096 samples per batch,
 24 x 20 x 8 spp images; the expectation test alone takes 2^20 samples per estimator."""
 import os
@@ -148,7 +148,7 @@ t.close()
 
 
 def test_kernels_agree(et, orc_vm, tmp_path):
-    """hetero_eqa_kernel against render_kernel_simple<12> (a fresh process with VPT_SIMPLE_KERNEL=1) and against the
+    """hetero_eqa_kernel against render_kernel_simple_eqa (a fresh process with VPT_SIMPLE_KERNEL=1) and against the
     in-order per-pixel sum of the per-sample call, bitwise, fp64 and fp32, nearest and trilinear; count_work is equal"""
     assert not os.environ.get("VPT_SIMPLE_KERNEL"), "this process must run hetero_eqa_kernel"
     out = str(tmp_path / "simple.npz")

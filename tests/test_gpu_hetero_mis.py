@@ -1,6 +1,6 @@
 """Estimator 13 (VPT_HETERO_MIS: the one-sample combination of a delta track and the equi-angular distance under the
 balance heuristic) on the GPU: the MIS probe against its host build bit for bit, the track fraction 0 against estimator
-12 bit for bit, hetero_mis_kernel against render_kernel_simple<13> and the per-sample call, the expectation against
+12 bit for bit, hetero_mis_kernel against render_kernel_simple_mis and the per-sample call, the expectation against
 estimator 10's and the per-sample noise against estimator 12's, the multi-tracer and the errors.  Shapes are those of
 tests/test_gpu_hetero_eqa.py: 4096 samples per batch, 24 x 20 x 8 spp images; the expectation test alone takes 2^20
 samples per estimator."""
@@ -136,7 +136,7 @@ t.close()
 
 
 def test_kernels_agree(mt, orc_vm, tmp_path):
-    """q = 0.5: hetero_mis_kernel against render_kernel_simple<13> (a fresh process with VPT_SIMPLE_KERNEL=1) and
+    """q = 0.5: hetero_mis_kernel against render_kernel_simple_mis (a fresh process with VPT_SIMPLE_KERNEL=1) and
     against the in-order per-pixel sum of the per-sample call, bitwise, fp64 and fp32, nearest and trilinear, blocks 0
     and 2; count_work is equal; the image is neither estimator 10's nor 12's; the fraction and the block are felt;
     interleaved band shards reassemble"""

@@ -1,6 +1,6 @@
 """Estimator 16 (VPT_HETERO_SPECTRAL: estimator 11 in the chromatic medium of estimator 14, by spectral tracking) on the
 GPU: the probe of the two walkers against its host build bit for bit, the grey medium against estimator 11 bit for bit,
-hetero_spectral_kernel against render_kernel_simple<16> and the per-sample call, every channel's expectation against
+hetero_spectral_kernel against render_kernel_simple_spectral and the per-sample call, every channel's expectation against
 estimator 10 under that channel's coefficients, the multi-tracer, the errors and the setting.  Shapes: 4096 rays or
 samples per batch, 20 x 12 x 8 spp images; the expectation test alone takes 2^20 samples per trace."""
 import os
@@ -134,7 +134,7 @@ def _band_rows(off):
 
 def test_kernels_agree(ct, orc_vm, tmp_path):
     """the coloured medium, 20 x 12 (edge tiles that are no multiples of 8): hetero_spectral_kernel against
-    render_kernel_simple<16> (a fresh process with VPT_SIMPLE_KERNEL=1) and against the in-order per-pixel sum of the
+    render_kernel_simple_spectral (a fresh process with VPT_SIMPLE_KERNEL=1) and against the in-order per-pixel sum of the
     per-sample call, bitwise, fp64 and fp32, nearest and trilinear, blocks 0 and 2; count_work is equal; the banded
     shards (band_rows 4, band_stride 2) are the whole image's rows; the image is neither estimator 11's nor 14's"""
     assert not os.environ.get("VPT_SIMPLE_KERNEL"), "this process must run hetero_spectral_kernel"

@@ -1,6 +1,6 @@
 """Local majorants for the delta tracking of estimator 10 on the GPU (vpt_set_grid_majorant_block): the probe
 against its host build bit for bit, the reduction to the global majorant with one super-voxel (per-sample call
-and render), a resampled field with the block doubled, hetero_kernel<LM> against render_kernel_simple<10>, the
+and render), a resampled field with the block doubled, hetero_kernel<LM> against render_kernel_simple_hetero, the
 per-sample call, shards and the multi-tracer, the step counts, and the estimator's mean.  Shapes are those of
 tests/test_gpu_hetero.py: 4096 samples per batch, 24 x 20 x 8 spp images."""
 import ctypes
@@ -125,7 +125,7 @@ t.close()
 
 
 def test_kernels_agree_with_local_majorants(mt, orc_vm, tmp_path):
-    """block 2 on the sparse 6 x 5 x 4 field: hetero_kernel<LM> against render_kernel_simple<10> (a fresh process
+    """block 2 on the sparse 6 x 5 x 4 field: hetero_kernel<LM> against render_kernel_simple_hetero (a fresh process
     with VPT_SIMPLE_KERNEL=1), the in-order per-pixel sum of the per-sample call, the two-shard reassembly and the
     multi-tracer, bitwise (the pattern of tests/test_gpu_hetero.py's test_kernels_agree)"""
     assert not os.environ.get("VPT_SIMPLE_KERNEL"), "this process must run hetero_kernel"

@@ -1,5 +1,5 @@
 """Estimator 11 (VPT_HETERO_RATIO: estimator 10 with every transmittance factor a ratio-tracking estimate) on the
-GPU: the ratio probe against its host build bit for bit, hetero_ratio_kernel against render_kernel_simple<11> and
+GPU: the ratio probe against its host build bit for bit, hetero_ratio_kernel against render_kernel_simple_ratio and
 the per-sample call, the vacuum anchor against estimator 10, resolution independence, the expectation against
 estimator 10's, the multi-tracer and the errors.  Shapes are those of tests/test_gpu_hetero.py: 4096 samples per
 batch, 24 x 20 x 8 spp images; the expectation test alone takes 2^20 samples per estimator."""
@@ -72,7 +72,7 @@ t.close()
 
 
 def test_kernels_agree(rt, orc_vm, tmp_path):
-    """hetero_ratio_kernel against render_kernel_simple<11> (a fresh process with VPT_SIMPLE_KERNEL=1) and against the
+    """hetero_ratio_kernel against render_kernel_simple_ratio (a fresh process with VPT_SIMPLE_KERNEL=1) and against the
     in-order per-pixel sum of the per-sample call, bitwise, at block 0 and 2; count_work (render_kernel_simple's
     counting mode in either process) is equal"""
     assert not os.environ.get("VPT_SIMPLE_KERNEL"), "this process must run hetero_ratio_kernel"

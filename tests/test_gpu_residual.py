@@ -1,6 +1,6 @@
 """Estimator 15 (VPT_HETERO_RESIDUAL: estimator 11 with every transmittance factor a residual ratio-tracking estimate
 over the block minima) on the GPU: the residual probe against its host build bit for bit (control grid staged in LDS
-and read from global memory), hetero_residual_kernel against render_kernel_simple<15> and the per-sample call, the
+and read from global memory), hetero_residual_kernel against render_kernel_simple_residual and the per-sample call, the
 reduction to estimator 11 where the control grid is zero and to estimator 10 in vacuum, the expectation against
 estimator 10's, the multi-tracer and the errors.  Shapes are those of tests/test_gpu_ratio.py: 4096 samples per batch,
 24 x 20 x 8 spp images; the expectation test alone takes 2^20 samples per estimator."""
@@ -92,8 +92,8 @@ t.close()
 
 
 def test_kernels_agree(rt, orc_vm, tmp_path):
-    """hetero_residual_kernel against render_kernel_simple<15> (a fresh process with VPT_SIMPLE_KERNEL=1) and against the
-    in-order per-pixel sum of the per-sample call, bitwise, fp64 and fp32, at block 1 and 2, nearest and trilinear;
+    """hetero_residual_kernel against render_kernel_simple_residual (a fresh process with VPT_SIMPLE_KERNEL=1) and against
+    the in-order per-pixel sum of the per-sample call, bitwise, fp64 and fp32, at block 1 and 2, nearest and trilinear;
     count_work (render_kernel_simple's counting mode in either process) is equal; the image is neither estimator 11's
     nor estimator 10's"""
     assert not os.environ.get("VPT_SIMPLE_KERNEL"), "this process must run hetero_residual_kernel"
