@@ -307,6 +307,25 @@ int vpt_render_multi(const vpt_sphere* spheres, int n, const vpt_params* p, int 
 typedef struct vpt_accum vpt_accum;
 
 int vpt_accum_create(vpt_context* ctx, const vpt_params* p, vpt_accum** out);
+/* The accumulator of the density-grid estimators (10-16), which vpt_accum_create refuses because they have no chunked
+ * sum: the same handle and the same calls below, with a contract of its own.  These estimators sum a pixel's samples
+ * strictly in order, and a pass continues that sum from the state.  For a pixel that holds m levels:
+ *   sum     is acc = L + acc over samples 0 .. mC - 1 of its stream, in order, from zero, whatever calls, tile lists and
+ *           groups brought the levels; the resolve scales by 1 / (double)(mC).  So the pixel is the pixel of
+ *           vpt_render(spp = mC), bit for bit, in FP64 and FP32; C does not change the image, it is the granularity of a
+ *           level and of the error statistic;
+ *   s1, s2  are as above: level k contributes y = lum(c_k), c_k the sum of samples [kC, kC + C) formed as c = L + c from
+ *           zero; s1 = y + s1, s2 = y*y + s2.  sum is not the sum of the c_k here: only the statistic sees the chunks;
+ *   errors, the active rule, vpt_accum_refine and its report are the ones below, unchanged.
+ * C = p->chunk_spp, or min(32, spp) when that is 0; p->spp, the cap, is a multiple of C.  Returns what vpt_render returns
+ * for the same parameters and context (no grid, estimator 15 without a majorant block, a channel without extinction:
+ * VPT_E_INVALID; an emission grid under estimators 12-16: VPT_E_UNSUPPORTED); an estimator below 10 is VPT_E_INVALID
+ * (vpt_accum_create is theirs).  Tile subsets are served for all seven estimators, and tiles at different level counts
+ * are one launch.  Every pass validates again: after vpt_clear_density_grid, or a setting that makes the estimator
+ * invalid, vpt_accum_add / vpt_accum_refine fail with the render's status and change no state.  The scene, the grid and
+ * its settings (majorant block, interpolation, emission, medium colour, track fraction) must not change while the
+ * accumulator holds samples: as for the scene above, that is the caller's error and is not detected. */
+int vpt_accum_create_grid(vpt_context* ctx, const vpt_params* p, vpt_accum** out);
 void vpt_accum_destroy(vpt_accum* a);
 /* the tile grid, the chunk size C and the cap in levels (any pointer may be NULL) */
 int vpt_accum_tiles(const vpt_accum* a, int* tiles_x, int* tiles_y, int* chunk, int* max_levels);

@@ -129,6 +129,7 @@ PROTOTYPES = [
     ("vpt_multi_destroy", None, [c_void_p]),
     ("vpt_render_multi", c_int, [c_void_p, c_int, POINTER(vpt_params), c_int, c_void_p]),
     ("vpt_accum_create", c_int, [c_void_p, POINTER(vpt_params), POINTER(c_void_p)]),
+    ("vpt_accum_create_grid", c_int, [c_void_p, POINTER(vpt_params), POINTER(c_void_p)]),
     ("vpt_accum_destroy", None, [c_void_p]),
     ("vpt_accum_tiles", c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     ("vpt_accum_add", c_int, [c_void_p, c_int, c_void_p, c_int]),

@@ -13,6 +13,27 @@
  * the same pool kernel a one-shot render runs; accum_kernel adds the levels as sum = c + sum, reduce_kernel's
  * order, and resolve_kernel scales by 1 / (double)(levels * C), reduce_kernel's 1 / (double)spp.  A pixel with
  * m levels is therefore the pixel of vpt_render(spp = mC, chunk_spp = C), whatever passes brought the levels.
+ *
+ * The grid accumulator (vpt_accum_create_grid; estimators 10 to 16, the density-grid estimators) is the same handle with
+ * another way of bringing the levels and a contract of its own.  Those estimators render with the persistent-wave loop,
+ * where one lane owns a pixel and sums its samples strictly in order; a pass continues that loop (wave_accum,
+ * vpt_wave_accum.h; vpt_int_grid_pass) from the state, so there is no partial buffer and no fold.  For a pixel that
+ * holds m levels:
+ *   sum     is acc = L + acc over samples 0 .. mC - 1 of its stream, in order, starting from zero, whatever calls, tile
+ *           lists and groups brought the levels; resolve_kernel scales by 1 / (double)(mC), as store_pixel does, so the
+ *           pixel is the pixel of vpt_render(spp = mC), bit for bit, in FP64 and FP32.  C does not change the image;
+ *   s1, s2  are as above: level k contributes y = vpt_accum_lum(c_k), c_k the sum of samples [kC, kC + C) formed as
+ *           c = L + c from zero, folded as s1 = y + s1, s2 = y*y + s2 (vpt_accum_level's lines).  sum is NOT the sum of
+ *           the c_k here: only the statistic sees the chunks;
+ *   errors and policy (vpt_accum_err, the tile maximum in which a NaN wins, vpt_accum_active, the refine loop and its
+ *           report) are vpt_accum.h's, unchanged.
+ * A pass is one launch of the render kernel for all listed tiles -- each at its own level count, each with its own
+ * number of levels to add -- and then grid_tail_kernel (vpt_grid_tail.hip, a unit of its own so that this one's code
+ * object stays what it was), which evaluates the tiles' errors and advances their level counts (the render kernel does
+ * not write them).  Every pass validates the parameters as vpt_render does: when the
+ * grid was cleared, or a setting no longer suits the estimator, the pass fails with the render's status and changes no
+ * state.  The scene, the grid and its settings (block, interpolation, emission, medium colour, track fraction) must stay
+ * as they are while the accumulator holds samples.
  */
 #include <hip/hip_runtime.h>
 
@@ -132,6 +153,7 @@ __global__ __launch_bounds__(256) void resolve_kernel(ResolveParams R)
 struct vpt_accum {
     vpt_context* ctx;
     int device;  /* ctx's, kept so that destroying the accumulator does not need the context */
+    bool grid;   /* vpt_accum_create_grid's: passes continue the persistent-wave loop (no partial buffer) */
     vpt_params p;
     int C, max_levels, rows, w, tiles_x, tiles_y, ntiles;
     double lum_floor;
@@ -140,6 +162,7 @@ struct vpt_accum {
     int* d_levels;
     double* d_err;
     unsigned* d_list;
+    int* d_nadd;  /* the grid accumulator's per-entry counts of a pass */
     unsigned* d_queue;
     double* d_partials;
     size_t partials_bytes;
@@ -180,6 +203,33 @@ int launch_accum(vpt_accum* a, const unsigned* d_list, unsigned n_list, int nlev
     return VPT_OK;
 }
 
+/* add_pass for the grid accumulator, the list sorted (ord): the list and the per-entry counts go up, ONE launch of the
+ * render kernel serves every entry, the tail kernel follows.  Validated first, so a failing pass changes no state */
+int grid_pass(vpt_accum* a, const std::vector<int32_t>& list, const std::vector<int32_t>& nadd, const std::vector<size_t>& ord,
+              const char* who)
+{
+    int rc = vpt_int_check_params(a->ctx, &a->p);
+    if (rc) return rc;
+    const unsigned n = (unsigned)ord.size();
+    std::vector<unsigned> h_list(n);
+    std::vector<int32_t> h_nadd(n);
+    for (size_t i = 0; i < ord.size(); ++i) {
+        h_list[i] = (unsigned)list[ord[i]];
+        h_nadd[i] = nadd[ord[i]];
+    }
+    HIP_OK(hipMemcpy(a->d_list, h_list.data(), sizeof(unsigned) * n, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(a->d_nadd, h_nadd.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    rc = vpt_int_grid_pass(a->ctx, &a->p, a->C, a->d_list, a->d_nadd, n, a->d_levels, a->d_sum, a->d_s12, a->d_queue);
+    if (!rc) {
+        rc = vpt_int_grid_tail(a->w, a->rows, a->tiles_x, a->d_list, a->d_nadd, n, a->d_s12, (double)a->C * a->lum_floor,
+                               a->d_levels, a->d_err);
+    }
+    const hipError_t e = hipDeviceSynchronize();
+    if (rc) return rc;
+    if (e != hipSuccess) return vpt_fail(VPT_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    return download_tiles(a);
+}
+
 /* nadd[i] more levels for tile list[i] (validated by the caller: in range, no duplicates, within the cap,
  * nadd > 0).  Groups of equal (level count, nadd), each: pool pass, then accum_kernel.  Synchronises, refreshes
  * the host mirrors and checks the pool kernel's guard. */
@@ -196,6 +246,7 @@ int add_pass(vpt_accum* a, const std::vector<int32_t>& list, const std::vector<i
         if (nadd[x] != nadd[y]) return nadd[x] < nadd[y];
         return list[x] < list[y];
     });
+    if (a->grid) return grid_pass(a, list, nadd, ord, who);
     if (a->p.medium.estimator > 1) {
         /* the pool kernel's tile-list variant exists for the estimators 0 and 1 (vpt_pool.h): the others take
          * whole-set passes only, i.e. every tile, from one level count, by one number of levels */
@@ -271,28 +322,31 @@ int launch_resolve(vpt_accum* a, void* d_out, hipStream_t stream)
 
 }  // namespace
 
-extern "C" {
-
-int vpt_accum_create(vpt_context* ctx, const vpt_params* p, vpt_accum** out)
+/* both constructors: the parameters against the context as vpt_render checks them, then the estimator's kind */
+static int accum_create(vpt_context* ctx, const vpt_params* p, vpt_accum** out, bool grid, const char* who)
 {
     vpt_clear_error();
-    if (!out) return vpt_fail(VPT_E_INVALID, "vpt_accum_create: out is NULL");
+    if (!out) return vpt_fail(VPT_E_INVALID, "%s: out is NULL", who);
     *out = nullptr;
     int rc = vpt_int_check_params(ctx, p);
     if (rc) return rc;
-    if (p->medium.estimator > 5)
+    if (!grid && p->medium.estimator > 5)
         return vpt_fail(VPT_E_UNSUPPORTED, "vpt_accum_create: estimator %d has no chunks (estimators 0-5 accumulate)",
                         p->medium.estimator);
+    if (grid && p->medium.estimator < VPT_HETERO_FREE)
+        return vpt_fail(VPT_E_INVALID, "vpt_accum_create_grid: estimator %d is not a density-grid estimator (10-16); "
+                        "estimators 0-5 accumulate with vpt_accum_create", p->medium.estimator);
     const int C = p->chunk_spp > 0 ? p->chunk_spp : (p->spp < 32 ? p->spp : 32);
     if (p->spp % C != 0)
-        return vpt_fail(VPT_E_INVALID, "vpt_accum_create: spp %d (the cap) is not a multiple of the chunk %d", p->spp, C);
+        return vpt_fail(VPT_E_INVALID, "%s: spp %d (the cap) is not a multiple of the chunk %d", who, p->spp, C);
     const int rows = vpt_shard_rows(p);
-    if (rows <= 0) return vpt_fail(VPT_E_INVALID, "vpt_accum_create: the shard has no rows");
+    if (rows <= 0) return vpt_fail(VPT_E_INVALID, "%s: the shard has no rows", who);
     if (p->width > 65535 || p->height > 65535) return vpt_fail(VPT_E_INVALID, "width and height must be < 65536");
     HIP_OK(hipSetDevice(vpt_int_device(ctx)));
     vpt_accum* a = new vpt_accum();
     a->ctx = ctx;
     a->device = vpt_int_device(ctx);
+    a->grid = grid;
     a->p = *p;
     a->C = C;
     a->max_levels = p->spp / C;
@@ -303,7 +357,7 @@ int vpt_accum_create(vpt_context* ctx, const vpt_params* p, vpt_accum** out)
     a->ntiles = a->tiles_x * a->tiles_y;
     a->lum_floor = 0.01;
     a->d_sum = a->d_s12 = a->d_err = a->d_partials = nullptr;
-    a->d_levels = nullptr;
+    a->d_levels = a->d_nadd = nullptr;
     a->d_list = a->d_queue = nullptr;
     a->partials_bytes = 0;
     a->levels.assign((size_t)a->ntiles, 0);
@@ -319,6 +373,7 @@ int vpt_accum_create(vpt_context* ctx, const vpt_params* p, vpt_accum** out)
     if (e == hipSuccess) e = hipMalloc((void**)&a->d_levels, nt * sizeof(int));
     if (e == hipSuccess) e = hipMalloc((void**)&a->d_err, nt * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&a->d_list, nt * sizeof(unsigned));
+    if (e == hipSuccess && grid) e = hipMalloc((void**)&a->d_nadd, nt * sizeof(int));
     if (e == hipSuccess) e = hipMalloc((void**)&a->d_queue, sizeof(unsigned));
     if (e == hipSuccess) e = hipMemset(a->d_sum, 0, npix * 3 * sizeof(double));
     if (e == hipSuccess) e = hipMemset(a->d_s12, 0, npix * 2 * sizeof(double));
@@ -326,10 +381,22 @@ int vpt_accum_create(vpt_context* ctx, const vpt_params* p, vpt_accum** out)
     if (e == hipSuccess) e = hipMemcpy(a->d_err, a->err.data(), nt * sizeof(double), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         vpt_accum_destroy(a);
-        return vpt_fail(VPT_E_HIP, "vpt_accum_create: %s", hipGetErrorString(e));
+        return vpt_fail(VPT_E_HIP, "%s: %s", who, hipGetErrorString(e));
     }
     *out = a;
     return VPT_OK;
+}
+
+extern "C" {
+
+int vpt_accum_create(vpt_context* ctx, const vpt_params* p, vpt_accum** out)
+{
+    return accum_create(ctx, p, out, false, "vpt_accum_create");
+}
+
+int vpt_accum_create_grid(vpt_context* ctx, const vpt_params* p, vpt_accum** out)
+{
+    return accum_create(ctx, p, out, true, "vpt_accum_create_grid");
 }
 
 void vpt_accum_destroy(vpt_accum* a)
@@ -344,6 +411,7 @@ void vpt_accum_destroy(vpt_accum* a)
     if (a->d_levels) (void)hipFree(a->d_levels);
     if (a->d_err) (void)hipFree(a->d_err);
     if (a->d_list) (void)hipFree(a->d_list);
+    if (a->d_nadd) (void)hipFree(a->d_nadd);
     if (a->d_queue) (void)hipFree(a->d_queue);
     if (a->d_partials) (void)hipFree(a->d_partials);
     (void)hipSetDevice(prev);

@@ -17,6 +17,14 @@ int vpt_int_check_guard(vpt_context* ctx, const char* who);   /* after a synchro
 int vpt_int_check_params(const vpt_context* ctx, const vpt_params* p);  /* build_kparams' validation */
 int vpt_int_pool_pass(vpt_context* ctx, const vpt_params* p, int C, int k0, int k1, const unsigned* d_tiles,
                       unsigned n_tiles, double* d_partials, unsigned* d_queue);
+/* the grid accumulator's pass (estimators 10 to 16): d_nadd[i] more levels of C samples for tile d_list[i] (NULL: the
+ * shard's tiles in order), continued from d_levels into d_sum / d_s12; validates as vpt_render does */
+int vpt_int_grid_pass(vpt_context* ctx, const vpt_params* p, int C, const unsigned* d_list, const int* d_nadd,
+                      unsigned n_tiles, const int* d_levels, double* d_sum, double* d_s12, unsigned* d_queue);
+/* its tail (vpt_grid_tail.hip), after the pass in stream order: per listed tile the error at levels[tile] + d_nadd[i]
+ * levels from d_s12 (cfloor = (double)C * lum_floor), into d_err[tile], and d_levels[tile] += d_nadd[i] */
+int vpt_int_grid_tail(int w, int rows, int tiles_x, const unsigned* d_list, const int* d_nadd, unsigned n_tiles,
+                      const double* d_s12, double cfloor, int* d_levels, double* d_err);
 
 /* the pool kernel's camera table for origin o: (o - centre, |o - centre|^2) of n spheres, centres `stride`
  * doubles apart (vpt_host.cpp) */

@@ -23,6 +23,7 @@
 #include "vpt_hetero_mis.h"
 #include "vpt_hetero_chroma.h"
 #include "vpt_hetero_launch.h"
+#include "vpt_grid_accum.h"
 
 /* the EST = 1 pool kernel comes from vpt_pool_mis.hip, compiled with flags of its own (VPT_MIS_TU;
  * -DVPT_MIS_TU=0 instantiates it here, as the syntax checks of tests/test_knobs.py do) */
@@ -889,6 +890,56 @@ int vpt_int_pool_pass(vpt_context* ctx, const vpt_params* p, int C, int k0, int 
     case 4: return pool_enqueue<4>(ctx, K, Q, first, units, base, d_queue, nullptr);
     default: return pool_enqueue<5>(ctx, K, Q, first, units, base, d_queue, nullptr);
     }
+}
+
+/* The code object that holds the grid accumulator's render kernel for an estimator, a lookup and, for estimators 10 and
+ * 11, a medium without or with emission (vpt_grid_accum.hip): hetero_unit()'s choice for the continuing loop */
+static vpt_grid_accum_launch* grid_accum_unit(int est, bool tl, bool em)
+{
+    switch (est) {
+    case VPT_HETERO_EQUIANGULAR: return tl ? vpt_int_grid_accum_eqa_tl : vpt_int_grid_accum_eqa;
+    case VPT_HETERO_MIS: return tl ? vpt_int_grid_accum_mis_tl : vpt_int_grid_accum_mis;
+    case VPT_HETERO_CHROMATIC: return tl ? vpt_int_grid_accum_chroma_tl : vpt_int_grid_accum_chroma;
+    case VPT_HETERO_RESIDUAL: return tl ? vpt_int_grid_accum_residual_tl : vpt_int_grid_accum_residual;
+    case VPT_HETERO_SPECTRAL: return tl ? vpt_int_grid_accum_spectral_tl : vpt_int_grid_accum_spectral;
+    default: break;  /* 10 and 11 */
+    }
+    if (em) return tl ? vpt_int_grid_accum_hetero_em_tl : vpt_int_grid_accum_hetero_em;
+    return tl ? vpt_int_grid_accum_hetero_tl : vpt_int_grid_accum_hetero;
+}
+
+/* One pass of the grid accumulator (estimators 10 to 16): d_nadd[i] further levels of C samples for tile d_list[i]
+ * (d_list NULL: the shard's tiles in order, n_tiles of them), from the level counts d_levels holds, into d_sum and
+ * d_s12 (vpt_wave_accum.h).  Validates as a render does, so a grid that was cleared or a setting that no longer suits
+ * the estimator fails here with the render's status before anything is enqueued.  One launch on the default stream;
+ * the caller owns the buffers and synchronises. */
+int vpt_int_grid_pass(vpt_context* ctx, const vpt_params* p, int C, const unsigned* d_list, const int* d_nadd,
+                      unsigned n_tiles, const int* d_levels, double* d_sum, double* d_s12, unsigned* d_queue)
+{
+    KParams K;
+    int rc = build_kparams(ctx, p, (void*)1, K);
+    if (rc) return rc;
+    if (K.est < VPT_HETERO_FREE) return vpt_fail(VPT_E_UNSUPPORTED, "estimator %d has no grid pass", K.est);
+    K.tiles_x = (K.w + 7) / 8;
+    K.tiles_y = (K.shard_rows + 7) / 8;
+    if (C <= 0 || n_tiles == 0 || n_tiles > (unsigned)K.tiles_x * (unsigned)K.tiles_y || K.shard_rows == 0 ||
+        (uint64_t)n_tiles * 64u >= 0xF0000000ull)  /* the u32 queue: every lane adds itself once more after it runs dry */
+        return vpt_fail(VPT_E_INVALID, "bad grid pass (%u tiles, levels of %d samples)", n_tiles, C);
+    K.cost_surf = env_int("VPT_COST_SURF", 1);
+    K.cost_med = env_int("VPT_COST_MED", 1);
+    K.out = nullptr;
+    K.queue = d_queue;
+    GridAccum A;
+    A.C = C;
+    A.n_list = n_tiles;
+    A.list = d_list;
+    A.nadd = d_nadd;
+    A.levels = d_levels;
+    A.sum = d_sum;
+    A.s12 = d_s12;
+    HIP_OK(hipMemsetAsync(d_queue, 0, sizeof(unsigned), nullptr));
+    return grid_accum_unit(K.est, ctx->h_grid.interp != 0, ctx->h_grid.emit != nullptr)(
+        ctx->device, K, ctx->d_scene, A, hetero_args(ctx, K.sigma_a, K.sigma_s, nullptr), nullptr);
 }
 
 extern "C" {

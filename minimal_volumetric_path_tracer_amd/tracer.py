@@ -559,6 +559,16 @@ class Tracer:
         accumulator holds samples."""
         return Accumulator(self, cfg, chunk)
 
+    def grid_accumulator(self, cfg: RenderConfig, chunk: Optional[int] = None) -> "Accumulator":
+        """A progressive accumulator for the density-grid estimators ("hetero" to "hetero_spectral", 10-16), which
+        `accumulator` refuses (vpt_accum_create_grid): the same class with the second of its two contracts.  cfg.spp is
+        the cap, a multiple of the chunk (`chunk`, else cfg.chunk_spp, else min(32, spp)); tile subsets work for every
+        one of these estimators.  Every pass validates as a render does: once the grid is cleared, or a setting makes
+        the estimator invalid, ``add`` and ``refine`` raise the render's error and change nothing.  The scene, the grid
+        and its settings (majorant block, interpolation, emission, medium colour, track fraction) must stay as they are
+        while the accumulator holds samples."""
+        return Accumulator(self, cfg, chunk, grid=True)
+
     def count_work(self, cfg: RenderConfig) -> tuple[int, int]:
         """(ray-sphere tests, estimator iterations) of the reference algorithm for this render."""
         t, i = c_uint64(), c_uint64()
@@ -669,16 +679,24 @@ class Tracer:
 
 class Accumulator:
     """A render that can be continued (vpt_accum_*, include/vpt.h).  Samples arrive in chunk levels of
-    `chunk` samples, for all 8x8 tiles or for chosen ones; a pixel that holds m levels equals, bit for bit,
-    the pixel of ``Tracer.render(spp=m * chunk, chunk_spp=chunk)``.  Tiles are numbered row-major over the
-    shard, ``tiles_x`` per row."""
+    `chunk` samples, for all 8x8 tiles or for chosen ones.  Tiles are numbered row-major over the shard,
+    ``tiles_x`` per row.  Two contracts, by the constructor:
 
-    def __init__(self, tracer: Tracer, cfg: RenderConfig, chunk: Optional[int] = None):
+    ``Tracer.accumulator`` (estimators 0-5, the chunked sum): a pixel that holds m levels equals, bit for bit, the
+    pixel of ``Tracer.render(spp=m * chunk, chunk_spp=chunk)``; its sum is the sum of the levels' chunk sums.
+
+    ``Tracer.grid_accumulator`` (estimators 10-16, the in-order sum): a pixel that holds m levels equals, bit for
+    bit, the pixel of ``Tracer.render(spp=m * chunk)`` -- its sum is ``acc = L + acc`` over its first m * chunk
+    samples in order, so `chunk` does not change the image; it is the granularity of a level and of the error
+    statistic (s1, s2 are folded from the levels' chunk sums as in the first contract)."""
+
+    def __init__(self, tracer: Tracer, cfg: RenderConfig, chunk: Optional[int] = None, grid: bool = False):
         p = cfg.params()
         if chunk is not None:
             p.chunk_spp = int(chunk)
         h = c_void_p()
-        check(lib().vpt_accum_create(tracer._ctx, byref(p), byref(h)))
+        create = lib().vpt_accum_create_grid if grid else lib().vpt_accum_create
+        check(create(tracer._ctx, byref(p), byref(h)))
         self._a = h
         self._tracer = tracer  # the context must outlive the accumulator
         tx, ty, c, ml = c_int(), c_int(), c_int(), c_int()
