@@ -256,6 +256,31 @@ int vpt_set_grid_interpolation(vpt_context* ctx, int mode);
  * grid: setting or clearing that one clears it; vpt_set_grid_majorant_block and vpt_set_grid_interpolation leave it in
  * place.  vpt_trace_batch, vpt_render*, vpt_count_work honour it; the progressive accumulator supports neither estimator. */
 int vpt_set_emission_grid(vpt_context* ctx, const float* eps, const double rgb[3]);
+/* Grids from device memory: vpt_set_density_grid and vpt_set_emission_grid for voxels that already lie on the context's
+ * device (a simulation step, a learned field, a frame of an animated cloud), without a host round trip.  d_density / d_eps:
+ * nx x ny x nz float32 in device memory of the context's device, x fastest; `stream` (a hipStream_t, NULL = the default
+ * stream) is the stream on which their producer wrote them: the call waits for it and is then synchronous, as the host
+ * calls are.  The voxels are COPIED, device to device, into the context's own allocation, so the caller's buffer may be
+ * freed or overwritten once the call has returned; lifetimes, ownership and "must not change while a render is in flight"
+ * are those of the host calls.  The check of the voxels, the maximum and the block maxima and minima are kernels
+ * (csrc/vpt_grid_build.hip) with the host's rules -- among voxels that compare equal (+0.0 and -0.0) the one first in z, y,
+ * x order stays -- so a grid set either way is the same afterwards, bit for bit: every estimator, probe, vpt_count_work
+ * and both accumulators work without knowing.  The context remembers where the grid came from: for a grid set from
+ * device memory vpt_set_grid_majorant_block and vpt_set_grid_interpolation rebuild on the device too, and no voxel
+ * crosses to the host.
+ * Before anything reads the pointer it is checked (hipPointerGetAttributes, hipMemGetAddressRange): not device memory of
+ * the context's device, or not that many bytes of one allocation -> VPT_E_INVALID.  A NULL context, descriptor or pointer
+ * -> VPT_E_INVALID before any GPU call ("... NULL context", "... NULL grid"): clearing stays with
+ * vpt_set_density_grid(ctx, NULL, NULL) and vpt_set_emission_grid(ctx, NULL, NULL).  Bad dimensions, a bad box or a bad
+ * voxel -> VPT_E_INVALID with the host call's message under this function's name (for emission: the lowest bad voxel and
+ * its value); the previous grid, its emission and all settings stay. */
+int vpt_set_density_grid_device(vpt_context* ctx, const vpt_grid_desc* desc, const float* d_density, void* stream);
+int vpt_set_emission_grid_device(vpt_context* ctx, const float* d_eps, const double rgb[3], void* stream);
+/* The majorant grid as the kernels read it, for a grid set either way: the nb[0] x nb[1] x nb[2] block maxima (x fastest)
+ * into maxima and the block minima into minima (either may be NULL), each with room for nbv floats.  Always fills nb and
+ * rho_max.  With block 0 there is no majorant grid: VPT_OK, nb = {0, 0, 0}, nothing copied.  nbv smaller than the grid's
+ * block count, or no density grid -> VPT_E_INVALID. */
+int vpt_get_grid_majorants(vpt_context* ctx, float* maxima, float* minima, size_t nbv, int32_t nb[3], double* rho_max);
 
 /* Renders into a DEVICE buffer on `stream` (a hipStream_t, NULL = default stream); returns
  * after enqueueing.  d_out: vpt_shard_rows(p) * width * 3 elements of fb_format, the
@@ -418,6 +443,16 @@ int vpt_math_probe(vpt_context* ctx, int fn, const double* x, const double* y, d
 int vpt_phase_probe(vpt_context* ctx, double g, const double din[3], const uint64_t* states, int n, double* dirs,
                     uint64_t* states_out, const double* wl, int nw, double* values);
 
+/* The majorant build on the host, on a grid given directly (no GPU needed): for block >= 1 and interp (vpt_grid_interp)
+ * the nbv = nb[0] nb[1] nb[2] block maxima of `density` and behind them the nbv block minima into out (2 nbv floats,
+ * nb[a] = ceil(n[a] / block)), and the largest voxel into rho_max.  vpt_grid_majorant_scatter_host is the build of
+ * vpt_set_density_grid (csrc/vpt_grid.h: every voxel updates the blocks it counts for), vpt_grid_majorant_gather_host
+ * the statement per output that the device builder runs (csrc/vpt_grid_build.h); the two agree bit for bit on every
+ * input.  The dimensions and the box are checked, the voxels are not. */
+int vpt_grid_majorant_scatter_host(const vpt_grid_desc* desc, const float* density, int block, int interp, float* out,
+                                   double* rho_max);
+int vpt_grid_majorant_gather_host(const vpt_grid_desc* desc, const float* density, int block, int interp, float* out,
+                                  double* rho_max);
 /* Density-grid probe (csrc/vpt_grid.h) on the GPU, in the style of vpt_phase_probe: for each of the n rays
  * (unit directions) with surface distance tmax[i] and erand48 state states[i]: tau[i] = the optical depth of
  * the context's grid over t in [0, tmax[i]] (no draw), t_coll[i] = the delta-tracking result for sigma_t (-1:

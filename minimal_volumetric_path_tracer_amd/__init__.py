@@ -16,6 +16,8 @@ from .tracer import (
     grid_emission_probe_host,
     grid_chroma_probe_host,
     grid_eqa_probe_host,
+    grid_majorant_gather_host,
+    grid_majorant_scatter_host,
     grid_mis_probe_host,
     grid_probe_host,
     grid_ratio_probe_host,
@@ -29,6 +31,6 @@ from .tracer import (
 
 __all__ = [
     "FB_F32", "FB_F64", "FREE_FLIGHT", "MIS_EQUIANGULAR", "EXPLICIT_FREE", "IMPLICIT_FREE", "EXPLICIT_EQUIANGULAR", "SURFACE_PT", "RAY_MARCHING",
-    "RAY_MARCHING_SA", "RAY_MARCHING_GLOBAL", "RAY_MARCHING_EXPLICIT", "HETERO_FREE", "HETERO_RATIO", "HETERO_EQUIANGULAR", "HETERO_MIS", "HETERO_CHROMATIC", "HETERO_RESIDUAL", "HETERO_SPECTRAL", "grid_chroma_probe_host", "grid_eqa_probe_host", "grid_mis_probe_host", "grid_probe_host", "grid_ratio_probe_host", "grid_residual_probe_host", "grid_spectral_probe_host", "grid_emission_probe_host", "RAY_DTYPE", "SPHERE_DTYPE", "VPTError", "build_id", "lib",
+    "RAY_MARCHING_SA", "RAY_MARCHING_GLOBAL", "RAY_MARCHING_EXPLICIT", "HETERO_FREE", "HETERO_RATIO", "HETERO_EQUIANGULAR", "HETERO_MIS", "HETERO_CHROMATIC", "HETERO_RESIDUAL", "HETERO_SPECTRAL", "grid_chroma_probe_host", "grid_eqa_probe_host", "grid_mis_probe_host", "grid_probe_host", "grid_ratio_probe_host", "grid_residual_probe_host", "grid_spectral_probe_host", "grid_emission_probe_host", "grid_majorant_gather_host", "grid_majorant_scatter_host", "RAY_DTYPE", "SPHERE_DTYPE", "VPTError", "build_id", "lib",
     "Accumulator", "MultiTracer", "render_multi", "Ray", "RenderConfig", "Sphere", "Tracer", "default_scene", "encode_ppm", "scene", "stream_state", "write_ppm",
 ]

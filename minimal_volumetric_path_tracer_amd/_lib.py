@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_int, c_int32, c_int64, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 import numpy as np
 
@@ -113,6 +113,11 @@ PROTOTYPES = [
     ("vpt_set_grid_majorant_block", c_int, [c_void_p, c_int]),
     ("vpt_set_grid_interpolation", c_int, [c_void_p, c_int]),
     ("vpt_set_emission_grid", c_int, [c_void_p, c_void_p, c_void_p]),
+    ("vpt_set_density_grid_device", c_int, [c_void_p, POINTER(vpt_grid_desc), c_void_p, c_void_p]),
+    ("vpt_set_emission_grid_device", c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vpt_get_grid_majorants", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, POINTER(c_double)]),
+    ("vpt_grid_majorant_scatter_host", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_int, c_void_p, POINTER(c_double)]),
+    ("vpt_grid_majorant_gather_host", c_int, [POINTER(vpt_grid_desc), c_void_p, c_int, c_int, c_void_p, POINTER(c_double)]),
     ("vpt_set_hetero_mis_fraction", c_int, [c_void_p, c_double]),
     ("vpt_set_medium_colour", c_int, [c_void_p, c_void_p, c_void_p]),
     ("vpt_render_device", c_int, [c_void_p, POINTER(vpt_params), c_void_p, c_void_p]),

@@ -202,14 +202,10 @@ static inline int vpt_grid_bad(const int32_t n[3], const double lo[3], const dou
     return 0;
 }
 
-/* host: the view of a valid grid (rho_max scanned here; `rho` is the pointer the walkers will read) */
-static inline void vpt_grid_view_init(vpt_grid_view* G, const int32_t n[3], const double lo[3], const double hi[3],
-                                      const float* density, const float* rho)
+/* host: the view of a valid grid whose largest voxel is mx (`rho` is the pointer the walkers will read) */
+static inline void vpt_grid_view_fill(vpt_grid_view* G, const int32_t n[3], const double lo[3], const double hi[3], float mx,
+                                      const float* rho)
 {
-    const int64_t nv = (int64_t)n[0] * n[1] * n[2];
-    float mx = 0.0f;
-    for (int64_t i = 0; i < nv; ++i)
-        if (density[i] > mx) mx = density[i];
     for (int a = 0; a < 3; ++a) {
         G->n[a] = n[a];
         G->lo[a] = lo[a];
@@ -224,6 +220,17 @@ static inline void vpt_grid_view_init(vpt_grid_view* G, const int32_t n[3], cons
     G->nb[0] = G->nb[1] = G->nb[2] = 0;
     G->block = 0;
     G->emit = 0;
+}
+
+/* host: the same, with rho_max scanned here from the host's copy of the voxels */
+static inline void vpt_grid_view_init(vpt_grid_view* G, const int32_t n[3], const double lo[3], const double hi[3],
+                                      const float* density, const float* rho)
+{
+    const int64_t nv = (int64_t)n[0] * n[1] * n[2];
+    float mx = 0.0f;
+    for (int64_t i = 0; i < nv; ++i)
+        if (density[i] > mx) mx = density[i];
+    vpt_grid_view_fill(G, n, lo, hi, mx, rho);
 }
 
 /* host: the super-voxel counts of block size B >= 1 and the block maxima of `density` into out (nb[2] x nb[1] x

@@ -21,6 +21,7 @@
 
 #include "vpt_accum.h"
 #include "vpt_grid.h"
+#include "vpt_grid_build.h"
 #include "vpt_grid_eqa.h"
 #include "vpt_grid_mis.h"
 #include "vpt_grid_chroma.h"
@@ -43,6 +44,12 @@ int vpt_fail(int code, const char* fmt, ...)
 
 void vpt_clear_error(void) { g_err.clear(); }
 
+/* what is said of the first bad voxel of an emission grid */
+int vpt_int_emission_bad(double value, size_t voxel, const char* who)
+{
+    return vpt_fail(VPT_E_INVALID, "%s: emission value %g at voxel %zu (finite and >= 0)", who, value, voxel);
+}
+
 /* an emission grid and its colour (rgb may be NULL: the voxels only) */
 int vpt_int_emission_check(const float* eps, size_t nv, const double rgb[3], const char* who)
 {
@@ -52,7 +59,7 @@ int vpt_int_emission_check(const float* eps, size_t nv, const double rgb[3], con
                 return vpt_fail(VPT_E_INVALID, "%s: rgb[%d] = %g (finite and >= 0)", who, c, rgb[c]);
     for (size_t i = 0; i < nv; ++i)
         if (!(eps[i] >= 0.0f && eps[i] - eps[i] == 0.0f))
-            return vpt_fail(VPT_E_INVALID, "%s: emission value %g at voxel %zu (finite and >= 0)", who, (double)eps[i], i);
+            return vpt_int_emission_bad((double)eps[i], i, who);
     return VPT_OK;
 }
 
@@ -61,7 +68,13 @@ int vpt_int_grid_check(const vpt_grid_desc* desc, const float* density, const ch
 {
     if (!desc || !density) return vpt_fail(VPT_E_INVALID, "%s: NULL grid", who);
     const int32_t n[3] = {desc->nx, desc->ny, desc->nz};
-    switch (vpt_grid_bad(n, desc->lo, desc->hi, density)) {
+    return vpt_int_grid_verdict(desc, vpt_grid_bad(n, desc->lo, desc->hi, density), who);
+}
+
+/* a verdict of vpt_grid_bad on desc's grid as a status with its message */
+int vpt_int_grid_verdict(const vpt_grid_desc* desc, int verdict, const char* who)
+{
+    switch (verdict) {
     case 1: return vpt_fail(VPT_E_INVALID, "%s: grid %d x %d x %d (each dimension >= 1, at most 2^27 voxels)", who,
                             desc->nx, desc->ny, desc->nz);
     case 2: return vpt_fail(VPT_E_INVALID, "%s: the box must be finite with hi > lo", who);
@@ -376,6 +389,71 @@ int vpt_grid_residual_probe_host(const vpt_grid_desc* desc, const float* density
         if (states_out) states_out[i] = X;
         if (steps) steps[i] = ns;
     }
+    return VPT_OK;
+}
+
+/* how the two probes of the majorant build open: the dimensions and the box are checked, the voxels are not (the builds
+ * are compared on every input) */
+static int majorant_probe_open(const char* who, const vpt_grid_desc* desc, const float* density, int block, int interp,
+                               const float* out, const double* rho_max)
+{
+    vpt_clear_error();
+    if (!desc || !density) return vpt_fail(VPT_E_INVALID, "%s: NULL grid", who);
+    if (!out || !rho_max) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
+    int rc = probe_block_interp_check(who, block, 1, interp);
+    if (rc) return rc;
+    const int32_t n[3] = {desc->nx, desc->ny, desc->nz};
+    return vpt_int_grid_verdict(desc, vpt_grid_bad(n, desc->lo, desc->hi, nullptr), who);
+}
+
+int vpt_grid_majorant_scatter_host(const vpt_grid_desc* desc, const float* density, int block, int interp, float* out,
+                                   double* rho_max)
+{
+    if (int rc = majorant_probe_open("vpt_grid_majorant_scatter_host", desc, density, block, interp, out, rho_max)) return rc;
+    const int32_t n[3] = {desc->nx, desc->ny, desc->nz};
+    vpt_grid_view G;
+    vpt_grid_view_init(&G, n, desc->lo, desc->hi, density, density);
+    *rho_max = G.rho_max;
+    vpt_grid_majorant_control_build(n, block, interp, density, out);
+    return VPT_OK;
+}
+
+int vpt_grid_majorant_gather_host(const vpt_grid_desc* desc, const float* density, int block, int interp, float* out,
+                                  double* rho_max)
+{
+    if (int rc = majorant_probe_open("vpt_grid_majorant_gather_host", desc, density, block, interp, out, rho_max)) return rc;
+    const int32_t n[3] = {desc->nx, desc->ny, desc->nz};
+    int32_t nb[3];
+    vpt_grid_majorant_counts(n, block, nb);
+    const size_t nbv = (size_t)nb[0] * (size_t)nb[1] * (size_t)nb[2], nsx = (size_t)n[2] * (size_t)n[1] * (size_t)nb[0];
+    std::vector<float> sx(2 * nsx);
+    float* sxmax = sx.data();
+    float* sxmin = sxmax + nsx;
+    vpt_gb_acc A, R;
+    vpt_gb_acc_init(&R);  /* rho_max: the maximum of the rows' maxima under the build's rule */
+    for (int64_t r = 0; r < (int64_t)n[2] * n[1]; ++r) {  /* pass X */
+        vpt_gb_scan_x(density + r * n[0], 0, n[0] - 1, 0, 1, &A);
+        vpt_gb_acc_step(&R, A.mx, A.mn, r);
+        for (int32_t bx = 0; bx < nb[0]; ++bx) {
+            int32_t x0, x1;
+            vpt_gb_range(n[0], block, interp, bx, &x0, &x1);
+            vpt_gb_scan_x(density + r * n[0], x0, x1, 0, 1, &A);
+            sxmax[r * nb[0] + bx] = A.mx;
+            sxmin[r * nb[0] + bx] = A.mn;
+        }
+    }
+    *rho_max = (double)R.mx;
+    for (int32_t bz = 0; bz < nb[2]; ++bz)  /* pass YZ */
+        for (int32_t by = 0; by < nb[1]; ++by)
+            for (int32_t bx = 0; bx < nb[0]; ++bx) {
+                int32_t z0, z1, y0, y1;
+                vpt_gb_range(n[2], block, interp, bz, &z0, &z1);
+                vpt_gb_range(n[1], block, interp, by, &y0, &y1);
+                vpt_gb_scan_yz(sxmax, sxmin, n[1], nb[0], bx, z0, z1, y0, y1, 0, 1, &A);
+                const size_t o = ((size_t)bz * (size_t)nb[1] + (size_t)by) * (size_t)nb[0] + (size_t)bx;
+                out[o] = A.mx;
+                out[nbv + o] = A.mn;
+            }
     return VPT_OK;
 }
 

@@ -32,7 +32,21 @@ void vpt_int_cam_table(const double* o, const double* centre, size_t stride, int
 
 /* vpt_grid_bad's verdict on a grid as a vpt_status with its message (vpt_host.cpp) */
 int vpt_int_grid_check(const vpt_grid_desc* desc, const float* density, const char* who);
+/* a verdict of vpt_grid_bad (0 .. 3) on desc's grid as a vpt_status with vpt_int_grid_check's message (vpt_host.cpp) */
+int vpt_int_grid_verdict(const vpt_grid_desc* desc, int verdict, const char* who);
 /* an emission grid of nv voxels and its colour: finite and >= 0, else VPT_E_INVALID with its message (vpt_host.cpp) */
 int vpt_int_emission_check(const float* eps, size_t nv, const double rgb[3], const char* who);
+/* its verdict on a bad voxel: VPT_E_INVALID with the message that names the voxel and its value (vpt_host.cpp) */
+int vpt_int_emission_bad(double value, size_t voxel, const char* who);
+
+/* ---- grids from device memory (vpt_grid_build.hip); both return a hipError_t's value (0: success), enqueue on the
+ * current device's default stream and return once their result is there ---- */
+/* the check and the maximum of nv voxels in device memory: *vmax the largest voxel (from +0.0f under strict >, the host's
+ * rho_max scan) and *bad the lowest linear index of a voxel that is NaN, negative or infinite (vpt_grid_bad's
+ * predicate), -1 where there is none */
+int vpt_int_grid_scan(const float* d_v, long long nv, float* vmax, long long* bad);
+/* vpt_grid_majorant_control_build's 2 nbv floats (vpt_grid.h) for the voxels d_rho of an n[0] x n[1] x n[2] grid, into
+ * d_out, bit for bit (vpt_grid_build.h) */
+int vpt_int_grid_build(const int* n, int B, int tl, const float* d_rho, float* d_out);
 
 #endif

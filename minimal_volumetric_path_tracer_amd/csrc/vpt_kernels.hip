@@ -322,6 +322,9 @@ struct vpt_context {
     vpt_grid_view* d_grid = nullptr;
     float* d_rho = nullptr;
     int has_grid = 0;
+    /* the current grid was set from device memory (vpt_set_density_grid_device): its majorant grid is rebuilt on the
+     * device, from d_rho (vpt_grid_build.hip) */
+    int grid_from_device = 0;
     /* local majorants (vpt_set_grid_majorant_block): the context's block size (0: off), the current grid's
      * block maxima on the device and the host's copy of its view */
     int maj_block = 0;
@@ -1075,6 +1078,7 @@ int vpt_set_density_grid(vpt_context* ctx, const vpt_grid_desc* desc, const floa
         ctx->d_emit = nullptr;  /* the emission grid goes with the grid whose dimensions it has */
         ctx->h_grid.emit = nullptr;
         ctx->has_grid = 0;  /* maj_block and grid_interp stay: the next grid gets its majorant grid and its mode */
+        ctx->grid_from_device = 0;
         return VPT_OK;
     }
     int rc = vpt_int_grid_check(desc, density, "vpt_set_density_grid");
@@ -1105,6 +1109,155 @@ int vpt_set_density_grid(vpt_context* ctx, const vpt_grid_desc* desc, const floa
     ctx->d_emit = nullptr;
     ctx->h_grid = G;
     ctx->has_grid = 1;
+    ctx->grid_from_device = 0;
+    return VPT_OK;
+}
+
+/* majorant_upload for a grid set from device memory: the same 2 nbv floats, built on the device from the context's copy
+ * of the voxels (vpt_grid_build.hip) */
+static hipError_t majorant_build_device(vpt_grid_view* G, int B, const float* d_rho, float** d_maj)
+{
+    int32_t nb[3];
+    vpt_grid_majorant_counts(G->n, B, nb);
+    hipError_t e = hipMalloc((void**)d_maj, 2 * (size_t)nb[0] * (size_t)nb[1] * (size_t)nb[2] * sizeof(float));
+    if (e == hipSuccess) e = (hipError_t)vpt_int_grid_build(G->n, B, G->interp, d_rho, *d_maj);
+    if (e == hipSuccess) vpt_grid_view_set_majorant(G, B, *d_maj);
+    return e;
+}
+
+/* `bytes` bytes at p are device memory of the context's device, inside one allocation: what the _device entry points ask
+ * of a pointer before any kernel or copy touches it */
+static int device_pointer_check(const vpt_context* ctx, const void* p, size_t bytes, const char* who, const char* what)
+{
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    hipError_t e = hipPointerGetAttributes(&at, p);
+    void* base = nullptr;
+    size_t size = 0;
+    if (e == hipSuccess && at.type == hipMemoryTypeDevice && at.device == ctx->device)
+        e = hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)p);
+    else if (e == hipSuccess)
+        e = hipErrorInvalidValue;
+    if (e == hipSuccess && (const char*)p + bytes > (const char*)base + size) e = hipErrorInvalidValue;
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  /* a pointer HIP does not know leaves its error behind */
+        return vpt_fail(VPT_E_INVALID, "%s: %s is not %zu bytes of device memory on device %d", who, what, bytes, ctx->device);
+    }
+    return VPT_OK;
+}
+
+int vpt_set_density_grid_device(vpt_context* ctx, const vpt_grid_desc* desc, const float* d_density, void* stream)
+{
+    const char* who = "vpt_set_density_grid_device";
+    vpt_clear_error();
+    if (!ctx) return vpt_fail(VPT_E_INVALID, "%s: NULL context", who);
+    if (!desc || !d_density) return vpt_fail(VPT_E_INVALID, "%s: NULL grid", who);
+    const int32_t dims[3] = {desc->nx, desc->ny, desc->nz};
+    int rc = vpt_int_grid_verdict(desc, vpt_grid_bad(dims, desc->lo, desc->hi, nullptr), who);
+    if (rc) return rc;
+    const long long nv = (long long)desc->nx * desc->ny * desc->nz;
+    const size_t bytes = (size_t)nv * sizeof(float);
+    HIP_OK(hipSetDevice(ctx->device));
+    rc = device_pointer_check(ctx, d_density, bytes, who, "d_density");
+    if (rc) return rc;
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));  /* the producer has written the voxels */
+    float* d_rho = nullptr;
+    HIP_OK(hipMalloc((void**)&d_rho, bytes));
+    /* the context's own copy first: what is checked is what is kept, whatever the caller does with its tensor */
+    hipError_t e = hipMemcpy(d_rho, d_density, bytes, hipMemcpyDeviceToDevice);
+    float mx = 0.0f;
+    long long bad = -1;
+    if (e == hipSuccess) e = (hipError_t)vpt_int_grid_scan(d_rho, nv, &mx, &bad);
+    if (e == hipSuccess && bad >= 0) {
+        (void)hipFree(d_rho);
+        return vpt_int_grid_verdict(desc, 3, who);
+    }
+    vpt_grid_view G;
+    vpt_grid_view_fill(&G, dims, desc->lo, desc->hi, mx, d_rho);
+    G.interp = ctx->grid_interp;
+    float* d_maj = nullptr;
+    if (e == hipSuccess && ctx->maj_block) e = majorant_build_device(&G, ctx->maj_block, d_rho, &d_maj);
+    if (e == hipSuccess && !ctx->d_grid) e = hipMalloc((void**)&ctx->d_grid, sizeof(vpt_grid_view));
+    if (e == hipSuccess) e = hipDeviceSynchronize();  /* nothing in flight reads the previous grid */
+    if (e == hipSuccess) e = hipMemcpy(ctx->d_grid, &G, sizeof G, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d_rho);
+        if (d_maj) (void)hipFree(d_maj);
+        return vpt_fail(VPT_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    if (ctx->d_rho) (void)hipFree(ctx->d_rho);
+    if (ctx->d_maj) (void)hipFree(ctx->d_maj);
+    if (ctx->d_emit) (void)hipFree(ctx->d_emit);  /* the previous grid's emission: G.emit is NULL */
+    ctx->d_rho = d_rho;
+    ctx->d_maj = d_maj;
+    ctx->d_emit = nullptr;
+    ctx->h_grid = G;
+    ctx->has_grid = 1;
+    ctx->grid_from_device = 1;
+    return VPT_OK;
+}
+
+int vpt_set_emission_grid_device(vpt_context* ctx, const float* d_eps, const double rgb[3], void* stream)
+{
+    const char* who = "vpt_set_emission_grid_device";
+    vpt_clear_error();
+    if (!ctx) return vpt_fail(VPT_E_INVALID, "%s: NULL context", who);
+    if (!d_eps) return vpt_fail(VPT_E_INVALID, "%s: NULL grid", who);  /* clearing stays with vpt_set_emission_grid */
+    if (!rgb) return vpt_fail(VPT_E_INVALID, "%s: rgb is NULL", who);
+    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "%s: no density grid set (vpt_set_density_grid)", who);
+    int rc = vpt_int_emission_check(nullptr, 0, rgb, who);  /* the colour; the voxels below */
+    if (rc) return rc;
+    vpt_grid_view G = ctx->h_grid;
+    const long long nv = (long long)G.n[0] * G.n[1] * G.n[2];
+    const size_t bytes = (size_t)nv * sizeof(float);
+    HIP_OK(hipSetDevice(ctx->device));
+    rc = device_pointer_check(ctx, d_eps, bytes, who, "d_eps");
+    if (rc) return rc;
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+    const double head[VPT_EMIT_HEAD] = {rgb[0], rgb[1], rgb[2], 0.0};
+    double* d_emit = nullptr;
+    HIP_OK(hipMalloc((void**)&d_emit, sizeof head + bytes));
+    float* d_vox = (float*)(d_emit + VPT_EMIT_HEAD);
+    hipError_t e = hipMemcpy(d_emit, head, sizeof head, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_vox, d_eps, bytes, hipMemcpyDeviceToDevice);
+    float mx = 0.0f, at_bad = 0.0f;
+    long long bad = -1;
+    if (e == hipSuccess) e = (hipError_t)vpt_int_grid_scan(d_vox, nv, &mx, &bad);
+    if (e == hipSuccess && bad >= 0) e = hipMemcpy(&at_bad, d_vox + bad, sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && bad >= 0) {
+        (void)hipFree(d_emit);
+        return vpt_int_emission_bad((double)at_bad, (size_t)bad, who);
+    }
+    G.emit = d_vox;
+    if (e == hipSuccess) e = hipDeviceSynchronize();  /* nothing in flight reads the view or the previous emission grid */
+    if (e == hipSuccess) e = hipMemcpy(ctx->d_grid, &G, sizeof G, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d_emit);
+        return vpt_fail(VPT_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    if (ctx->d_emit) (void)hipFree(ctx->d_emit);
+    ctx->d_emit = d_emit;
+    ctx->h_grid = G;
+    return VPT_OK;
+}
+
+int vpt_get_grid_majorants(vpt_context* ctx, float* maxima, float* minima, size_t nbv, int32_t nb[3], double* rho_max)
+{
+    const char* who = "vpt_get_grid_majorants";
+    vpt_clear_error();
+    if (!ctx) return vpt_fail(VPT_E_INVALID, "%s: NULL context", who);
+    if (!nb || !rho_max) return vpt_fail(VPT_E_INVALID, "%s: bad arguments", who);
+    if (!ctx->has_grid) return vpt_fail(VPT_E_INVALID, "%s: no density grid set (vpt_set_density_grid)", who);
+    const vpt_grid_view& G = ctx->h_grid;
+    for (int a = 0; a < 3; ++a) nb[a] = G.nb[a];
+    *rho_max = G.rho_max;
+    if (!G.block) return VPT_OK;
+    const size_t need = (size_t)G.nb[0] * (size_t)G.nb[1] * (size_t)G.nb[2];
+    if (nbv < need) return vpt_fail(VPT_E_INVALID, "%s: room for %zu blocks, the majorant grid has %zu", who, nbv, need);
+    HIP_OK(hipSetDevice(ctx->device));
+    HIP_OK(hipDeviceSynchronize());
+    if (maxima) HIP_OK(hipMemcpy(maxima, ctx->d_maj, need * sizeof(float), hipMemcpyDeviceToHost));
+    if (minima) HIP_OK(hipMemcpy(minima, ctx->d_maj + need, need * sizeof(float), hipMemcpyDeviceToHost));
     return VPT_OK;
 }
 
@@ -1159,7 +1312,9 @@ int vpt_set_grid_majorant_block(vpt_context* ctx, int block)
     vpt_grid_view G = ctx->h_grid;
     float* d_maj = nullptr;
     hipError_t e = hipSuccess;
-    if (block) {  /* the block maxima are scanned on the host, from the device's copy of the voxels */
+    if (block && ctx->grid_from_device) {  /* built where the voxels are */
+        e = majorant_build_device(&G, block, ctx->d_rho, &d_maj);
+    } else if (block) {  /* the block maxima are scanned on the host, from the device's copy of the voxels */
         const size_t nv = (size_t)G.n[0] * (size_t)G.n[1] * (size_t)G.n[2];
         std::vector<float> rho(nv);
         e = hipMemcpy(rho.data(), ctx->d_rho, nv * sizeof(float), hipMemcpyDeviceToHost);
@@ -1220,7 +1375,9 @@ int vpt_set_grid_interpolation(vpt_context* ctx, int mode)
     G.interp = mode;
     float* d_maj = nullptr;
     hipError_t e = hipSuccess;
-    if (G.block) {  /* the majorant grid follows the mode: rebuilt from the device's copy of the voxels */
+    if (G.block && ctx->grid_from_device) {  /* the majorant grid follows the mode: built where the voxels are */
+        e = majorant_build_device(&G, G.block, ctx->d_rho, &d_maj);
+    } else if (G.block) {  /* the majorant grid follows the mode: rebuilt from the device's copy of the voxels */
         const size_t nv = (size_t)G.n[0] * (size_t)G.n[1] * (size_t)G.n[2];
         std::vector<float> rho(nv);
         e = hipMemcpy(rho.data(), ctx->d_rho, nv * sizeof(float), hipMemcpyDeviceToHost);

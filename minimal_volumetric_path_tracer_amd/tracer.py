@@ -73,13 +73,18 @@ def stream_state(seed: int, pixel_idx: int, sample: int) -> int:
 def _grid_args(rho, lo, hi) -> tuple[_lib.vpt_grid_desc, np.ndarray]:
     """(vpt_grid_desc, float32 voxels) of a density array of shape [nz, ny, nx] (x fastest) in the box [lo, hi]."""
     r = np.ascontiguousarray(rho, dtype=np.float32)
+    return _grid_desc(r, lo, hi), r
+
+
+def _grid_desc(r, lo, hi) -> _lib.vpt_grid_desc:
+    """the vpt_grid_desc of voxels r (an array or a tensor) of shape [nz, ny, nx] in the box [lo, hi]"""
     if r.ndim != 3:
         raise ValueError("rho must have shape [nz, ny, nx]")
     d = _lib.vpt_grid_desc()
     d.nz, d.ny, d.nx = r.shape
     d.lo[:] = [float(v) for v in lo]
     d.hi[:] = [float(v) for v in hi]
-    return d, r
+    return d
 
 
 def _probe_args(rays, tmax, states):
@@ -285,16 +290,76 @@ def grid_spectral_probe_host(rho, lo, hi, sigma_a: float, sigma_s: float, rays, 
     return out
 
 
+def _emission_colour(rgb) -> np.ndarray:
+    c = np.ascontiguousarray(rgb, dtype=np.float64)
+    if c.shape != (3,):
+        raise _lib.VPTError(_lib.VPT_E_INVALID, f"emission colour of shape {c.shape}: three numbers (r, g, b)")
+    return c
+
+
 def _emission_args(eps, rgb, shape) -> tuple[np.ndarray, np.ndarray]:
     """(float32 voxels, float64 colour) of an emission grid for a density grid of `shape` (None: not known here, the
     library says what is missing); another shape or a colour that is not three numbers is VPT_E_INVALID"""
     e = np.ascontiguousarray(eps, dtype=np.float32)
     if shape is not None and e.shape != tuple(shape):
         raise _lib.VPTError(_lib.VPT_E_INVALID, f"emission grid of shape {e.shape}: the density grid's is {tuple(shape)}")
-    c = np.ascontiguousarray(rgb, dtype=np.float64)
-    if c.shape != (3,):
-        raise _lib.VPTError(_lib.VPT_E_INVALID, f"emission colour of shape {c.shape}: three numbers (r, g, b)")
-    return e, c
+    return e, _emission_colour(rgb)
+
+
+def _on_gpu(x) -> bool:
+    """a torch tensor in GPU memory, told by its attributes: torch is not imported here"""
+    return bool(getattr(x, "is_cuda", False)) and hasattr(x, "data_ptr")
+
+
+def _device_voxels(x, device: int):
+    """(float32 contiguous tensor, its producer's stream) of a GPU tensor of voxels for the tracer on `device`; made
+    float32 and contiguous on the device where it is not (a torch op on the current stream, no host round trip).  A
+    tensor on another device is VPT_E_INVALID."""
+    import torch  # the tensor is torch's, so it is there
+
+    if x.device.index != device:
+        raise _lib.VPTError(_lib.VPT_E_INVALID, f"tensor on {x.device}: the tracer's device is cuda:{device}")
+    t = x.detach().to(dtype=torch.float32).contiguous()
+    return t, torch.cuda.current_stream(x.device).cuda_stream
+
+
+def _emission_shape_check(eps, shape) -> None:
+    """_emission_args' refusal of another shape, for a GPU tensor"""
+    if shape is not None and tuple(eps.shape) != tuple(shape):
+        raise _lib.VPTError(_lib.VPT_E_INVALID,
+                            f"emission grid of shape {tuple(eps.shape)}: the density grid's is {tuple(shape)}")
+
+
+def _refuse_gpu_tensor(*grids) -> None:
+    """MultiTracer's grids come from host arrays: a set from device memory would need one peer copy per context"""
+    if any(_on_gpu(g) for g in grids):
+        raise _lib.VPTError(_lib.VPT_E_UNSUPPORTED, "MultiTracer does not take a grid from a GPU tensor (device memory): "
+                            "pass a host array, or use a Tracer per device")
+
+
+def _majorant_host(fn, rho, block: int, interpolation: str):
+    mode = _interp_mode(interpolation)
+    d, r = _grid_args(rho, (0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
+    if int(block) < 1:
+        raise _lib.VPTError(_lib.VPT_E_INVALID, f"block {block} (>= 1)")
+    nb = tuple((n - 1) // int(block) + 1 for n in r.shape)
+    out = np.zeros((2,) + nb, dtype=np.float32)
+    rho_max = ctypes.c_double()
+    check(fn(byref(d), r.ctypes.data, int(block), mode, out.ctypes.data, byref(rho_max)))
+    return out[0], out[1], rho_max.value
+
+
+def grid_majorant_gather_host(rho, block: int, interpolation: str = "nearest"):
+    """csrc/vpt_grid_build.h on the host (vpt_grid_majorant_gather_host, no GPU): the block maxima and minima of rho
+    ([nz, ny, nx]) for super-voxels of `block` voxels per axis, stated per output as the device builder runs them.
+    Returns (maxima[nbz, nby, nbx], minima[nbz, nby, nbx], rho_max), float32 and a float."""
+    return _majorant_host(lib().vpt_grid_majorant_gather_host, rho, block, interpolation)
+
+
+def grid_majorant_scatter_host(rho, block: int, interpolation: str = "nearest"):
+    """grid_majorant_gather_host's quantities from the build that set_density_grid runs on a host array
+    (vpt_grid_majorant_scatter_host: csrc/vpt_grid.h's vpt_grid_majorant_control_build and rho_max scan)."""
+    return _majorant_host(lib().vpt_grid_majorant_scatter_host, rho, block, interpolation)
 
 
 def grid_emission_probe_host(rho, eps, lo, hi, sigma_t: float, rays, tmax, states, majorant_block: int = 0,
@@ -408,13 +473,31 @@ class Tracer:
         majorant_block: set_majorant_block for this and later grids (None leaves the tracer's setting alone); a
         grid that is rejected leaves the setting as it was.  interpolation: set_grid_interpolation in the same way.
         emission: set_emission_grid(emission, emission_rgb) for this grid; a new density grid always drops the
-        previous grid's emission."""
-        d, r = _grid_args(rho, lo, hi)
-        if emission is not None:
-            _emission_args(emission, emission_rgb, r.shape)  # rejected before anything is uploaded
+        previous grid's emission.
+        rho and emission may also be torch tensors on the tracer's GPU (a CPU tensor is an array like any other): the
+        voxels are then copied device to device, and checked, scanned and built into majorants by kernels
+        (vpt_set_density_grid_device), with the same result bit for bit.  The tensor is made float32 and contiguous on
+        the device where it is not, the call waits for torch's current stream, and the tensor may be freed or
+        overwritten afterwards; a tensor on another device is VPT_E_INVALID."""
+        if _on_gpu(rho):
+            d = _grid_desc(rho, lo, hi)
+            r, stream = _device_voxels(rho, self.device)
+            shape = tuple(r.shape)
+        else:
+            d, r = _grid_args(rho, lo, hi)
+            shape = r.shape
+        if emission is not None:  # rejected before anything is uploaded
+            if _on_gpu(emission):
+                _emission_shape_check(emission, shape)
+                _emission_colour(emission_rgb)
+            else:
+                _emission_args(emission, emission_rgb, shape)
         def upload():  # the shape goes with the grid the context holds, whatever the settings after it do
-            check(lib().vpt_set_density_grid(self._ctx, byref(d), r.ctypes.data))
-            self._grid_shape = r.shape
+            if _on_gpu(rho):
+                check(lib().vpt_set_density_grid_device(self._ctx, byref(d), r.data_ptr(), stream))
+            else:
+                check(lib().vpt_set_density_grid(self._ctx, byref(d), r.ctypes.data))
+            self._grid_shape = shape
 
         _set_grid_with_block(self, majorant_block, upload, interpolation)
         if emission is not None:
@@ -425,7 +508,14 @@ class Tracer:
         looked up as the density is, and a colour rgb (finite, >= 0).  The medium emits sigma_a rho(x) eps(x) rgb per
         unit length (Kirchhoff's form: no absorption or no density, no emission), scored on every tentative collision
         of the delta track without a random draw, so paths and draw counts stay what they are.  Needs a density grid
-        and goes with it: a new or cleared density grid drops it; the majorant block and the interpolation do not."""
+        and goes with it: a new or cleared density grid drops it; the majorant block and the interpolation do not.
+        eps may be a torch tensor on the tracer's GPU, as set_density_grid's rho may (vpt_set_emission_grid_device)."""
+        if _on_gpu(eps):
+            _emission_shape_check(eps, self._grid_shape)
+            c = _emission_colour(rgb)
+            e, stream = _device_voxels(eps, self.device)
+            check(lib().vpt_set_emission_grid_device(self._ctx, e.data_ptr(), c.ctypes.data, stream))
+            return
         e, c = _emission_args(eps, rgb, self._grid_shape)
         check(lib().vpt_set_emission_grid(self._ctx, e.ctypes.data, c.ctypes.data))
 
@@ -464,6 +554,23 @@ class Tracer:
     def clear_density_grid(self) -> None:
         check(lib().vpt_set_density_grid(self._ctx, None, None))
         self._grid_shape = None
+
+    def grid_majorants(self):
+        """The majorant grid as the kernels read it (vpt_get_grid_majorants), however the density grid was set:
+        (maxima[nbz, nby, nbx], minima[nbz, nby, nbx], rho_max), float32 arrays and a float; (None, None, rho_max) with
+        majorant block 0.  Needs a density grid."""
+        nb = (ctypes.c_int32 * 3)()
+        rho_max = ctypes.c_double()
+        B = self._majorant_block
+        if not B or self._grid_shape is None:
+            check(lib().vpt_get_grid_majorants(self._ctx, None, None, 0, nb, byref(rho_max)))
+            return None, None, rho_max.value
+        shape = tuple((n - 1) // B + 1 for n in self._grid_shape)
+        out = np.zeros((2,) + shape, dtype=np.float32)
+        check(lib().vpt_get_grid_majorants(self._ctx, out[0].ctypes.data, out[1].ctypes.data, out[0].size, nb,
+                                           byref(rho_max)))
+        assert (nb[2], nb[1], nb[0]) == shape, (tuple(nb), shape)
+        return out[0], out[1], rho_max.value
 
     def grid_emission_probe(self, sigma_t: float, rays, tmax, states):
         """grid_emission_probe_host's quantities for the tracer's density and emission grids, majorant block and
@@ -795,7 +902,8 @@ class MultiTracer:
 
     def set_density_grid(self, rho, lo, hi, majorant_block: Optional[int] = None,
                          interpolation: Optional[str] = None, emission=None, emission_rgb=(1, 1, 1)) -> None:
-        """Tracer.set_density_grid on every rank's context."""
+        """Tracer.set_density_grid on every rank's context (arrays only: a GPU tensor is VPT_E_UNSUPPORTED)."""
+        _refuse_gpu_tensor(rho, emission)
         d, r = _grid_args(rho, lo, hi)
         if emission is not None:
             _emission_args(emission, emission_rgb, r.shape)
@@ -809,7 +917,8 @@ class MultiTracer:
             self.set_emission_grid(emission, emission_rgb)
 
     def set_emission_grid(self, eps, rgb=(1, 1, 1)) -> None:
-        """Tracer.set_emission_grid on every rank's context."""
+        """Tracer.set_emission_grid on every rank's context (arrays only, as set_density_grid)."""
+        _refuse_gpu_tensor(eps)
         e, c = _emission_args(eps, rgb, self._grid_shape)
         check(lib().vpt_multi_set_emission_grid(self._m, e.ctypes.data, c.ctypes.data))
 
